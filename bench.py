@@ -12,6 +12,13 @@ scope.
 Launch: python bench.py [--gpus N --steps K --warmup W].  N > 1: bench.py starts the N ranks itself
 (a child `torch.distributed.run`, one process per GPU), or runs as one rank of an outside launcher
 whose WORLD_SIZE must equal N (a mismatch is an error).  Prints one JSON line on rank 0.
+
+A plain run sets up, warms up, times the K steps and prints the headline line (`value`,
+`ms_per_step`).  `--full` adds everything else, each leg a run of its own after the timed steps: the
+shard check and byte-level parity gate against the C restatement, the serial kernel pass behind
+`roofline` and `kernels_ms_per_step`, the helper-only variant, the CPU baseline and the HPKE-open
+stage (`--prof-steps`, `--helper-only`, `--cpu-baseline`, `--hpke` tune those legs under `--full`).
+`--dump-outputs DIR` writes what the last timed step computed as DIR/<name>.npy (see dump_outputs).
 """
 import argparse
 import ctypes
@@ -232,6 +239,43 @@ def oracle_transcript_gate(vdaf, kind, bits, length, chunk, vk, syn, d_pub, d_li
             f"== Python oracle run_vdaf (XofTurboShake128)")
 
 
+DUMP_ROWS = 1024         # --dump-outputs: report rows sampled from each per-report array
+DUMP_BUDGET = 64 << 20   # --dump-outputs: bytes written in all, at most
+
+
+def dump_rows(n, row_bytes):
+    """The report rows --dump-outputs keeps of an n-report batch: every row of a small batch,
+    else a fixed sample (seeded, sorted, first and last row included), cut so that float32 copies
+    of `row_bytes` bytes per row fill at most half of DUMP_BUDGET (the rest covers the per-batch
+    arrays)."""
+    k = max(2, min(DUMP_ROWS, DUMP_BUDGET // 2 // (4 * max(1, row_bytes))))
+    if n <= k:
+        return np.arange(n, dtype=np.int64)
+    rows = np.random.default_rng(0x5eed).choice(n - 2, k - 2, replace=False) + 1
+    return np.sort(np.concatenate([[0, n - 1], rows])).astype(np.int64)
+
+
+def dump_outputs(path, rank, world, per_report, per_batch):
+    """Write the outputs of the last timed step as <path>/<name>.npy (rank r > 0 of an N-rank run:
+    <name>.rank<r>.npy).  `per_report`: {name: (n, width) uint8 device tensor or None}, of which
+    the rows dump_rows picks are kept (`sample_rows` holds their indices); `per_batch`: {name:
+    numpy array}, kept whole.  Bytes are stored one per float32 (exact), counts as float64."""
+    import torch
+    os.makedirs(path, exist_ok=True)
+    per_report = {k: v for k, v in per_report.items() if v is not None}
+    n = next(iter(per_report.values())).shape[0]
+    rows = dump_rows(n, sum(v.reshape(n, -1).shape[1] for v in per_report.values()))
+    idx = torch.from_numpy(rows)
+    arrays = {"sample_rows": rows.astype(np.float64)}
+    for name, t in per_report.items():
+        arrays[name] = t.reshape(n, -1)[idx.to(t.device)].cpu().numpy().astype(np.float32)
+    arrays.update(per_batch)
+    assert sum(a.nbytes for a in arrays.values()) <= DUMP_BUDGET, "dump exceeds its budget"
+    for name, a in arrays.items():
+        assert a.dtype in (np.float32, np.float64), name
+        np.save(os.path.join(path, name + (f".rank{rank}" if rank else "") + ".npy"), a)
+
+
 def free_port() -> int:
     import socket
     with socket.socket(socket.AF_INET, socket.SOCK_STREAM) as s:
@@ -262,6 +306,15 @@ def main():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=5)
     ap.add_argument("--warmup", type=int, default=1)
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run the parity gates against the C "
+                         "restatement, the serial kernel pass (roofline, kernels_ms_per_step), the "
+                         "helper-only variant, the CPU baseline and the HPKE-open stage, and report "
+                         "them in the JSON line; a plain run prints the headline figure only")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the outputs of the last timed step (prep shares, prep messages and "
+                         "statuses of a fixed sample of reports; both aggregate shares, report "
+                         "counts and report-ID checksums) as DIR/<name>.npy")
     ap.add_argument("--config", default="sumvec", choices=list(CONFIGS))
     ap.add_argument("--reports", type=int, default=0, help="reports per GPU per step (B)")
     ap.add_argument("--leader-pitch", type=int, default=0,
@@ -308,6 +361,8 @@ def main():
                          "stream) and one contiguous slice of the batch each (Janus "
                          "max_concurrent_job_workers)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
     if args.overlap < 0:  # profiles/r04/ab_r4u_*.log
         args.overlap = 0 if args.config == "sumvec" else 1
 
@@ -410,7 +465,9 @@ def main():
     del d_rand
     gen_s = time.time() - t0
     U = min(U, B)  # CPU-baseline sample size
-    if turbo:
+    if not args.full:  # a plain run checks nothing against the restatements
+        pass
+    elif turbo:
         turbo_gate = oracle_transcript_gate(vdaf, kind, bits, length, chunk, vk, syn, d_pub, d_lin,
                                             d_hin, n=2)
     else:
@@ -650,7 +707,7 @@ def main():
     # HIP-event spans of the timed schedule: with two contexts co-running (--overlap >= 1) a
     # kernel's span also covers the time it waited behind, or shared the CUs with, the other
     # context's kernel, so these are spans, not kernel durations
-    kt_timed = read_prof(args.prof_steps > 0)
+    kt_timed = read_prof(args.full and args.prof_steps > 0)
     if dist is not None:
         t = torch.tensor([elapsed], dtype=torch.float64)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
@@ -662,6 +719,75 @@ def main():
         for wk in workers:
             for v_ in (wk.v, wk.hv):
                 v_.set_async(False)
+
+    # ---- --dump-outputs: what a caller of the timed path holds after its last step -------------
+    if args.dump_outputs:
+        u8 = lambda b: np.frombuffer(b, np.uint8).astype(np.float32)
+        aggs = {a: [getattr(wk, a).read(0) for wk in workers] for a in ("lagg", "hagg")}
+        cks = {a: [getattr(wk, a).read_reports(0) for wk in workers] for a in ("lagg", "hagg")}
+        last_lst = pipe["lst"][(args.steps - 1) % 2] if pipe is not None else d_lst
+        dump_outputs(
+            args.dump_outputs, rank, world,
+            {"leader_prep_shares": d_lprep,
+             "helper_prep_shares": d_hprep2 if pipe is not None else d_hprep,
+             "prep_messages": d_msgs if s.prep_msg else None,
+             "leader_status": last_lst, "helper_status": d_hst},
+            {"status_nonzero": np.array([int((last_lst != 0).sum().item()),
+                                         int((d_hst != 0).sum().item())], np.float64),
+             # one row per job worker: running aggregates over the warm-up and the timed steps
+             "leader_aggregate_share": np.stack([u8(a) for a, _ in aggs["lagg"]]),
+             "helper_aggregate_share": np.stack([u8(a) for a, _ in aggs["hagg"]]),
+             "aggregate_report_counts": np.array([[c for _, c in aggs[a]] for a in
+                                                  ("lagg", "hagg")], np.float64),
+             "leader_report_checksum": np.stack([u8(c) for c, _ in cks["lagg"]]),
+             "helper_report_checksum": np.stack([u8(c) for c, _ in cks["hagg"]])})
+
+    reports = args.steps * B * world
+    value = reports / elapsed
+    ms_per_step = elapsed / args.steps * 1e3
+    out = {
+        "metric": (METRIC if args.config == "sumvec" and not turbo else
+                   f"reports/sec prepared+aggregated, {label}" + (", XofTurboShake128" if turbo
+                                                                  else "")),
+        "value": round(value, 2),
+        "unit": "reports/s",
+        "n_gpus": world,
+        "steps": args.steps,
+        "warmup": args.warmup,
+        "ms_per_step": round(ms_per_step, 3),
+        "higher_is_better": True,
+        "scaling": "weak",
+        "vs_baseline": None,
+        "dtype": "u128 (Field128 mod p)" if s.field_size == 16 else "u64 (Field64 mod p)",
+        "data": f"synthetic: {B} distinct reports/GPU (SURVEY §8(d) recipe; shares made by the GPU "
+                f"client shard), resident in HBM",
+        "config": {"workload": label, "xof": "XofTurboShake128" if turbo else "XofShake128",
+                   "engine_options": dict(engine_opts),
+                   "schedule": f"overlap {args.overlap}" + (", async calls" if async_calls else ""),
+                   "reports_per_gpu_per_step": B, "job_workers_per_gpu": W,
+                   "parallelism": f"report-sharded x{world}, {W} job stream(s)/GPU, "
+                                  + ("RCCL all-gather merge" if args.merge == "rccl" else
+                                     "gloo rehearsal (ranks share GPUs, host merge)")},
+        "full": args.full,
+        # HIP-event spans in the timed (possibly co-running) schedule: a span includes time spent
+        # queued behind or sharing the CUs with the other context's kernels
+        "kernels_timed_span_ms_per_step": {k: round(v[0] / args.steps, 3)
+                                           for k, v in kt_timed.items()},
+        "gen_seconds": round(gen_s, 1),
+        # the engine build that ran: SHA-256 of its sources + flags (janus_amd/_lib.py)
+        "build_hash": L.prio3gpu_build_hash().decode(),
+    }
+
+    def finish():
+        if rank == 0:
+            print(json.dumps(out), flush=True)
+        if comm is not None:
+            comm.close()
+        if dist is not None:
+            dist.destroy_process_group()
+
+    if not args.full:  # the headline figure alone; everything below is a run of its own
+        return finish()
 
     # ---- serial kernel pass (untimed): the same calls, each synchronous, one after the other
     # from one thread, so no two kernels share the GPU and each HIP-event span is the kernel's
@@ -848,10 +974,6 @@ def main():
                                "+ accumulate + report checksums), leader prep shares precomputed"}
         hagg2.close()
 
-    reports = args.steps * B * world
-    value = reports / elapsed
-    ms_per_step = elapsed / args.steps * 1e3
-
     # ---- roofline of the dominant kernel (HIP events on the engine's stream) -------------------
     perms = perms_per_report(args.config, s)
     dom = max(kt.items(), key=lambda kv: kv[1][0])
@@ -1034,29 +1156,7 @@ def main():
                     "sample": f"{nh} helper input shares x {reps}",
                     "note": "CPU stage in front of the GPU path (north star); not in `value`"}
 
-    out = {
-        "metric": (METRIC if args.config == "sumvec" and not turbo else
-                   f"reports/sec prepared+aggregated, {label}" + (", XofTurboShake128" if turbo
-                                                                  else "")),
-        "value": round(value, 2),
-        "unit": "reports/s",
-        "n_gpus": world,
-        "steps": args.steps,
-        "warmup": args.warmup,
-        "ms_per_step": round(ms_per_step, 3),
-        "higher_is_better": True,
-        "scaling": "weak",
-        "vs_baseline": None,
-        "dtype": "u128 (Field128 mod p)" if s.field_size == 16 else "u64 (Field64 mod p)",
-        "data": f"synthetic: {B} distinct reports/GPU (SURVEY §8(d) recipe; shares made by the GPU "
-                f"client shard), resident in HBM",
-        "config": {"workload": label, "xof": "XofTurboShake128" if turbo else "XofShake128",
-                   "engine_options": dict(engine_opts),
-                   "schedule": f"overlap {args.overlap}" + (", async calls" if async_calls else ""),
-                   "reports_per_gpu_per_step": B, "job_workers_per_gpu": W,
-                   "parallelism": f"report-sharded x{world}, {W} job stream(s)/GPU, "
-                                  + ("RCCL all-gather merge" if args.merge == "rccl" else
-                                     "gloo rehearsal (ranks share GPUs, host merge)")},
+    out.update({
         "roofline": roof,
         "cpu_baseline": cpu,
         "hpke_open": hpke_rep,
@@ -1071,26 +1171,14 @@ def main():
                          "ms_per_step": round(serial_el / args.prof_steps * 1e3, 3),
                          "kernel_ms_per_step": round(sum(v[0] for v in kt.values()) / kt_steps, 3)}
                         if serial_el else None),
-        # HIP-event spans in the timed (possibly co-running) schedule: a span includes time spent
-        # queued behind or sharing the CUs with the other context's kernels
-        "kernels_timed_span_ms_per_step": {k: round(v[0] / args.steps, 3)
-                                           for k, v in kt_timed.items()},
         "parity": parity,
-        "gen_seconds": round(gen_s, 1),
-        # the engine build that ran: SHA-256 of its sources + flags (janus_amd/_lib.py)
-        "build_hash": L.prio3gpu_build_hash().decode(),
-    }
+    })
     if cpu:
         out["speedup_vs_cpu"] = round(value / cpu["value"], 1)
         fair = cpu.get("cpus_per_gpu_on_host_8gpu") or 0
         if fair > cpu["cores"]:  # the same speedup against a linearly scaled fair CPU share
             out["speedup_vs_cpu_at_host_share"] = round(value / (cpu["value"] * fair / cpu["cores"]), 1)
-    if rank == 0:
-        print(json.dumps(out), flush=True)
-    if comm is not None:
-        comm.close()
-    if dist is not None:
-        dist.destroy_process_group()
+    finish()
 
 
 if __name__ == "__main__":

@@ -37,6 +37,33 @@ def test_flp_op_model_matches_survey_appendix_b():
     assert bench.flp_mults_per_report(mk(8, 1, 5, 4), 0) == 14
 
 
+def test_dump_rows_fixed_sample():
+    """--dump-outputs keeps every row of a small batch, else the same sorted sample on every call
+    (first and last row included), cut so that float32 copies of the rows fill at most half of the
+    dump budget."""
+    import bench
+    assert np.array_equal(bench.dump_rows(8, 100), np.arange(8))
+    a, b = bench.dump_rows(393216, 2912), bench.dump_rows(393216, 2912)
+    assert np.array_equal(a, b) and len(a) == bench.DUMP_ROWS == len(set(a.tolist()))
+    assert a[0] == 0 and a[-1] == 393215 and (np.diff(a) > 0).all()
+    wide = bench.dump_rows(1 << 20, 1 << 20)  # 1 MiB rows: the budget, not DUMP_ROWS, cuts
+    assert 2 <= len(wide) and len(wide) * 4 * (1 << 20) <= bench.DUMP_BUDGET // 2
+
+
+def test_dump_outputs_writes_float_arrays(tmp_path):
+    import bench
+    import torch
+    t = torch.arange(12, dtype=torch.uint8).reshape(4, 3)
+    bench.dump_outputs(str(tmp_path / "d"), 0, 1, {"prep": t, "absent": None},
+                       {"counts": np.array([4.0, 4.0])})
+    assert sorted(p.name for p in (tmp_path / "d").iterdir()) == ["counts.npy", "prep.npy",
+                                                                   "sample_rows.npy"]
+    got = np.load(tmp_path / "d" / "prep.npy")
+    assert got.dtype == np.float32 and np.array_equal(got, t.numpy())
+    bench.dump_outputs(str(tmp_path / "d"), 1, 2, {"prep": t}, {})
+    assert (tmp_path / "d" / "prep.rank1.npy").exists()
+
+
 def test_flp_weights_bytes_model():
     """k_flp_weights' algorithmic bytes per report (bench.py roofline.hbm_weights): SumVec(8,1000)
     reads 255 gadget coefficients + t, r and writes a 274-entry weight row, 12 block-start prefix

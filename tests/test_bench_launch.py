@@ -39,8 +39,9 @@ def test_self_launch_runs_n_ranks(tmp_path):
     """launch_ranks starts torch.distributed.run with WORLD_SIZE = N in every child: a stand-in
     script (the launcher argv with the bench swapped for a probe) reports what each rank saw."""
     probe = tmp_path / "probe.py"
-    probe.write_text("import os\nprint('rank', os.environ['RANK'], 'of', os.environ['WORLD_SIZE'],"
-                     " flush=True)\n")
+    # one write per rank: the ranks share a pipe, and print() writes its arguments piecewise
+    probe.write_text("import os\nos.write(1, ('rank %s of %s\\n' % (os.environ['RANK'], "
+                     "os.environ['WORLD_SIZE'])).encode())\n")
     code = ("import sys; sys.path.insert(0, %r); import bench; real = bench.launcher_argv; "
             "bench.launcher_argv = lambda n, a, p: real(n, a, p)[:-1 - len(a)] + [%r]; "
             "sys.exit(bench.launch_ranks(2, []))" % (ROOT, str(probe)))

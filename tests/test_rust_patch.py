@@ -239,7 +239,6 @@ def test_mod_rs_status_mapping_covers_prepare_error():
     assert "_ => PrepareError::VdafPrepError" in body
 
 
-@needs_ref
 def test_leader_feed_reads_reports_undecoded(tmp_path):
     """The leader's engine batch is fed the stored encodings: a
     `get_client_report_raw` datastore read (the columns of aggregator_core/src/datastore.rs:

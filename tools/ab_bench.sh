@@ -6,7 +6,7 @@
 #   bash tools/ab_bench.sh "ov0|base|-|--overlap 0" "ov2cap|base|PRIO3GPU_JR_LDS=65536|--overlap 2"
 # Output: gpurun_out/ab_LABEL.log, one summary line per run on stdout.
 O=gpurun_out; mkdir -p $O
-COMMON="--steps 6 --warmup 2 --cpu-baseline 0 --hpke 0 --helper-only 0"
+COMMON="--full --steps 6 --warmup 2 --cpu-baseline 0 --hpke 0 --helper-only 0"
 for spec in "$@"; do
   IFS='|' read -r label libn envs args <<< "$spec"
   vars=()

@@ -7,7 +7,7 @@ tail -1 $O/pytest_gpu.log
 timeout -k 10 300 python -u -c "import __graft_entry__ as g; g.smoke()" > $O/smoke.log 2>&1 || { tail -20 $O/smoke.log; exit 1; }
 tail -1 $O/smoke.log
 for c in sumvec sum histogram count; do
-  timeout -k 10 400 python -u bench.py --config $c > $O/bench_$c.log 2>&1 || { tail -20 $O/bench_$c.log; exit 1; }
+  timeout -k 10 400 python -u bench.py --full --config $c > $O/bench_$c.log 2>&1 || { tail -20 $O/bench_$c.log; exit 1; }
   python3 -c "
 import json
 for l in open('$O/bench_$c.log'):

@@ -8,7 +8,7 @@ R=$(cd "$(dirname "$0")/.." && pwd)
 O=$R/gpurun_out/pmc_$TAG
 mkdir -p "$O"
 if [ $# -gt 0 ] && [[ "$1" == *.py ]]; then SCRIPT=$R/$1; shift; ARGS="$*"
-else SCRIPT=$R/bench.py; ARGS="--steps 1 --warmup 0 --cpu-baseline 0 --hpke 0 --helper-only 0 $*"; fi
+else SCRIPT=$R/bench.py; ARGS="--full --steps 1 --warmup 0 --cpu-baseline 0 --hpke 0 --helper-only 0 $*"; fi
 cd /tmp && export TMPDIR=/tmp
 timeout -s KILL 600 rocprofv3 --pmc $CTRS --output-format csv -d "$O/raw" -o run -- python3 "$SCRIPT" $ARGS > "$O/run.log" 2>&1
 rc=$?

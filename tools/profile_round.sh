@@ -9,8 +9,8 @@ R=$(cd "$(dirname "$0")/.." && pwd)
 O=$R/gpurun_out/prof_${TAG}_$CFG
 mkdir -p "$O" "$R/profiles"
 cd /tmp && export TMPDIR=/tmp
-ARGS="--steps 3 --warmup 1 --cpu-baseline 0 --hpke 0 --helper-only 0 --config $CFG"
-ONE="--steps 1 --warmup 0 --cpu-baseline 0 --hpke 0 --helper-only 0 --config $CFG"
+ARGS="--full --steps 3 --warmup 1 --cpu-baseline 0 --hpke 0 --helper-only 0 --config $CFG"
+ONE="--full --steps 1 --warmup 0 --cpu-baseline 0 --hpke 0 --helper-only 0 --config $CFG"
 # the trace pass runs every kernel alone (--overlap 0: one context, one stream), so its durations
 # are the kernels' own, like the PMC passes (which serialise dispatches) and bench.py's serial pass
 timeout -k 10 500 rocprofv3 --kernel-trace --stats --output-format csv -d "$O/trace" -o run -- python3 "$R/bench.py" $ARGS --overlap 0 > "$O/trace.log" 2>&1

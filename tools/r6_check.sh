@@ -12,7 +12,7 @@ tail -1 $O/smoke.log
 for c in ${3:-sumvec}; do
   for lib in prod $2; do
     if [ $lib = prod ]; then E=""; else E="PRIO3GPU_LIB=janus_amd/lib/libprio3gpu_$lib.so"; fi
-    env $E timeout -k 10 400 python -u bench.py --config $c > $O/bench_${c}_$lib.log 2>&1 || { tail -20 $O/bench_${c}_$lib.log; exit 1; }
+    env $E timeout -k 10 400 python -u bench.py --full --config $c > $O/bench_${c}_$lib.log 2>&1 || { tail -20 $O/bench_${c}_$lib.log; exit 1; }
     python3 -c "
 import json
 for l in open('$O/bench_${c}_$lib.log'):
