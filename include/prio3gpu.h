@@ -184,7 +184,10 @@ void* prio3gpu_ctx_stream(prio3gpu_ctx* ctx);
  * hold is PRIO3GPU_E_CAPACITY (the message gives the bytes needed and free) with nothing
  * allocated, and calls on a created state do not allocate (except the FixedPoint helper's exact
  * path after a non-canonical squeezed element in snapshot mode, which allocates the full rows and
- * also reports a failure as PRIO3GPU_E_CAPACITY). */
+ * also reports a failure as PRIO3GPU_E_CAPACITY).  The GPU HPKE open (prio3gpu_hpke_open_batch,
+ * prio3gpu_hpke_open_report_shares_gpu) takes no state: its scratch belongs to the CONTEXT and
+ * grows on demand to the largest batch the context has opened (PRIO3GPU_E_CAPACITY if the device
+ * cannot hold it), so the first call at a new size does allocate. */
 int prio3gpu_state_create(prio3gpu_ctx* ctx, int agg_id, size_t capacity, prio3gpu_state** out);
 int prio3gpu_state_destroy(prio3gpu_state* st);
 /* Row pitch of the input shares this state's prepare_init / prepare_init_xof / helper_init calls
@@ -505,6 +508,40 @@ int prio3gpu_hpke_open_report_shares(const uint8_t* task_id, const prio3gpu_hpke
                                      const prio3gpu_prepare_init_view* views, size_t n,
                                      uint8_t* plaintexts, uint64_t* offsets, uint8_t* status,
                                      int threads);
+
+/* ---- HPKE open on the GPU (janus_amd/csrc/hpke_gpu.h) ------------------------------------------
+ * n opens under ONE keypair, one GPU lane per report, for the suite Janus generates by default:
+ * DHKEM(X25519, HKDF-SHA256) / HKDF-SHA256 / AES-128-GCM (0x0020 / 1 / 1); any other suite is
+ * PRIO3GPU_E_UNSUPPORTED with nothing launched (use the host functions above).  sk, pk and info
+ * are host memory; every other pointer may be host or device (detected).  Report i has
+ * enc = encs[32 i .. 32 i + 32), aad = aads[aad_offsets[i] .. aad_offsets[i+1]), ciphertext ||
+ * tag = cts[ct_offsets[i] .. ct_offsets[i+1]) and its plaintext goes to pts[pt_offsets[i] ..
+ * pt_offsets[i+1]) (room for the ciphertext length - 16; a longer slot is zero-filled).
+ * status in/out: non-zero on entry = skipped (the slot is zeroed); a failed open -- bad tag,
+ * ciphertext shorter than the tag, an all-zero DH value, offsets that do not fit -- sets 4
+ * (HpkeDecryptError) and writes zeros, never unauthenticated plaintext.  The private key reaches
+ * the GPU only as a kernel argument; the device buffer that held the per-report DH values is
+ * zeroed before the call returns.  Scratch belongs to the context (see prio3gpu_state_create). */
+int prio3gpu_hpke_open_batch(prio3gpu_ctx* ctx, uint16_t kem_id, uint16_t kdf_id, uint16_t aead_id,
+                             const uint8_t* sk, size_t sk_len, const uint8_t* pk, size_t pk_len,
+                             const uint8_t* info, size_t info_len, size_t n, const uint8_t* encs,
+                             const uint8_t* aads, const uint64_t* aad_offsets, const uint8_t* cts,
+                             const uint64_t* ct_offsets, uint8_t* pts, const uint64_t* pt_offsets,
+                             uint8_t* status);
+/* prio3gpu_hpke_open_report_shares with the GPU opening every report whose first-choice key (task
+ * key by config id, else global key) is of the suite above, one batch per key: same arguments,
+ * offsets, statuses and key-selection order.  Reports whose first choice is another suite (P-256,
+ * SHA-384/512, AES-256, ChaCha20), and the global-key second trial after a failed task-key open,
+ * run on the host path on `threads` threads.  The plaintext slot of a report that ends with a
+ * non-zero status is unspecified in both functions.  All pointers are host memory. */
+int prio3gpu_hpke_open_report_shares_gpu(prio3gpu_ctx* ctx, const uint8_t* task_id,
+                                         const prio3gpu_hpke_keypair* task_keys, size_t n_task_keys,
+                                         const prio3gpu_hpke_keypair* global_keys,
+                                         size_t n_global_keys, uint8_t sender_role,
+                                         uint8_t recipient_role, const uint8_t* msg,
+                                         const prio3gpu_prepare_init_view* views, size_t n,
+                                         uint8_t* plaintexts, uint64_t* offsets, uint8_t* status,
+                                         int threads);
 
 /* Last error message for this thread (static storage). */
 const char* prio3gpu_last_error(void);

@@ -40,6 +40,12 @@ int prio3gpu_memcpy(prio3gpu_ctx* ctx, void* dst, const void* src, size_t bytes)
  * without IFMA. */
 int prio3gpu_test_hpke_set_ifma(int on);
 
+/* TEST ONLY.  The GPU open's X25519 ladder alone (k_x25519, one lane per point): out[i] =
+ * X25519(sk, points[i]) for n 32-byte points under one 32-byte private key (clamped inside), the
+ * GPU counterpart of prio3gpu_x25519_batch.  points / out may be host or device memory. */
+int prio3gpu_test_x25519_gpu(prio3gpu_ctx* ctx, const uint8_t* sk, const uint8_t* points, size_t n,
+                             uint8_t* out);
+
 #ifdef __cplusplus
 }
 #endif

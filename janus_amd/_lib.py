@@ -181,6 +181,14 @@ def _declare(lib):
         "prio3gpu_hpke_open_report_shares": (c.c_int, [u8p, P, c.c_size_t, P, c.c_size_t,
                                                        c.c_uint8, c.c_uint8, u8p, P, c.c_size_t,
                                                        u8p, P, u8p, c.c_int]),
+        # HPKE open on the GPU (hpke_gpu.h)
+        "prio3gpu_hpke_open_batch": (c.c_int, [P, c.c_uint16, c.c_uint16, c.c_uint16, u8p,
+                                               c.c_size_t, u8p, c.c_size_t, u8p, c.c_size_t,
+                                               c.c_size_t, u8p, u8p, P, u8p, P, u8p, P, u8p]),
+        "prio3gpu_hpke_open_report_shares_gpu": (c.c_int, [P, u8p, P, c.c_size_t, P, c.c_size_t,
+                                                           c.c_uint8, c.c_uint8, u8p, P,
+                                                           c.c_size_t, u8p, P, u8p, c.c_int]),
+        "prio3gpu_test_x25519_gpu": (c.c_int, [P, u8p, u8p, c.c_size_t, u8p]),
     }
     for name, (res, args) in sigs.items():
         f = getattr(lib, name)
@@ -212,11 +220,12 @@ EXPORTED = [
     "prio3gpu_encode_agg_init_req", "prio3gpu_decode_agg_job_resp", "prio3gpu_gather_helper_resps",
     "prio3gpu_hpke_open", "prio3gpu_hpke_seal", "prio3gpu_hpke_public_key",
     "prio3gpu_hpke_open_report_shares", "prio3gpu_x25519_batch",
+    "prio3gpu_hpke_open_batch", "prio3gpu_hpke_open_report_shares_gpu",
 ]
 # The test / benchmark hooks of include/prio3gpu_test.h (same library, not part of the product ABI).
 TEST_EXPORTED = [
     "prio3gpu_test_squeeze", "prio3gpu_test_flp_query", "prio3gpu_dev_alloc", "prio3gpu_dev_free",
-    "prio3gpu_memcpy", "prio3gpu_test_hpke_set_ifma",
+    "prio3gpu_memcpy", "prio3gpu_test_hpke_set_ifma", "prio3gpu_test_x25519_gpu",
 ]
 
 

@@ -11,6 +11,7 @@
 #include <string>
 #include <initializer_list>
 #include <mutex>
+#include <thread>
 #include <vector>
 
 #include "../../include/prio3gpu.h"
@@ -21,6 +22,7 @@
 #include "wires_mfma.h"
 #include "fpvec_mfma.h"
 #include "fpvec_pair.h"
+#include "hpke_gpu.h"
 
 using namespace p3g;
 
@@ -164,7 +166,7 @@ enum KernelId {
   KID_PNEXT, KID_ACC_PART, KID_ACC_SPEC, KID_ACC_MERGE, KID_OUT, KID_MERGE, KID_SHARD_SEEDS,
   KID_SHARD_MEAS, KID_SHARD_JR, KID_PROVE, KID_SHARD_PROOF, KID_REPORT_META, KID_REPORT_META_FOLD,
   KID_SHARD_NORM, KID_JR_RING, KID_FLP_QUERY_LANE, KID_FLP_WIRES_COLS, KID_FLP_WIRES_MFMA,
-  KID_FPV_REGEN, KID_COUNT
+  KID_FPV_REGEN, KID_X25519, KID_HPKE_OPEN, KID_COUNT
 };
 const char* const kKernelNames[KID_COUNT] = {
     "k_query_rand", "k_expand", "k_helper_xof", "k_jr", "k_flp_weights", "k_flp_wires",
@@ -172,7 +174,7 @@ const char* const kKernelNames[KID_COUNT] = {
     "k_prepare_next", "k_accum_partial", "k_accum_spec", "k_accum_merge", "k_out_shares", "k_merge",
     "k_shard_seeds", "k_shard_meas", "k_shard_jr", "k_flp_prove", "k_shard_proof", "k_report_meta",
     "k_report_meta_fold", "k_shard_norm", "k_jr_ring", "k_flp_query_lane", "k_flp_wires_cols",
-    "k_flp_wires_mfma", "k_fpv_regen"};
+    "k_flp_wires_mfma", "k_fpv_regen", "k_x25519", "k_hpke_open"};
 
 // Per-kernel HIP-event timing on the context's stream (opt-in; used by bench.py).
 struct Prof {
@@ -212,6 +214,9 @@ struct prio3gpu_ctx {
   // generic staging (inputs given as host pointers) and scratch
   DevBuf io[6];
   DevBuf perm, chunks, partials, pcounts, spec_idx;
+  // prio3gpu_hpke_open_batch: staging of host inputs / outputs (enc, aad, aad offsets, ct, ct
+  // offsets, pt, pt offsets, status) and the ladder's DH values; grown on demand
+  DevBuf hpke[9];
   std::vector<uint32_t> h_perm, h_chunk_begin, h_chunk_slot;
   // Engine options (prio3gpu_ctx_set_option; include/prio3gpu.h lists them).  The defaults are the
   // measured-fastest paths; every alternative is parity-tested against the oracle.
@@ -2601,6 +2606,325 @@ int prio3gpu_test_flp_query(prio3gpu_ctx* c, size_t n, const uint8_t* leader_inp
   rc = run();
   prio3gpu_state_destroy(st);
   return rc;
+}
+
+}  // extern "C"
+
+// ---- batched HPKE open on the GPU (hpke_gpu.h) --------------------------------------------------
+namespace {
+
+// A host buffer is copied into the context's scratch (grown on demand); a device buffer is used
+// where it is.
+int hpke_stage_in(prio3gpu_ctx* c, DevBuf& buf, const void* src, size_t bytes, const void** d) {
+  if (src && is_device_ptr(src)) {
+    *d = src;
+    return 0;
+  }
+  CHK(buf.ensure(std::max<size_t>(bytes, 16)));
+  if (bytes) HIPCHK(hipMemcpyAsync(buf.p, src, bytes, hipMemcpyHostToDevice, c->stream));
+  *d = buf.p;
+  return 0;
+}
+
+int hpke_fetch_u64(prio3gpu_ctx* c, const uint64_t* p, uint64_t* out) {
+  if (is_device_ptr(p)) {
+    HIPCHK(hipMemcpyAsync(out, p, 8, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
+  } else {
+    *out = *p;
+  }
+  return 0;
+}
+
+void wipe(void* p, size_t n) {  // a memset the compiler may not drop
+  memset(p, 0, n);
+  __asm__ __volatile__("" : : "r"(p) : "memory");
+}
+
+// f(i) for i in [0, n) on up to `threads` host threads (<= 0: all cores), contiguous ranges.
+template <class F>
+void host_parallel(size_t n, int threads, F&& f) {
+  size_t t = threads > 0 ? size_t(threads) : std::max(1u, std::thread::hardware_concurrency());
+  t = std::min(t, (n + 1023) / 1024);
+  if (t <= 1) {
+    for (size_t i = 0; i < n; ++i) f(i);
+    return;
+  }
+  const size_t per = (n + t - 1) / t;
+  std::vector<std::thread> pool;
+  for (size_t k = 1; k < t; ++k)
+    pool.emplace_back([&f, k, per, n] {
+      for (size_t i = k * per; i < std::min(n, (k + 1) * per); ++i) f(i);
+    });
+  for (size_t i = 0; i < std::min(n, per); ++i) f(i);
+  for (auto& th : pool) th.join();
+}
+
+// d_out[r] = X25519(sk, d_points[r]); the clamped scalar travels as a kernel argument, so no
+// device buffer ever holds the private key.
+int launch_x25519(prio3gpu_ctx* c, const uint8_t* sk, size_t n, const uint8_t* d_points,
+                  uint32_t* d_out) {
+  uint8_t k[32];
+  memcpy(k, sk, 32);
+  k[0] &= 248;  // decodeScalar25519
+  k[31] &= 127;
+  k[31] |= 64;
+  X25519Scalar ks;
+  memcpy(ks.w, k, 32);  // little-endian host
+  {
+    PROF(KID_X25519);
+    hipLaunchKernelGGL(k_x25519, dim3((unsigned)((n + 63) / 64)), dim3(64), 0, c->stream,
+                       (uint32_t)n, ks, d_points, d_out);
+  }
+  wipe(k, sizeof k);
+  wipe(&ks, sizeof ks);
+  HIPCHK(hipGetLastError());
+  return 0;
+}
+
+int hpke_open_batch_impl(prio3gpu_ctx* c, const uint8_t* sk, const uint8_t* pk, const uint8_t* info,
+                         size_t info_len, size_t n, const uint8_t* encs, const uint8_t* aads,
+                         const uint64_t* aad_offsets, const uint8_t* cts,
+                         const uint64_t* ct_offsets, uint8_t* pts, const uint64_t* pt_offsets,
+                         uint8_t* status) {
+  HpkeBatchConsts bc;
+  if (!hpke_batch_consts(pk, info, info_len, &bc)) {
+    set_err("HPKE primitives unavailable");
+    return PRIO3GPU_E_UNSUPPORTED;
+  }
+  HIPCHK(hipSetDevice(c->device));
+  uint64_t aad_total = 0, ct_total = 0, pt_total = 0, pt_first = 0;
+  CHK(hpke_fetch_u64(c, aad_offsets + n, &aad_total));
+  CHK(hpke_fetch_u64(c, ct_offsets + n, &ct_total));
+  CHK(hpke_fetch_u64(c, pt_offsets + n, &pt_total));
+  CHK(hpke_fetch_u64(c, pt_offsets, &pt_first));
+  if ((aad_total && !aads) || (ct_total && !cts) || (pt_total && !pts) || pt_first > pt_total) {
+    set_err("HPKE open: null data buffer or offsets out of order");
+    return PRIO3GPU_E_ARG;
+  }
+  const void *d_enc, *d_aad, *d_aoff, *d_ct, *d_coff, *d_poff, *d_st_in;
+  CHK(hpke_stage_in(c, c->hpke[0], encs, n * 32, &d_enc));
+  CHK(hpke_stage_in(c, c->hpke[1], aads, aad_total, &d_aad));
+  CHK(hpke_stage_in(c, c->hpke[2], aad_offsets, (n + 1) * 8, &d_aoff));
+  CHK(hpke_stage_in(c, c->hpke[3], cts, ct_total, &d_ct));
+  CHK(hpke_stage_in(c, c->hpke[4], ct_offsets, (n + 1) * 8, &d_coff));
+  CHK(hpke_stage_in(c, c->hpke[6], pt_offsets, (n + 1) * 8, &d_poff));
+  CHK(hpke_stage_in(c, c->hpke[7], status, n, &d_st_in));
+  uint8_t* d_st = static_cast<uint8_t*>(const_cast<void*>(d_st_in));
+  uint8_t* d_pt = pts;
+  const bool pt_host = !(pts && is_device_ptr(pts));
+  if (pt_host) {
+    CHK(c->hpke[5].ensure(std::max<uint64_t>(pt_total, 16)));
+    d_pt = c->hpke[5].u8();
+    if (pt_total) HIPCHK(hipMemsetAsync(d_pt, 0, pt_total, c->stream));
+  }
+  CHK(c->hpke[8].ensure(n * 32));
+  uint32_t* d_dh = static_cast<uint32_t*>(c->hpke[8].p);
+  auto run = [&]() -> int {
+    CHK(launch_x25519(c, sk, n, static_cast<const uint8_t*>(d_enc), d_dh));
+    {
+      PROF(KID_HPKE_OPEN);
+      hipLaunchKernelGGL(k_hpke_open, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, c->stream,
+                         (uint32_t)n, bc, d_dh, static_cast<const uint8_t*>(d_enc),
+                         static_cast<const uint8_t*>(d_aad), static_cast<const uint64_t*>(d_aoff),
+                         aad_total, static_cast<const uint8_t*>(d_ct),
+                         static_cast<const uint64_t*>(d_coff), ct_total, d_pt,
+                         static_cast<const uint64_t*>(d_poff), pt_total, d_st);
+    }
+    HIPCHK(hipGetLastError());
+    return 0;
+  };
+  int rc = run();
+  // the per-report secrets: the DH values (keys and nonces never leave registers)
+  if (hipMemsetAsync(d_dh, 0, n * 32, c->stream) != hipSuccess && !rc) {
+    set_err("clearing the DH values failed");
+    rc = PRIO3GPU_E_HIP;
+  }
+  if (rc) {
+    (void)hipStreamSynchronize(c->stream);
+    return rc;
+  }
+  if (pt_host && pt_total > pt_first)
+    HIPCHK(hipMemcpyAsync(pts + pt_first, d_pt + pt_first, pt_total - pt_first,
+                          hipMemcpyDeviceToHost, c->stream));
+  if (d_st != status) HIPCHK(hipMemcpyAsync(status, d_st, n, hipMemcpyDeviceToHost, c->stream));
+  return finish_call(c, {encs, aads, aad_offsets, cts, ct_offsets, pts, pt_offsets, status});
+}
+
+bool hpke_gpu_suite(uint16_t kem, uint16_t kdf, uint16_t aead) {
+  return kem == 0x0020 && kdf == 1 && aead == 1;
+}
+
+}  // namespace
+
+extern "C" {
+
+int prio3gpu_hpke_open_batch(prio3gpu_ctx* c, uint16_t kem_id, uint16_t kdf_id, uint16_t aead_id,
+                             const uint8_t* sk, size_t sk_len, const uint8_t* pk, size_t pk_len,
+                             const uint8_t* info, size_t info_len, size_t n, const uint8_t* encs,
+                             const uint8_t* aads, const uint64_t* aad_offsets, const uint8_t* cts,
+                             const uint64_t* ct_offsets, uint8_t* pts, const uint64_t* pt_offsets,
+                             uint8_t* status) {
+  if (!c) {
+    set_err("null context");
+    return PRIO3GPU_E_ARG;
+  }
+  if (!hpke_gpu_suite(kem_id, kdf_id, aead_id)) {
+    set_err("HPKE suite 0x%04x/%u/%u is not opened on the GPU", kem_id, kdf_id, aead_id);
+    return PRIO3GPU_E_UNSUPPORTED;
+  }
+  if (!sk || sk_len != 32 || !pk || pk_len != 32 || (info_len && !info)) {
+    set_err("HPKE open: X25519 keys are 32 bytes");
+    return PRIO3GPU_E_ARG;
+  }
+  if (n == 0) return 0;
+  if (!encs || !aad_offsets || !ct_offsets || !pt_offsets || !status || n > 0x7FFFFFFFu) {
+    set_err("HPKE open: null argument");
+    return PRIO3GPU_E_ARG;
+  }
+  return hpke_open_batch_impl(c, sk, pk, info, info_len, n, encs, aads, aad_offsets, cts,
+                              ct_offsets, pts, pt_offsets, status);
+}
+
+int prio3gpu_hpke_open_report_shares_gpu(
+    prio3gpu_ctx* c, const uint8_t* task_id, const prio3gpu_hpke_keypair* task_keys,
+    size_t n_task_keys, const prio3gpu_hpke_keypair* global_keys, size_t n_global_keys,
+    uint8_t sender_role, uint8_t recipient_role, const uint8_t* msg,
+    const prio3gpu_prepare_init_view* views, size_t n, uint8_t* plaintexts, uint64_t* offsets,
+    uint8_t* status, int threads) {
+  if (!c) {
+    set_err("null context");
+    return PRIO3GPU_E_ARG;
+  }
+  if (n == 0 || !plaintexts)  // n = 0 and the sizing call: offsets only
+    return prio3gpu_hpke_open_report_shares(task_id, task_keys, n_task_keys, global_keys,
+                                            n_global_keys, sender_role, recipient_role, msg, views,
+                                            n, plaintexts, offsets, status, threads);
+  if (!msg || !views || !offsets || !task_id || !status) return PRIO3GPU_E_ARG;
+  offsets[0] = 0;
+  for (size_t i = 0; i < n; ++i)
+    offsets[i + 1] = offsets[i] + (views[i].payload_len >= 16 ? views[i].payload_len - 16 : 0);
+  auto find = [](const prio3gpu_hpke_keypair* ks, size_t nk, uint8_t id) {
+    for (size_t k = 0; k < nk; ++k)
+      if (ks[k].config_id == id) return &ks[k];
+    return static_cast<const prio3gpu_hpke_keypair*>(nullptr);
+  };
+  // The first-choice key of every report (task key, else global key, by config id).  Reports
+  // whose first choice is an X25519 / HKDF-SHA256 / AES-128-GCM key go to the GPU, one batch per
+  // key; everything else (other suites, malformed keys or encapsulated keys, unknown ids) is the
+  // host path's, untouched.
+  std::vector<const prio3gpu_hpke_keypair*> first(n, nullptr), groups;
+  std::vector<uint8_t> st_host(status, status + n), st_retry(n, 1);
+  for (size_t i = 0; i < n; ++i) {
+    if (status[i]) continue;
+    const prio3gpu_hpke_keypair* tk = find(task_keys, n_task_keys, views[i].hpke_config_id);
+    const prio3gpu_hpke_keypair* kp =
+        tk ? tk : find(global_keys, n_global_keys, views[i].hpke_config_id);
+    if (!kp || !hpke_gpu_suite(kp->kem_id, kp->kdf_id, kp->aead_id) || !kp->private_key ||
+        kp->private_key_len != 32 || !kp->public_key || kp->public_key_len != 32 ||
+        views[i].enc_len != 32 || views[i].payload_len < 16)
+      continue;
+    first[i] = kp;
+    st_host[i] = 1;  // not the host pass's
+    if (std::find(groups.begin(), groups.end(), kp) == groups.end()) groups.push_back(kp);
+  }
+  const uint8_t info[20] = {'d', 'a', 'p', '-', '0', '7', ' ', 'i', 'n', 'p', 'u', 't', ' ', 's',
+                            'h', 'a', 'r', 'e', sender_role, recipient_role};  // hpke.rs:52-77
+  bool any_retry = false;
+  std::vector<uint8_t> encs, aads, cts, pts, st;
+  std::vector<uint64_t> aoff, coff, poff;
+  std::vector<size_t> idx;
+  for (const prio3gpu_hpke_keypair* kp : groups) {
+    idx.clear();
+    for (size_t i = 0; i < n; ++i)
+      if (first[i] == kp) idx.push_back(i);
+    const size_t m = idx.size();
+    aoff.assign(m + 1, 0), coff.assign(m + 1, 0), poff.assign(m + 1, 0);
+    for (size_t j = 0; j < m; ++j) {
+      const prio3gpu_prepare_init_view& v = views[idx[j]];
+      aoff[j + 1] = aoff[j] + 60 + v.public_share_len;  // InputShareAad
+      coff[j + 1] = coff[j] + v.payload_len;
+      poff[j + 1] = poff[j] + (v.payload_len - 16);
+    }
+    encs.resize(m * 32), aads.resize(aoff[m]), cts.resize(coff[m]);
+    // the fields of one report lie kilobytes apart in the request (its prep share is between
+    // them): the gather is DRAM-latency-bound on one thread, so it runs on the host threads
+    host_parallel(m, threads, [&](size_t j) {
+      const prio3gpu_prepare_init_view& v = views[idx[j]];
+      memcpy(&encs[j * 32], msg + v.enc_off, 32);
+      uint8_t* a = &aads[aoff[j]];  // task id, report id, time, u32-prefixed public share
+      memcpy(a, task_id, 32);
+      memcpy(a + 32, msg + v.report_id_off, 16);
+      for (int b = 0; b < 8; ++b) a[48 + b] = uint8_t(v.time >> (56 - 8 * b));
+      for (int b = 0; b < 4; ++b) a[56 + b] = uint8_t(v.public_share_len >> (24 - 8 * b));
+      memcpy(a + 60, msg + v.public_share_off, v.public_share_len);
+      memcpy(&cts[coff[j]], msg + v.payload_off, v.payload_len);
+    });
+    pts.assign(std::max<size_t>(poff.back(), 1), 0);
+    st.assign(m, 0);
+    CHK(hpke_open_batch_impl(c, kp->private_key, kp->public_key, info, sizeof info, m, encs.data(),
+                             aads.data(), aoff.data(), cts.data(), coff.data(), pts.data(),
+                             poff.data(), st.data()));
+    for (size_t j = 0; j < m; ++j) {
+      const size_t i = idx[j];
+      if (st[j] == 0) {
+        memcpy(plaintexts + offsets[i], pts.data() + poff[j], poff[j + 1] - poff[j]);
+        continue;
+      }
+      // a failed open: the global key of the same id gets the second trial, on the host
+      const bool is_task_key = kp >= task_keys && kp < task_keys + n_task_keys;
+      if (is_task_key && find(global_keys, n_global_keys, views[i].hpke_config_id)) {
+        st_retry[i] = 0;
+        any_retry = true;
+      } else {
+        status[i] = PRIO3GPU_HPKE_DECRYPT_ERROR;
+      }
+    }
+  }
+  wipe(pts.data(), pts.size());
+  bool any_host = false;
+  for (size_t i = 0; i < n; ++i) any_host |= !first[i] && !status[i];
+  if (any_host) {
+    CHK(prio3gpu_hpke_open_report_shares(task_id, task_keys, n_task_keys, global_keys,
+                                         n_global_keys, sender_role, recipient_role, msg, views, n,
+                                         plaintexts, offsets, st_host.data(), threads));
+    for (size_t i = 0; i < n; ++i)
+      if (!first[i]) status[i] = st_host[i];
+  }
+  if (any_retry) {
+    std::vector<uint8_t> was_retry(st_retry);
+    CHK(prio3gpu_hpke_open_report_shares(task_id, nullptr, 0, global_keys, n_global_keys,
+                                         sender_role, recipient_role, msg, views, n, plaintexts,
+                                         offsets, st_retry.data(), threads));
+    for (size_t i = 0; i < n; ++i)
+      if (!was_retry[i]) status[i] = st_retry[i];
+  }
+  return 0;
+}
+
+int prio3gpu_test_x25519_gpu(prio3gpu_ctx* c, const uint8_t* sk, const uint8_t* points, size_t n,
+                             uint8_t* out) {
+  if (!c || (n && (!sk || !points || !out)) || n > 0x7FFFFFFFu) {
+    set_err("null argument");
+    return PRIO3GPU_E_ARG;
+  }
+  if (n == 0) return 0;
+  HIPCHK(hipSetDevice(c->device));
+  const void* d_pts;
+  CHK(hpke_stage_in(c, c->hpke[0], points, n * 32, &d_pts));
+  uint8_t* d_out = out;
+  if (!is_device_ptr(out)) {
+    CHK(c->hpke[8].ensure(n * 32));
+    d_out = c->hpke[8].u8();
+  }
+  CHK(launch_x25519(c, sk, n, static_cast<const uint8_t*>(d_pts),
+                    reinterpret_cast<uint32_t*>(d_out)));
+  if (d_out != out) {
+    HIPCHK(hipMemcpyAsync(out, d_out, n * 32, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipMemsetAsync(d_out, 0, n * 32, c->stream));
+  }
+  HIPCHK(hipStreamSynchronize(c->stream));
+  return 0;
 }
 
 int prio3gpu_prof_enable(prio3gpu_ctx* c, int on) {

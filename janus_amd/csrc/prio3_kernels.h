@@ -2227,17 +2227,16 @@ __constant__ uint32_t kSha256K[64] = {
 DEVI uint32_t rotr32(uint32_t x, uint32_t n) { return __builtin_amdgcn_alignbit(x, x, n); }
 DEVI uint32_t bswap32(uint32_t x) { return __builtin_bswap32(x); }
 
-// SHA-256 of a 16-byte message (one padded block): h = digest as 8 big-endian state words.
-DEVI void sha256_16(const uint8_t* m, uint32_t h[8]) {
-  uint32_t w[16];
-#pragma unroll
-  for (int i = 0; i < 4; ++i) w[i] = bswap32(*reinterpret_cast<const uint32_t*>(m + 4 * i));
-  w[4] = 0x80000000u;
-#pragma unroll
-  for (int i = 5; i < 15; ++i) w[i] = 0u;
-  w[15] = 128u;  // message length in bits
-  const uint32_t iv[8] = {0x6a09e667, 0xbb67ae85, 0x3c6ef372, 0xa54ff53a,
-                          0x510e527f, 0x9b05688c, 0x1f83d9ab, 0x5be0cd19};
+DEVI void sha256_iv(uint32_t h[8]) {
+  h[0] = 0x6a09e667; h[1] = 0xbb67ae85; h[2] = 0x3c6ef372; h[3] = 0xa54ff53a;
+  h[4] = 0x510e527f; h[5] = 0x9b05688c; h[6] = 0x1f83d9ab; h[7] = 0x5be0cd19;
+}
+
+// One SHA-256 compression: h (8 big-endian state words) absorbs the 64-byte block given as 16
+// big-endian words (w is consumed as the message schedule).  Multi-block messages and HMAC
+// (hpke_gpu.h) chain it; fully unrolled, so constant block words fold away.
+DEVI void sha256_compress(uint32_t h[8], uint32_t w[16]) {
+  const uint32_t iv[8] = {h[0], h[1], h[2], h[3], h[4], h[5], h[6], h[7]};
   uint32_t a = iv[0], b = iv[1], c = iv[2], d = iv[3], e = iv[4], f = iv[5], g = iv[6], hh = iv[7];
 #pragma unroll
   for (int t = 0; t < 64; ++t) {
@@ -2260,6 +2259,19 @@ DEVI void sha256_16(const uint8_t* m, uint32_t h[8]) {
   }
   h[0] = iv[0] + a; h[1] = iv[1] + b; h[2] = iv[2] + c; h[3] = iv[3] + d;
   h[4] = iv[4] + e; h[5] = iv[5] + f; h[6] = iv[6] + g; h[7] = iv[7] + hh;
+}
+
+// SHA-256 of a 16-byte message (one padded block): h = digest as 8 big-endian state words.
+DEVI void sha256_16(const uint8_t* m, uint32_t h[8]) {
+  uint32_t w[16];
+#pragma unroll
+  for (int i = 0; i < 4; ++i) w[i] = bswap32(*reinterpret_cast<const uint32_t*>(m + 4 * i));
+  w[4] = 0x80000000u;
+#pragma unroll
+  for (int i = 5; i < 15; ++i) w[i] = 0u;
+  w[15] = 128u;  // message length in bits
+  sha256_iv(h);
+  sha256_compress(h, w);
 }
 
 struct WaveMeta {

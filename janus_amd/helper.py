@@ -8,6 +8,7 @@ Per aggregation job (one AggregationJobInitializeReq):
      fails it too (`EmptyAggregation`, aggregator.rs:1851-1863); gather the engine inputs and
      each report's structural faults                                 codec.cpp   (aggregator.rs:1561-1612)
   2. HPKE-open every encrypted input share on host threads            hpke.cpp    (aggregator.rs:1634-1700)
+     (hpke="gpu": X25519 / HKDF-SHA256 / AES-128-GCM shares on the GPU, hpke_gpu.h)
   3. decode the PlaintextInputShares into the input-share array, then apply the structural
      faults to the reports still OK (Janus's precedence: HPKE 3/4, plaintext/input share 8,
      public share 8, ping-pong 5)                                                 (aggregator.rs:1702-1797)
@@ -94,9 +95,25 @@ class HelperAggregateInit:
     def __init__(self, vdaf: Prio3Gpu, task_id: bytes, task_keys: Sequence[hpke.HpkeKeypair],
                  global_keys: Sequence[hpke.HpkeKeypair] = (), query_type: int = C.TIME_INTERVAL,
                  hpke_threads: int = 0,
-                 batch_slot_of: Optional[Callable[[np.ndarray], np.ndarray]] = None):
+                 batch_slot_of: Optional[Callable[[np.ndarray], np.ndarray]] = None,
+                 hpke: str = "host"):
         """`batch_slot_of(times) -> slots` maps report times to aggregate slots (Janus's
-        Q::to_batch_identifier, aggregator.rs:1614-1619); None = one slot."""
+        Q::to_batch_identifier, aggregator.rs:1614-1619); None = one slot.
+
+        `hpke` = "host" (default): step 2 on `hpke_threads` host threads; "gpu": the reports
+        whose first-choice key is X25519 / HKDF-SHA256 / AES-128-GCM are opened on the GPU
+        (hpke.open_report_shares(gpu=...)), the rest on the host threads.  `open` still runs on
+        the pipeline's host worker while the driver thread prepares the previous job, and a
+        context serves one thread at a time, so the driver owns a second context on the same
+        device for HPKE."""
+        if hpke not in ("host", "gpu"):
+            raise ValueError('hpke must be "host" or "gpu"')
+        self.hpke_mode = hpke
+        self._hpke_ctx = None
+        if hpke == "gpu":
+            self._hpke_ctx = Prio3Gpu(vdaf.kind, vdaf.verify_key, bits=vdaf.bits,
+                                      length=vdaf.length, chunk_length=vdaf.chunk_length,
+                                      device=vdaf.device, xof=vdaf.xof)
         self.vdaf = vdaf
         self.task_id = bytes(task_id)
         self.task_keys = list(task_keys)
@@ -122,7 +139,8 @@ class HelperAggregateInit:
         try:
             nonces, pub, lps, faults = C.gather_prepare_inits(s, req, lps_out=buf)
             pts, offs, st = hpke.open_report_shares(self.task_id, req, self.task_keys,
-                                                    self.global_keys, None, self.hpke_threads)
+                                                    self.global_keys, None, self.hpke_threads,
+                                                    gpu=self._hpke_ctx)
             hin, st = C.decode_plaintext_input_shares_raw(s, pts, offs, 1, st)
             C.apply_faults(st, faults)
             slots = None
@@ -195,4 +213,7 @@ class HelperAggregateInit:
         if self._state is not None:
             self._state.close()
             self._state = None
+        if self._hpke_ctx is not None:
+            self._hpke_ctx.close()
+            self._hpke_ctx = None
         self._pinned.clear()

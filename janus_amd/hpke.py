@@ -150,16 +150,74 @@ def input_share_aad(task_id: bytes, report_id: bytes, time: int, public_share: b
             + len(public_share).to_bytes(4, "big") + bytes(public_share))
 
 
+def _ctx_handle(gpu):
+    """A `Prio3Gpu` (its context) or a raw prio3gpu_ctx handle."""
+    return getattr(gpu, "_ctx", gpu)
+
+
+def _ptr(x, dtype):
+    """Host numpy array -> (pointer, keep-alive); an int / c_void_p is a device pointer."""
+    if isinstance(x, (int, ctypes.c_void_p)):
+        return x, None
+    a = np.ascontiguousarray(x, dtype)
+    return a.ctypes.data, a
+
+
+def open_batch_gpu(gpu, keypair: HpkeKeypair, info: bytes, encs, aads, aad_offsets, cts,
+                   ct_offsets, pts=None, pt_offsets=None, status=None, n: Optional[int] = None):
+    """n HPKE opens under ONE keypair on the GPU (prio3gpu_hpke_open_batch; X25519 /
+    HKDF-SHA256 / AES-128-GCM only -- `ValueError` for any other suite, nothing launched).
+
+    `gpu` is a `Prio3Gpu` or a context handle.  Report i: enc = encs[32 i : 32 i + 32], aad =
+    aads[aad_offsets[i] : aad_offsets[i+1]], ciphertext || tag = cts[ct_offsets[i] :
+    ct_offsets[i+1]].  Buffers are numpy arrays (host) or integer device pointers (then `n`,
+    `pts`, `pt_offsets` and `status` must be given).  By default plaintext i has the ciphertext's
+    length - 16 and the plaintexts are packed.
+    -> (plaintexts, pt_offsets, status); a failed open has status 4 and zeros."""
+    c = keypair.config
+    if n is None:
+        n = len(np.asarray(ct_offsets)) - 1
+    if pt_offsets is None:
+        lens = np.diff(np.asarray(ct_offsets, np.uint64).astype(np.int64)) - 16
+        pt_offsets = np.concatenate([[0], np.cumsum(np.maximum(lens, 0))]).astype(np.uint64)
+    if pts is None:
+        pts = np.zeros(max(1, int(np.asarray(pt_offsets)[-1])), np.uint8)
+    if status is None:
+        status = np.zeros(max(1, n), np.uint8)
+    keep = []
+    args = []
+    for x, dt in ((encs, np.uint8), (aads, np.uint8), (aad_offsets, np.uint64), (cts, np.uint8),
+                  (ct_offsets, np.uint64), (pts, np.uint8), (pt_offsets, np.uint64),
+                  (status, np.uint8)):
+        p, k = _ptr(x, dt)
+        args.append(p)
+        keep.append(k)
+    for out, k in ((pts, keep[5]), (status, keep[7])):  # outputs must be written in place
+        assert k is None or k is out, "pts / status must be contiguous uint8 arrays"
+    _rc(lib().prio3gpu_hpke_open_batch(_ctx_handle(gpu), c.kem_id, c.kdf_id, c.aead_id,
+                                       _buf(keypair.private_key), len(keypair.private_key),
+                                       _buf(c.public_key), len(c.public_key), _buf(info),
+                                       len(info), n, *args), "HPKE GPU open")
+    del keep
+    return pts, pt_offsets, status
+
+
 def open_report_shares(task_id: bytes, req, task_keys: Sequence[HpkeKeypair],
                        global_keys: Sequence[HpkeKeypair] = (),
                        status: Optional[np.ndarray] = None, threads: int = 0,
-                       recipient_role: int = ROLE_HELPER):
+                       recipient_role: int = ROLE_HELPER, gpu=None):
     """Open every encrypted input share of a decoded AggregationJobInitializeReq
-    (`janus_amd.codec.AggInitReq`) on `threads` host threads (0: all cores).
+    (`janus_amd.codec.AggInitReq`) on `threads` host threads (0: all cores).  With `gpu` (a
+    `Prio3Gpu` or a context handle) the reports whose first-choice key is X25519 / HKDF-SHA256 /
+    AES-128-GCM are opened on that context's GPU instead (prio3gpu_hpke_open_report_shares_gpu);
+    statuses, offsets and plaintexts are the host path's.
 
     -> (plaintexts uint8 array, offsets (n + 1), status); report i's PlaintextInputShare is
     plaintexts[offsets[i]:offsets[i+1]] -- the input of codec.decode_plaintext_input_shares_raw.
     Status 3 = HpkeUnknownConfigId, 4 = HpkeDecryptError (aggregator.rs:1634-1700)."""
+    if gpu is not None:
+        return _open_report_shares_gpu(_ctx_handle(gpu), task_id, req, task_keys, global_keys,
+                                       status, threads, recipient_role)
     n = req.n
     st = np.zeros(n, np.uint8) if status is None else status
     offs = np.zeros(n + 1, np.uint64)
@@ -178,5 +236,26 @@ def open_report_shares(task_id: bytes, req, task_keys: Sequence[HpkeKeypair],
                                            req.raw.ctypes.data, req.views, n, pts.ctypes.data,
                                            offs.ctypes.data, st.ctypes.data, threads),
         "open report shares")
+    del keep_t, keep_g
+    return pts, offs, st
+
+
+def _open_report_shares_gpu(ctx, task_id, req, task_keys, global_keys, status, threads,
+                            recipient_role):
+    n = req.n
+    st = np.zeros(n, np.uint8) if status is None else status
+    offs = np.zeros(n + 1, np.uint64)
+    tid = np.frombuffer(bytes(task_id), np.uint8).copy()
+    assert tid.size == 32, "TaskId is 32 bytes"
+    tk, keep_t = _keypairs(task_keys)
+    gk, keep_g = _keypairs(global_keys)
+    f = lib().prio3gpu_hpke_open_report_shares_gpu
+    _rc(f(ctx, tid.ctypes.data, tk, len(task_keys), gk, len(global_keys), ROLE_CLIENT,
+          recipient_role, req.raw.ctypes.data, req.views, n, None, offs.ctypes.data,
+          st.ctypes.data, threads), "size")
+    pts = np.zeros(max(1, int(offs[-1])), np.uint8)
+    _rc(f(ctx, tid.ctypes.data, tk, len(task_keys), gk, len(global_keys), ROLE_CLIENT,
+          recipient_role, req.raw.ctypes.data, req.views, n, pts.ctypes.data, offs.ctypes.data,
+          st.ctypes.data, threads), "open report shares (GPU)")
     del keep_t, keep_g
     return pts, offs, st

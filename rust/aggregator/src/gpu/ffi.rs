@@ -292,6 +292,24 @@ extern "C" {
                                             plaintexts: *mut u8, offsets: *mut u64,
                                             status: *mut u8, threads: c_int) -> c_int;
 
+    // -- HPKE open on the GPU (X25519 / HKDF-SHA256 / AES-128-GCM) ----------------------------
+    pub fn prio3gpu_hpke_open_batch(ctx: *mut prio3gpu_ctx, kem_id: u16, kdf_id: u16,
+                                    aead_id: u16, sk: *const u8, sk_len: usize, pk: *const u8,
+                                    pk_len: usize, info: *const u8, info_len: usize, n: usize,
+                                    encs: *const u8, aads: *const u8, aad_offsets: *const u64,
+                                    cts: *const u8, ct_offsets: *const u64, pts: *mut u8,
+                                    pt_offsets: *const u64, status: *mut u8) -> c_int;
+    pub fn prio3gpu_hpke_open_report_shares_gpu(ctx: *mut prio3gpu_ctx, task_id: *const u8,
+                                                task_keys: *const prio3gpu_hpke_keypair,
+                                                n_task_keys: usize,
+                                                global_keys: *const prio3gpu_hpke_keypair,
+                                                n_global_keys: usize, sender_role: u8,
+                                                recipient_role: u8, msg: *const u8,
+                                                views: *const prio3gpu_prepare_init_view,
+                                                n: usize, plaintexts: *mut u8,
+                                                offsets: *mut u64, status: *mut u8,
+                                                threads: c_int) -> c_int;
+
     // -- errors and build identity ------------------------------------------------------------
     pub fn prio3gpu_last_error() -> *const c_char;
     pub fn prio3gpu_build_hash() -> *const c_char;

@@ -6,7 +6,7 @@ while the GPU prepares job k).  Prio3SumVec(8, 1000, 89).  Inputs: seeded random
 randomness and measurements, shares from the GPU client shard, leader prep shares from the GPU leader prepare_init, helper shares sealed to
 one X25519/HKDF-SHA256/AES-128-GCM key -- all made before timing.
 
-  python tools/bench_helper_e2e.py --jobs 8 --job-size 16384 --threads 16
+  python tools/bench_helper_e2e.py --jobs 8 --job-size 16384 --threads 16 [--hpke gpu]
 """
 import argparse
 import hashlib
@@ -34,6 +34,8 @@ def main():
     ap.add_argument("--job-size", type=int, default=16384)
     ap.add_argument("--threads", type=int, default=16)
     ap.add_argument("--reps", type=int, default=2)
+    ap.add_argument("--hpke", choices=("host", "gpu"), default="host",
+                    help="where the helper input shares are opened (HelperAggregateInit hpke=)")
     args = ap.parse_args()
     dev = torch.device("cuda", 0)
     kind, bits, length, chunk, label = CONFIGS["sumvec"]
@@ -74,15 +76,18 @@ def main():
     ls.close()
     hs0.close()
     gen_s = time.time() - t0
-    drv = HelperAggregateInit(v, task_id, [tk], hpke_threads=args.threads)
+    drv = HelperAggregateInit(v, task_id, [tk], hpke_threads=args.threads, hpke=args.hpke)
     agg = v.new_aggregate(1)
     drv.handle_jobs(reqs[:1], agg)  # warm (allocates the state)
     agg = v.new_aggregate(1)
     torch.cuda.synchronize()
     t0 = time.perf_counter()
+    rep_s = []
     for _ in range(args.reps):
+        t = time.perf_counter()
         resps = drv.handle_jobs(reqs, agg)
-    torch.cuda.synchronize()
+        torch.cuda.synchronize()
+        rep_s.append(time.perf_counter() - t)
     dt = time.perf_counter() - t0
     n = J * M * args.reps
     for j, resp in enumerate(resps):
@@ -101,7 +106,8 @@ def main():
     nonces_, pub_, lps_, faults_ = C.gather_prepare_inits(s, req)
     stages["check_gather"] = time.perf_counter() - t
     t = time.perf_counter()
-    pts, offs, st_ = H.open_report_shares(task_id, req, [tk], [], None, args.threads)
+    pts, offs, st_ = H.open_report_shares(task_id, req, [tk], [], None, args.threads,
+                                          gpu=drv._hpke_ctx)
     stages["hpke_open"] = time.perf_counter() - t
     t = time.perf_counter()
     C.decode_plaintext_input_shares_raw(s, pts, offs, 1, st_)
@@ -121,7 +127,8 @@ def main():
                 "threads) -> GPU prepare+decide+prepare_next+accumulate -> response bytes, "
                 "pipelined over jobs",
         "value": round(n / dt, 1), "unit": "reports/s", "jobs": J, "job_size": M,
-        "reps": args.reps, "hpke_threads": args.threads, "seconds": round(dt, 3),
+        "reps": args.reps, "hpke": args.hpke, "hpke_threads": args.threads, "seconds": round(dt, 3),
+        "reports_per_s_by_rep": [round(J * M / x) for x in rep_s],
         "request_mb_per_job": round(len(reqs[0]) / 1e6, 1), "gen_seconds": round(gen_s, 1),
         "workload": label, "stage_ms_per_job": stages}))
 

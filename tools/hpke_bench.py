@@ -1,22 +1,106 @@
-# Batched helper HPKE open rate vs host threads (tools/hpke_bench.py 1,8,16 [scalar]: 'scalar' = the
-# scalar X25519 ladder for every report, prio3gpu_test_hpke_set_ifma(0))
-import sys, time, os
-sys.path.insert(0,'/root/repo'); sys.path.insert(0,'/root/repo/tests')
-import numpy as np
-from janus_amd import codec as C, hpke as H
-from test_hpke import _request
-rng=np.random.default_rng(1); n=4096
-task_id=bytes(32); tk=H.generate_hpke_config_and_private_key(1)
-nonces=rng.integers(0,256,(n,16),dtype=np.uint8); public=rng.integers(0,256,(n,32),dtype=np.uint8)
-payloads=[bytes(48) for _ in range(n)]
-if len(sys.argv) > 2 and sys.argv[2] == 'scalar':
-    from janus_amd._lib import lib
-    lib().prio3gpu_test_hpke_set_ifma(0)
-req=C.decode_agg_init_req(_request(task_id,nonces,[0]*n,public,payloads,[tk]*n))
-for th in [int(x) for x in sys.argv[1].split(",")]:
-    H.open_report_shares(task_id,req,[tk],[],None,th)
-    t=time.perf_counter(); r=0
-    while time.perf_counter()-t<1.5:
-        _,_,st=H.open_report_shares(task_id,req,[tk],[],None,th); r+=1
-    dt=time.perf_counter()-t; assert (st==0).all()
-    print(th, f"{r*n/dt:.0f} opens/s  {dt/(r*n)*th*1e6:.1f} us/open/thread")
+"""Batched helper HPKE open rate: host threads vs the GPU open, same request builder.
+
+  python tools/hpke_bench.py host --threads 1,8,16 [--scalar]   host threads ('--scalar': the
+                                                    scalar X25519 ladder for every report,
+                                                    prio3gpu_test_hpke_set_ifma(0))
+  python tools/hpke_bench.py gpu --n 4096,65536,1048576 --threads 16
+                                                    prio3gpu_hpke_open_report_shares_gpu, with
+                                                    the per-kernel HIP-event times of one call
+  python tools/hpke_bench.py both --n 65536 --threads 16    both on the same request
+  python tools/hpke_bench.py 1,8,16 [scalar]        the former spelling of `host`
+
+Each figure is the median of --reps timed calls after one warm-up call, with the min..max spread;
+one JSON line per (mode, n, threads)."""
+import argparse
+import json
+import os
+import statistics
+import sys
+import time
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.join(ROOT, "tests"))
+
+import numpy as np  # noqa: E402
+
+from janus_amd import codec as C, hpke as H  # noqa: E402
+from janus_amd._lib import lib  # noqa: E402
+from test_hpke import _request  # noqa: E402
+
+
+def build_request(n, tk, task_id):
+    rng = np.random.default_rng(1)
+    nonces = rng.integers(0, 256, (n, 16), dtype=np.uint8)
+    public = rng.integers(0, 256, (n, 32), dtype=np.uint8)
+    payloads = [bytes(48)] * n
+    return C.decode_agg_init_req(_request(task_id, nonces, [0] * n, public, payloads, [tk] * n))
+
+
+def timed(fn, reps):
+    fn()  # warm-up: scratch growth, first launches
+    ts = []
+    for _ in range(reps):
+        t = time.perf_counter()
+        st = fn()
+        ts.append(time.perf_counter() - t)
+        assert (st == 0).all()
+    return ts
+
+
+def kernel_ms(ctx, fn):
+    """HIP-event time per kernel of one call (prio3gpu_prof_*)."""
+    import ctypes
+    L = lib()
+    ms, launches = (ctypes.c_double * 64)(), (ctypes.c_uint64 * 64)()
+    L.prio3gpu_prof_enable(ctx, 1)
+    L.prio3gpu_prof_read(ctx, ms, launches, 64)
+    fn()
+    k = L.prio3gpu_prof_read(ctx, ms, launches, 64)
+    L.prio3gpu_prof_enable(ctx, 0)
+    return {L.prio3gpu_prof_kernel_name(i).decode(): round(ms[i], 3)
+            for i in range(k) if launches[i]}
+
+
+def main():
+    argv = sys.argv[1:]
+    if argv and argv[0][0].isdigit():  # former spelling: THREADS [scalar]
+        argv = ["host", "--threads", argv[0]] + (["--scalar"] if "scalar" in argv[1:] else [])
+    ap = argparse.ArgumentParser()
+    ap.add_argument("mode", choices=("host", "gpu", "both"))
+    ap.add_argument("--threads", default="16")
+    ap.add_argument("--n", default="4096")
+    ap.add_argument("--reps", type=int, default=7)
+    ap.add_argument("--scalar", action="store_true")
+    args = ap.parse_args(argv)
+    if args.scalar:
+        lib().prio3gpu_test_hpke_set_ifma(0)
+    task_id = bytes(32)
+    tk = H.generate_hpke_config_and_private_key(1)
+    gpu = None
+    if args.mode != "host":
+        from janus_amd.prio3 import Prio3Gpu
+        gpu = Prio3Gpu.new_count(bytes(16))
+    for n in [int(x) for x in args.n.split(",")]:
+        req = build_request(n, tk, task_id)
+        for th in [int(x) for x in args.threads.split(",")]:
+            for mode in (("host", "gpu") if args.mode == "both" else (args.mode,)):
+                g = gpu if mode == "gpu" else None
+
+                def call():
+                    return H.open_report_shares(task_id, req, [tk], [], None, th, gpu=g)[2]
+
+                ts = timed(call, args.reps)
+                med = statistics.median(ts)
+                out = {"mode": mode, "n": n, "threads": th, "reps": args.reps,
+                       "opens_per_s": round(n / med), "ms_per_call": round(med * 1e3, 3),
+                       "ms_min": round(min(ts) * 1e3, 3), "ms_max": round(max(ts) * 1e3, 3)}
+                if mode == "host":
+                    out["us_per_open_per_thread"] = round(med / n * th * 1e6, 2)
+                else:
+                    out["kernel_ms"] = kernel_ms(gpu._ctx, call)
+                print(json.dumps(out), flush=True)
+
+
+if __name__ == "__main__":
+    main()
