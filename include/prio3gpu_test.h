@@ -1,7 +1,8 @@
 /* prio3gpu_test.h -- test and benchmark hooks of libprio3gpu.so, kept out of the product ABI
  * (include/prio3gpu.h).  A Janus build binds only prio3gpu.h (rust/aggregator/src/gpu/ffi.rs);
  * these entry points exist for the parity tests (tests/test_gpu_squeeze.py,
- * tests/test_gpu_flp_branches.py) and the host benchmarks (tools/hpke_bench.py). */
+ * tests/test_gpu_flp_branches.py, tests/test_gpu_field_ops.py) and the host benchmarks
+ * (tools/hpke_bench.py). */
 #ifndef PRIO3GPU_TEST_H
 #define PRIO3GPU_TEST_H
 
@@ -45,6 +46,38 @@ int prio3gpu_test_hpke_set_ifma(int on);
  * GPU counterpart of prio3gpu_x25519_batch.  points / out may be host or device memory. */
 int prio3gpu_test_x25519_gpu(prio3gpu_ctx* ctx, const uint8_t* sk, const uint8_t* points, size_t n,
                              uint8_t* out);
+
+/* TEST ONLY.  One field primitive over caller-supplied operands, one lane per tuple: the device
+ * functions the product kernels call (Field128Ops / Field64Ops, the generated carry chains and
+ * fused Montgomery programs, the lazy dot product, the inverses), run alone so that tests can
+ * feed them the operands uniform XOF output never produces (tests/test_gpu_field_ops.py).
+ * field_size 8 or 16; in is n x arity(op) x field_size bytes of little-endian elements, out
+ * n x results(op) x field_size bytes, both host memory.  op (operands -> results; R = 2^64 or
+ * 2^128; "128" = Field128 only):
+ *    0 add  1 sub            a b -> a + b, a - b
+ *    2 neg  3 dbl            a -> -a, 2a
+ *    4 mul                   a b -> a b / R
+ *    5 to_mont  6 from_mont  a -> a R, a / R
+ *    7 is_canonical          any field_size-byte value -> 1 if < p, else 0
+ *    8 inv                   x -> R^2 / x (Montgomery in and out), 0 -> 0
+ *    9 inv_plain (128)       x -> 1 / x, 0 -> 0
+ *   10 pow                   x -> x^param in Montgomery form (x R -> x^param R)
+ *   11 mul2  12 mul3  13 mul5 (128)   a0 b0 .. a(k-1) b(k-1) -> k products a_s b_s / R
+ *   14 fma2_mul1 (128)       a0 b0 c0 d0  a1 b1 c1 d1  a2 b2
+ *                            -> (a0 b0 + c0 d0)/R, (a1 b1 + c1 d1)/R, a2 b2/R
+ *   15 q1_fma1_mul1 (128)    a0 b0 c0 d0 e0 f0 i0 j0  a1 b1 c1 d1  a2 b2
+ *                            -> (a0 b0 + c0 d0 + e0 f0 + i0 j0)/R, (a1 b1 + c1 d1)/R, a2 b2/R
+ *   16 addsub_AASS (128)     a0 b0 .. a3 b3 -> a0 + b0, a1 + b1, a2 - b2, a3 - b3
+ *   17 addsub_ASAA (128)     a0 b0 .. a3 b3 -> a0 + b0, a1 - b1, a2 + b2, a3 + b3
+ *   18 addsub_A (128)        a b -> a + b
+ *   19 dot (128)             a_0 x_0 .. a_(param-1) x_(param-1) -> (sum a_k x_k) / R,
+ *                            1 <= param < 2^30
+ *   20 limb_sums (128)       four little-endian u64 xs[0..3] (32 bytes) -> sum xs[q] 2^(32 q)
+ * All results are canonical (mod p).  Inputs must be < p except for is_canonical and limb_sums.
+ * n == 0 returns 0 and launches nothing; an unknown op, a Field128-only op with field_size 8, or
+ * null pointers with n > 0 return PRIO3GPU_E_ARG.  Runs on the current HIP device. */
+int prio3gpu_test_field_op(int field_size, int op, uint32_t param, const uint8_t* in, size_t n,
+                           uint8_t* out);
 
 #ifdef __cplusplus
 }

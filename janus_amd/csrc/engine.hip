@@ -23,6 +23,7 @@
 #include "fpvec_mfma.h"
 #include "fpvec_pair.h"
 #include "hpke_gpu.h"
+#include "field_test_kernels.h"
 
 using namespace p3g;
 
@@ -2551,6 +2552,92 @@ int prio3gpu_test_squeeze(int field_size, const uint64_t* blocks, size_t nblocks
   if (d_blocks) (void)hipFree(d_blocks);
   if (d_out) (void)hipFree(d_out);
   if (d_over) (void)hipFree(d_over);
+  return rc;
+}
+
+// Test-only: one field primitive per lane over caller-supplied operands (field_test_kernels.h
+// states the operand order of every op).  Null stream of the current device, like test_squeeze.
+int prio3gpu_test_field_op(int field_size, int op, uint32_t param, const uint8_t* in, size_t n,
+                           uint8_t* out) {
+  const bool f128 = field_size == 16;
+  if ((field_size != 8 && field_size != 16) || op < 0 || op >= FT_NOPS ||
+      (!f128 && !field_test_op_has_field64(op))) {
+    set_err("test_field_op: unknown op %d for field size %d", op, field_size);
+    return PRIO3GPU_E_ARG;
+  }
+  // wide_mac's accumulators hold < 2^30 terms
+  if (op == FT_DOT && (param == 0 || param >= (1u << 30))) {
+    set_err("test_field_op: dot needs 1 <= param < 2^30 terms");
+    return PRIO3GPU_E_ARG;
+  }
+  if (n == 0) return 0;
+  const size_t arity = op == FT_DOT ? 2 * (size_t)param : field_test_arity(op);
+  const size_t results = field_test_results(op);
+  if (!in || !out || n > (1u << 24) || arity > ((size_t)1 << 26) / n) {  // <= 1 GiB of operands
+    set_err("test_field_op: bad argument");
+    return PRIO3GPU_E_ARG;
+  }
+  const size_t ib = n * arity * (size_t)field_size, ob = n * results * (size_t)field_size;
+  void *d_in = nullptr, *d_out = nullptr;
+  int rc = 0;
+  if (hipMalloc(&d_in, ib) != hipSuccess || hipMalloc(&d_out, ob) != hipSuccess) {
+    set_err("test_field_op: hipMalloc failed");
+    rc = PRIO3GPU_E_HIP;
+  }
+  if (!rc && (hipMemcpy(d_in, in, ib, hipMemcpyHostToDevice) != hipSuccess ||
+              hipMemset(d_out, 0, ob) != hipSuccess)) {
+    set_err("test_field_op: copy failed");
+    rc = PRIO3GPU_E_HIP;
+  }
+  if (!rc) {
+    const dim3 grid((unsigned)((n + 63) / 64)), block(64);
+    const uint8_t* di = static_cast<const uint8_t*>(d_in);
+    uint8_t* dout = static_cast<uint8_t*>(d_out);
+#define FT_LAUNCH(FO, OP) \
+  hipLaunchKernelGGL((k_test_field_op<FO, OP>), grid, block, 0, nullptr, (uint32_t)n, param, di, dout)
+#define FT_BOTH(OP)                          \
+  case OP:                                   \
+    if (f128) FT_LAUNCH(Field128Ops, OP);    \
+    else FT_LAUNCH(Field64Ops, OP);          \
+    break;
+#define FT_128(OP)                \
+  case OP:                        \
+    FT_LAUNCH(Field128Ops, OP);   \
+    break;
+    switch (op) {
+      FT_BOTH(FT_ADD)
+      FT_BOTH(FT_SUB)
+      FT_BOTH(FT_NEG)
+      FT_BOTH(FT_DBL)
+      FT_BOTH(FT_MUL)
+      FT_BOTH(FT_TO_MONT)
+      FT_BOTH(FT_FROM_MONT)
+      FT_BOTH(FT_IS_CANONICAL)
+      FT_BOTH(FT_INV)
+      FT_BOTH(FT_POW)
+      FT_128(FT_INV_PLAIN)
+      FT_128(FT_MUL2)
+      FT_128(FT_MUL3)
+      FT_128(FT_MUL5)
+      FT_128(FT_FMA2_MUL1)
+      FT_128(FT_Q1_FMA1_MUL1)
+      FT_128(FT_ADDSUB_AASS)
+      FT_128(FT_ADDSUB_ASAA)
+      FT_128(FT_ADDSUB_A)
+      FT_128(FT_DOT)
+      FT_128(FT_LIMB_SUMS)
+    }
+#undef FT_128
+#undef FT_BOTH
+#undef FT_LAUNCH
+    if (hipGetLastError() != hipSuccess || hipDeviceSynchronize() != hipSuccess ||
+        hipMemcpy(out, d_out, ob, hipMemcpyDeviceToHost) != hipSuccess) {
+      set_err("test_field_op: kernel failed");
+      rc = PRIO3GPU_E_HIP;
+    }
+  }
+  if (d_in) (void)hipFree(d_in);
+  if (d_out) (void)hipFree(d_out);
   return rc;
 }
 

@@ -119,7 +119,9 @@ def open_(keypair: HpkeKeypair, info: bytes, enc: bytes, payload: bytes, aad: by
     _rc(lib().prio3gpu_hpke_open(c.kem_id, c.kdf_id, c.aead_id, _buf(keypair.private_key),
                                  len(keypair.private_key), _buf(c.public_key), len(c.public_key),
                                  _buf(enc), len(enc), _buf(info), len(info), _buf(aad), len(aad),
-                                 _buf(payload), len(payload), pt, n, ctypes.byref(ln)),
+                                 # an empty payload is a decryption failure, not a null argument
+                                 ctypes.c_char_p(bytes(payload)), len(payload), pt, n,
+                                 ctypes.byref(ln)),
         "HPKE open")
     return pt.raw[:ln.value]
 

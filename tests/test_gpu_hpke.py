@@ -186,6 +186,121 @@ def test_length_sweep(gpu):
     assert pts == want
 
 
+# ---- 3a. short ciphertexts, long plaintexts -------------------------------------------------------
+def _host_open(kp, info, item):
+    """(status, plaintext) of the host implementation (hpke.cpp) for one (enc, aad, ct)."""
+    enc, aad, ct = item
+    try:
+        return 0, H.open_(kp, info, enc, ct, aad)
+    except H.HpkeError:
+        return 4, bytes(max(0, len(ct) - 16))
+
+
+SHORT_CT_LENS = (0, 1, 15)
+
+
+def _short_items(kp, rng):
+    """Ciphertexts shorter than a tag (0, 1, 15 bytes), the shortest valid one (16 bytes: the tag
+    of an empty plaintext) and 16 bytes that are no valid tag, each between intact neighbours."""
+    def sealed(pl):
+        pt = rng.integers(0, 256, pl, dtype=np.uint8).tobytes()
+        aad = rng.integers(0, 256, 20, dtype=np.uint8).tobytes()
+        _, enc, ct = H.seal(kp.config, INFO, pt, aad)
+        return (enc, aad, ct), pt
+    items, want = [], []
+    for kind in SHORT_CT_LENS + ("empty", "badtag"):
+        it, pt = sealed(33)
+        items.append(it)
+        want.append((0, pt))
+        if kind == "empty":
+            it, pt = sealed(0)
+            assert len(it[2]) == 16
+            items.append(it)
+            want.append((0, b""))
+        elif kind == "badtag":
+            (enc, aad, ct), _ = sealed(0)
+            items.append((enc, aad, _flip(ct, 77)))
+            want.append((4, b""))
+        else:
+            (enc, aad, ct), _ = sealed(40)
+            items.append((enc, aad, ct[:kind]))
+            want.append((4, b""))
+    it, pt = sealed(17)
+    return items + [it], want + [(0, pt)]
+
+
+def test_short_ciphertexts(gpu):
+    kp = H.generate_hpke_config_and_private_key(1)
+    items, want = _short_items(kp, np.random.default_rng(31))
+    assert [len(it[2]) for it in items[1::2]] == [0, 1, 15, 16, 16]
+    host = [_host_open(kp, INFO, it) for it in items]
+    assert host == want
+    pts, st = _open(gpu, kp, INFO, items)
+    assert [(int(st[i]), pts[i]) for i in range(len(items))] == want
+    # the short ones first and last in the batch, and alone
+    for order in (items[1::2] + items[0::2], items[0::2] + items[1::2], items[1:2], items[5:6]):
+        pts, st = _open(gpu, kp, INFO, order)
+        assert [(int(st[i]), pts[i]) for i in range(len(order))] == \
+            [_host_open(kp, INFO, it) for it in order]
+
+
+def test_short_ciphertexts_in_report_shares(gpu):
+    rng = np.random.default_rng(32)
+    task_id = bytes(range(1, 33))
+    tk = H.generate_hpke_config_and_private_key(1)
+    lens = [48, 0, 48, 1, 48, 15, 48, 16, 48]  # payload lengths; 16 = the tag of an empty plaintext
+    n = len(lens)
+    nonces = rng.integers(0, 256, (n, 16), dtype=np.uint8)
+    times = [1_700_000_000 + i for i in range(n)]
+    public = rng.integers(0, 256, (n, 32), dtype=np.uint8)
+    cts, pts_want = [], []
+    for i, ln in enumerate(lens):
+        aad = H.input_share_aad(task_id, nonces[i].tobytes(), times[i], public[i].tobytes())
+        pt = rng.integers(0, 256, 32 if ln == 48 else 0, dtype=np.uint8).tobytes()
+        cid, enc, ct = H.seal(tk.config, INFO, pt if ln >= 16 else bytes(24), aad)
+        cts.append((cid, enc, ct[:ln] if ln < 16 else ct))
+        assert len(cts[-1][2]) == ln
+        pts_want.append(pt)
+    req = C.decode_agg_init_req(bytearray(C.encode_agg_init_req(
+        C.TIME_INTERVAL, None, b"", nonces, times, public, cts, np.zeros((n, 4), np.uint8))))
+    pts, offs, st = _both(gpu, task_id, req, [tk], [], np.zeros(n, np.uint8), 2)
+    assert st.tolist() == [0, 4, 0, 4, 0, 4, 0, 0, 0]
+    assert np.diff(offs.astype(np.int64)).tolist() == [max(0, ln - 16) for ln in lens]
+    for i in range(n):
+        if st[i] == 0:
+            assert pts[int(offs[i]):int(offs[i + 1])].tobytes() == pts_want[i], i
+
+
+LONG_PT_LENS = (4064, 4080, 4081, 4112)  # 254 .. 257 blocks: CTR counters 2 .. 258 cross 0x100
+
+
+def test_long_plaintexts_and_aad(gpu):
+    kp = H.generate_hpke_config_and_private_key(1)
+    rng = np.random.default_rng(33)
+    items, want = [], []
+    for pl, al in [(pl, 20) for pl in LONG_PT_LENS] + [(54, 4097), (4081, 4097)]:
+        pt = rng.integers(0, 256, pl, dtype=np.uint8).tobytes()
+        aad = rng.integers(0, 256, al, dtype=np.uint8).tobytes()
+        _, enc, ct = H.seal(kp.config, INFO, pt, aad)
+        items.append((enc, aad, ct))
+        want.append(pt)
+    assert [_host_open(kp, INFO, it) for it in items] == [(0, pt) for pt in want]
+    pts, st = _open(gpu, kp, INFO, items)
+    assert (st[:len(items)] == 0).all()
+    assert pts == want
+    # one flipped bit in the last block of the body (and, for the long AAD, in its last byte)
+    bad = []
+    for (enc, aad, ct), pt in zip(items, want):
+        bad.append((enc, aad, _flip(ct, 8 * (len(pt) - 1) + 3)))
+    bad.append((items[4][0], _flip(items[4][1], 8 * 4096 + 5), items[4][2]))
+    mixed = [x for pair in zip(bad, items + items[:1]) for x in pair]  # bad, intact, bad, ...
+    pts, st = _open(gpu, kp, INFO, mixed)
+    assert st[:len(mixed)].tolist() == [4, 0] * len(bad)
+    assert [_host_open(kp, INFO, it)[0] for it in mixed] == [4, 0] * len(bad)
+    for i, it in enumerate(mixed):
+        assert pts[i] == (bytes(len(it[2]) - 16) if i % 2 == 0 else (want + want[:1])[i // 2]), i
+
+
 # ---- 4. report shares, GPU == host ----------------------------------------------------------------
 def _request(task_id, nonces, times, public, payloads, keypairs, prep_share_len=4):
     n = len(nonces)
