@@ -179,12 +179,18 @@ int prio3gpu_ctx_wait_mark(prio3gpu_ctx* ctx, prio3gpu_ctx* other, int mark);
 void* prio3gpu_ctx_stream(prio3gpu_ctx* ctx);
 
 /* Preparation state + device scratch for up to `capacity` reports of one aggregator
- * (Prio3PrepareState for a whole batch).  Every buffer a call on the state can use is allocated
- * here, after checking the total against the device's free memory: a state the device cannot
- * hold is PRIO3GPU_E_CAPACITY (the message gives the bytes needed and free) with nothing
- * allocated, and calls on a created state do not allocate (except the FixedPoint helper's exact
- * path after a non-canonical squeezed element in snapshot mode, which allocates the full rows and
- * also reports a failure as PRIO3GPU_E_CAPACITY).  The GPU HPKE open (prio3gpu_hpke_open_batch,
+ * (Prio3PrepareState for a whole batch).  Every buffer the kernels of a call on the state use is
+ * allocated here, after checking the total against the device's free memory: a state the device
+ * cannot hold is PRIO3GPU_E_CAPACITY (the message gives the bytes needed and free) with nothing
+ * allocated.
+ * Callers that pass device pointers get the no-allocation guarantee: such calls on a created state
+ * never allocate or grow one of its buffers.  Staging of host-pointer inputs, and prio3gpu_shard,
+ * allocate on first use at a new size and report PRIO3GPU_E_CAPACITY if the device cannot hold it.
+ * The context's scratch (accumulation plan and partial sums, staged outputs) grows to the largest
+ * batch the context has seen.
+ * (The one other exception is the FixedPoint helper's exact path after a non-canonical squeezed
+ * element in snapshot mode, which allocates the full rows and also reports a failure as
+ * PRIO3GPU_E_CAPACITY.)  The GPU HPKE open (prio3gpu_hpke_open_batch,
  * prio3gpu_hpke_open_report_shares_gpu) takes no state: its scratch belongs to the CONTEXT and
  * grows on demand to the largest batch the context has opened (PRIO3GPU_E_CAPACITY if the device
  * cannot hold it), so the first call at a new size does allocate. */

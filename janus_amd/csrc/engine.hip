@@ -17,6 +17,8 @@
 #include "../../include/prio3gpu.h"
 #include "../../include/prio3gpu_test.h"
 #include "errors.h"
+#include "plan_cfg.h"
+#include "plan_accum.h"
 #include "prio3_kernels.h"
 #include "fpvec_kernels.h"
 #include "wires_mfma.h"
@@ -68,36 +70,6 @@ namespace {
     if (rc_ != 0) return rc_;    \
   } while (0)
 
-typedef unsigned __int128 u128;
-
-// ---- host modular arithmetic for table setup only ---------------------------------------------
-u128 addmod(u128 x, u128 y, u128 p) {
-  u128 s = x + y;
-  if (s < x || s >= p) s -= p;
-  return s;
-}
-u128 mulmod(u128 a, u128 b, u128 p) {
-  u128 r = 0;
-  a %= p;
-  while (b) {
-    if (b & 1) r = addmod(r, a, p);
-    a = addmod(a, a, p);
-    b >>= 1;
-  }
-  return r;
-}
-u128 powmod(u128 a, u128 e, u128 p) {
-  u128 r = 1;
-  while (e) {
-    if (e & 1) r = mulmod(r, a, p);
-    a = mulmod(a, a, p);
-    e >>= 1;
-  }
-  return r;
-}
-const u128 P128 = ((u128)0xFFFFFFFFFFFFFFE4ull << 64) | 1u;
-const u128 P64 = (u128)0xFFFFFFFF00000001ull;
-
 bool is_device_ptr(const void* p) {
   if (!p) return false;
   hipPointerAttribute_t a;
@@ -109,22 +81,15 @@ bool is_device_ptr(const void* p) {
   return a.type == hipMemoryTypeDevice;
 }
 
-uint32_t next_pow2(uint32_t x) {
-  uint32_t r = 1;
-  while (r < x) r <<= 1;
-  return r;
-}
-uint32_t ilog2(uint32_t x) {
-  uint32_t l = 0;
-  while ((1u << l) < x) ++l;
-  return l;
-}
-
 // Grow-only device buffer; owns its allocation (freed on destruction, never copied).  Every
-// per-state buffer is sized by prio3gpu_state_create, so a call on a state never grows one (a
-// hipFree inside a call would wait for the whole device); the context-level scratch grows to the
-// largest batch it has seen.  An allocation the device cannot hold is PRIO3GPU_E_CAPACITY, with
-// the HIP error cleared so the next launch check of the same context does not report it.
+// per-state buffer the kernels use is sized by prio3gpu_state_create (a hipFree inside a call
+// would wait for the whole device).  Callers that pass device pointers get the no-allocation
+// guarantee: such calls on a created state never allocate or grow one of its buffers.  Staging of
+// host-pointer inputs, and prio3gpu_shard, allocate on first use at a new size and report
+// PRIO3GPU_E_CAPACITY if the device cannot hold it.  The context's scratch (accumulation plan and
+// partial sums, staged outputs) grows to the largest batch the context has seen.  An allocation
+// the device cannot hold is PRIO3GPU_E_CAPACITY, with the HIP error cleared so the next launch
+// check of the same context does not report it.
 struct DevBuf {
   void* p = nullptr;
   size_t cap = 0;
@@ -218,7 +183,6 @@ struct prio3gpu_ctx {
   // prio3gpu_hpke_open_batch: staging of host inputs / outputs (enc, aad, aad offsets, ct, ct
   // offsets, pt, pt offsets, status) and the ladder's DH values; grown on demand
   DevBuf hpke[9];
-  std::vector<uint32_t> h_perm, h_chunk_begin, h_chunk_slot;
   // Engine options (prio3gpu_ctx_set_option; include/prio3gpu.h lists them).  The defaults are the
   // measured-fastest paths; every alternative is parity-tested against the oracle.
   bool speculate = true;     // "speculate": accumulation from k_jr's column sums (0: direct)
@@ -262,13 +226,12 @@ struct prio3gpu_ctx {
   hipEvent_t wait_ev = nullptr;  // prio3gpu_ctx_wait: recorded on the other context, not a mark
   int wait_ev_dev = -1;          // device wait_ev was created on (the other context's)
   std::mutex mark_mu;            // ev_next / ev_gen / wait_ev
-  // the device-side accumulation plan of the last call (single slot, no per-report slots):
-  // reused while (n, speculative layout, slot count) are unchanged -- no host planning, no upload
+  // the accumulation plan of the last call (plan_accum.h), as uploaded to perm / chunks /
+  // spec_idx.  plan_valid: that call had no per-report slots, so a call with an equal key reuses
+  // the plan on the device -- no host planning, no upload
+  AccumPlan plan;
+  AccumKey plan_key;
   bool plan_valid = false;
-  size_t plan_n = 0;
-  uint32_t plan_slots = 0, plan_nd = 0, plan_e0 = 0, plan_e1 = 0;
-  bool plan_spec = false;
-  uint32_t plan_ndir = 0, plan_nspec = 0, plan_nch = 0, plan_tiles = 0, plan_epb = 0;
 };
 
 namespace {
@@ -348,230 +311,41 @@ struct prio3gpu_comm {
 
 namespace {
 
-// prio `optimal_chunk_length` (src/vdaf/prio3.rs, ext): among gadget_calls = 2^k - 1,
-// k = round(log2(len + 1)) .. 1, the chunk length minimising the ParallelSum(Mul) proof length
-// 2 chunk + 2 ((1 + calls).next_power_of_two() - 1) + 1; the first minimum (largest k) wins.
-uint32_t optimal_chunk_length(uint32_t len) {
-  if (len <= 1) return 1;
-  const int max_log2 = (int)std::lround(std::log2((double)len + 1.0));
-  uint64_t best_cost = ~0ull;
-  uint32_t best = 1;
-  for (int k = max_log2; k >= 1; --k) {
-    const uint64_t calls = (1ull << k) - 1;
-    const uint64_t chunk = (len + calls - 1) / calls;
-    const uint64_t cost = 2 * chunk + 2 * (next_pow2((uint32_t)(1 + calls)) - 1) + 1;
-    if (cost < best_cost) {
-      best_cost = cost;
-      best = (uint32_t)chunk;
-    }
-  }
-  return best;
-}
-
-// FLP tables of one gadget (Montgomery form), 3m + 1 entries:
-//   [0, m)        alpha_m^k
-//   m             1/m
-//   [m+1, 2m+1)   S_i = sum_{k=1..calls} alpha_m^(ik)   (gadget-output sum as a dot product)
-//   [2m+1, 3m+1)  alpha_m^k / m                          (Lagrange weight scale)
-int upload_tables(DevBuf& buf, uint32_t m, uint32_t calls, uint32_t es) {
-  const u128 p = (es == 16) ? P128 : P64;
-  const u128 R = (es == 16) ? (u128)0 - P128 /* 2^128 mod p */ : ((u128)1 << 64) % P64;
-  const u128 alpha = powmod(7, (p - 1) / m, p);
-  const u128 inv_m = p - (p - 1) / m;
-  std::vector<u128> tv(3 * (size_t)m + 1);
-  u128 a = 1;
-  for (uint32_t k = 0; k < m; ++k) {
-    tv[k] = a;
-    tv[2 * m + 1 + k] = mulmod(a, inv_m, p);
-    a = mulmod(a, alpha, p);
-  }
-  tv[m] = inv_m;
-  for (uint32_t i = 0; i < m; ++i) {
-    const u128 x = tv[i];  // alpha^i
-    u128 y = x, acc = 0;
-    for (uint32_t k = 1; k <= calls; ++k) {
-      acc = addmod(acc, y, p);
-      y = mulmod(y, x, p);
-    }
-    tv[m + 1 + i] = acc;
-  }
-  std::vector<uint8_t> tw(tv.size() * es);
-  for (size_t k = 0; k < tv.size(); ++k) {
-    const u128 mv = mulmod(tv[k], R, p);
-    for (uint32_t b = 0; b < es; ++b) tw[k * es + b] = (uint8_t)(mv >> (8 * b));
-  }
-  CHK(buf.ensure(tw.size()));
-  HIPCHK(hipMemcpy(buf.p, tw.data(), tw.size(), hipMemcpyHostToDevice));
+int upload(DevBuf& buf, const std::vector<uint8_t>& bytes) {
+  CHK(buf.ensure(bytes.size()));
+  HIPCHK(hipMemcpy(buf.p, bytes.data(), bytes.size(), hipMemcpyHostToDevice));
   return 0;
 }
 
+// The instance's lengths (plan_cfg.h) and its three FLP tables on the device.
 int setup_cfg(prio3gpu_ctx* c, int kind, uint32_t bits, uint32_t length, uint32_t chunk) {
   Cfg& g = c->cfg;
-  g.kind = (uint32_t)kind;
-  g.wave_prio = 1u;
-  // VDAF-07 algorithm IDs: Count 0, Sum 1, SumVec 2, Histogram 3; FixedPoint L2 0xFFFF0000
-  g.algo_id = kind == PRIO3GPU_FPVEC ? 0xFFFF0000u : (uint32_t)kind;
-  g.qr_len = kind == PRIO3GPU_FPVEC ? 2u : 1u;
-  uint32_t calls = 0, arity = 0, prove_rand = 0;
-  switch (kind) {
-    case PRIO3GPU_COUNT:
-      g.es = 8;
-      g.meas_len = 1;
-      g.out_len = 1;
-      g.jr_len = 0;
-      calls = 1;
-      arity = 2;
-      prove_rand = 2;
-      break;
-    case PRIO3GPU_SUM:
-      if (bits == 0 || bits > 64) {
-        set_err("Prio3Sum: bits must be in 1..64");
-        return PRIO3GPU_E_ARG;
-      }
-      g.es = 16;
-      g.meas_len = bits;
-      g.out_len = 1;
-      g.jr_len = 1;
-      calls = bits;
-      arity = 1;
-      prove_rand = 1;
-      break;
-    case PRIO3GPU_SUMVEC:
-      if (bits == 0 || bits > 64 || length == 0 || chunk == 0) {
-        set_err("Prio3SumVec: bad parameters");
-        return PRIO3GPU_E_ARG;
-      }
-      g.es = 16;
-      g.meas_len = bits * length;
-      g.out_len = length;
-      g.jr_len = 1;
-      calls = (g.meas_len + chunk - 1) / chunk;
-      arity = 2 * chunk;
-      prove_rand = 2 * chunk;
-      break;
-    case PRIO3GPU_HISTOGRAM:
-      if (length == 0 || chunk == 0) {
-        set_err("Prio3Histogram: bad parameters");
-        return PRIO3GPU_E_ARG;
-      }
-      g.es = 16;
-      g.meas_len = length;
-      g.out_len = length;
-      g.jr_len = 2;
-      calls = (length + chunk - 1) / chunk;
-      arity = 2 * chunk;
-      prove_rand = 2 * chunk;
-      break;
-    case PRIO3GPU_FPVEC:
-      if ((bits != 16 && bits != 32 && bits != 64) || length == 0) {
-        set_err("Prio3FixedPointBoundedL2VecSum: bits must be 16, 32 or 64 and length >= 1");
-        return PRIO3GPU_E_ARG;
-      }
-      g.es = 16;
-      g.meas_len = bits * length + 2 * bits - 2;  // entry bits || norm bits
-      g.out_len = length;
-      g.jr_len = 2;
-      chunk = optimal_chunk_length(g.meas_len);
-      calls = (g.meas_len + chunk - 1) / chunk;
-      arity = 2 * chunk;
-      g.chunk1 = optimal_chunk_length(length);
-      g.calls1 = (length + g.chunk1 - 1) / g.chunk1;
-      prove_rand = 2 * chunk + g.chunk1;
-      break;
-    default:
-      set_err("unknown kind %d", kind);
-      return PRIO3GPU_E_ARG;
+  std::string err;
+  if (const int rc = derive_cfg(kind, bits, length, chunk, &g, &err)) {
+    set_err("%s", err.c_str());
+    return rc;
   }
-  g.bits = bits;
-  g.length = length;
-  g.chunk =
-      (kind == PRIO3GPU_SUMVEC || kind == PRIO3GPU_HISTOGRAM || kind == PRIO3GPU_FPVEC) ? chunk : 0;
-  g.calls = calls;
-  g.arity = arity;
-  g.prove_rand_len = prove_rand;
-  g.m = next_pow2(1 + calls);
-  g.logm = ilog2(g.m);
-  if (g.m > 4096) {
-    set_err("gadget too large (m = %u)", g.m);
-    return PRIO3GPU_E_ARG;
-  }
-  g.gp_len = 2 * (g.m - 1) + 1;  // every gadget here has degree 2
-  g.proof_len = arity + g.gp_len;
-  g.verifier_len = 1 + arity + 1;
-  if (kind == PRIO3GPU_FPVEC) {
-    g.m1 = next_pow2(1 + g.calls1);
-    g.logm1 = ilog2(g.m1);
-    g.gp_len1 = 2 * (g.m1 - 1) + 1;
-    g.proof_len += g.chunk1 + g.gp_len1;
-    g.verifier_len += g.chunk1 + 1;
-    // k_fpv_weights keeps three m-entry tables and an r-power table in LDS
-    if (g.m > 2048 || g.chunk + 1 > 4096 ||
-        (size_t)16 * (3 * (size_t)g.m + g.chunk + 1 + 12) + 16 > 160 * 1024) {
-      set_err("FixedPointBoundedL2VecSum: length %u too large (m = %u, chunk = %u)", length, g.m,
-              g.chunk);
-      return PRIO3GPU_E_ARG;
-    }
-  }
-  const uint32_t es = g.es;
-  g.leader_share_len = es * (g.meas_len + g.proof_len) + (g.jr_len ? 16 : 0);
-  g.helper_share_len = g.jr_len ? 48 : 32;
-  g.public_share_len = g.jr_len ? 32 : 0;
-  g.prep_share_len = es * g.verifier_len + (g.jr_len ? 16 : 0);
-  g.prep_msg_len = g.jr_len ? 16 : 0;
-
-  prio3gpu_sizes& s = c->sz;
-  s.field_size = es;
-  s.meas_len = g.meas_len;
-  s.proof_len = g.proof_len;
-  s.verifier_len = g.verifier_len;
-  s.joint_rand_len = g.jr_len;
-  s.output_len = g.out_len;
-  s.leader_input_share = g.leader_share_len;
-  s.helper_input_share = g.helper_share_len;
-  s.public_share = g.public_share_len;
-  s.prep_share = g.prep_share_len;
-  s.prep_msg = g.prep_msg_len;
-  s.aggregate_share = g.out_len * es;
-
-  CHK(upload_tables(c->twiddles, g.m, g.calls, es));
+  c->sz = cfg_sizes(g);
+  CHK(upload(c->twiddles, gadget_table(g.m, g.calls, g.es)));
   g.twiddles = c->twiddles.u8();
-  g.twiddles1 = nullptr;
   if (kind == PRIO3GPU_FPVEC) {
-    CHK(upload_tables(c->twiddles1, g.m1, g.calls1, es));
+    CHK(upload(c->twiddles1, gadget_table(g.m1, g.calls1, g.es)));
     g.twiddles1 = c->twiddles1.u8();
   }
-  // prover table: w^k (k < 2m, w = primitive 2m-th root), 1/m, 1/(2m); Montgomery
-  {
-    const u128 p = (es == 16) ? P128 : P64;
-    const u128 R = (es == 16) ? (u128)0 - P128 /* 2^128 mod p */ : ((u128)1 << 64) % P64;
-    const uint32_t m2 = 2 * g.m;
-    const u128 w = powmod(7, (p - 1) / m2, p);
-    std::vector<uint8_t> t2((size_t)(m2 + 2) * es);
-    u128 x = 1;
-    for (uint32_t k = 0; k < m2 + 2; ++k) {
-      u128 v = k < m2 ? x : (k == m2 ? p - (p - 1) / g.m : p - (p - 1) / m2);
-      u128 mv = mulmod(v, R, p);
-      for (uint32_t b = 0; b < es; ++b) t2[(size_t)k * es + b] = (uint8_t)(mv >> (8 * b));
-      x = mulmod(x, w, p);
-    }
-    CHK(c->twiddles2.ensure(t2.size()));
-    HIPCHK(hipMemcpy(c->twiddles2.p, t2.data(), t2.size(), hipMemcpyHostToDevice));
-  }
-  return 0;
+  return upload(c->twiddles2, prover_table(g.m, g.es));
 }
 
 // Make `src` (host or device, `bytes`) available on device; returns the device pointer.
-int stage_in(prio3gpu_ctx* c, DevBuf& buf, const void* src, size_t bytes, const uint8_t** out) {
-  if (!src || bytes == 0) {
+// A null or empty source is passed through, unless `min_bytes` asks for a staging buffer of at
+// least that size in its place (the HPKE kernels take non-null pointers).
+int stage_in(prio3gpu_ctx* c, DevBuf& buf, const void* src, size_t bytes, const uint8_t** out,
+             size_t min_bytes = 0) {
+  if ((min_bytes == 0 && (!src || bytes == 0)) || (src && is_device_ptr(src))) {
     *out = static_cast<const uint8_t*>(src);
     return 0;
   }
-  if (is_device_ptr(src)) {
-    *out = static_cast<const uint8_t*>(src);
-    return 0;
-  }
-  CHK(buf.ensure(bytes));
-  HIPCHK(hipMemcpyAsync(buf.p, src, bytes, hipMemcpyHostToDevice, c->stream));
+  CHK(buf.ensure(std::max(bytes, min_bytes)));
+  if (bytes) HIPCHK(hipMemcpyAsync(buf.p, src, bytes, hipMemcpyHostToDevice, c->stream));
   *out = buf.u8();
   return 0;
 }
@@ -591,23 +365,6 @@ bool spread_ok(const prio3gpu_ctx* c, uint32_t blocks) { return c->spread && blo
 uint32_t chain_pairs(const prio3gpu_ctx* c, size_t n) {
   if (c->chain_pairs) return c->chain_pairs;
   return (n + 63) / 64 > std::max<uint32_t>(1u, c->cus / 2) ? 2u : 1u;
-}
-
-// Measurement-share words that k_jr absorbs through its LDS window ("fast" blocks 1..lf cover
-// words [16, 21 (lf+1) - 5)); elements [e0, e1) lie entirely inside.  Field128 types with JR only.
-bool spec_range(const Cfg& g, uint32_t& nd, uint32_t& e0, uint32_t& e1) {
-  if (g.es != 16 || g.jr_len == 0) return false;
-  const int64_t nbytes = (int64_t)g.meas_len * 16;
-  const int64_t ndw = nbytes / 8, padw = (42 + nbytes) >> 3;
-  auto is_fast = [&](int64_t b) { return b >= 1 && 21 * b + 15 < ndw && 21 * b + 20 < padw; };
-  int64_t lf = 0;
-  while (is_fast(lf + 1)) ++lf;
-  if (lf < 1) return false;
-  const int64_t f1 = (21 * (lf + 1) - 5) & ~(int64_t)1;
-  nd = (uint32_t)ndw;
-  e0 = 8;
-  e1 = (uint32_t)(f1 / 2);
-  return e1 > e0;
 }
 
 // Snapshot mode: the helper's expanded measurement shares of reports [r0, r0 + nr) rewritten
@@ -767,6 +524,15 @@ size_t input_pitch(const prio3gpu_state* st) {
   return st->in_pitch ? st->in_pitch : (st->agg_id == 0 ? g.leader_share_len : g.helper_share_len);
 }
 
+// The XOF phase over n reports has been queued: where it left the shares; the query phase is due.
+void xof_phase_done(prio3gpu_state* st, size_t n, CRows meas, CRows proof) {
+  st->meas_rows = meas;
+  st->proof_rows = proof;
+  st->n = n;
+  st->xof_done = true;
+  st->weights_done = false;
+}
+
 // prepare_init, first phase: query randomness, (helper) share expansion, joint randomness.
 template <class FO>
 int launch_prep_xof(prio3gpu_ctx* c, prio3gpu_state* st, size_t n, const uint8_t* d_nonces,
@@ -806,11 +572,7 @@ int launch_prep_xof(prio3gpu_ctx* c, prio3gpu_state* st, size_t n, const uint8_t
                          d_nonces, vk_lo, vk_hi);
     }
     HIPCHK(hipGetLastError());
-    st->meas_rows = meas;
-    st->proof_rows = proof;
-    st->n = n;
-    st->xof_done = true;
-    st->weights_done = false;
+    xof_phase_done(st, n, meas, proof);
     st->query_done = true;
     return 0;
   }
@@ -889,11 +651,7 @@ int launch_prep_xof(prio3gpu_ctx* c, prio3gpu_state* st, size_t n, const uint8_t
         st->spec_e0 = 0;
         st->spec_e1 = g.meas_len;
       }
-      st->meas_rows = CRows{mo.base, mo.stride};
-      st->proof_rows = CRows{po.base, po.stride};
-      st->n = n;
-      st->xof_done = true;
-      st->weights_done = false;
+      xof_phase_done(st, n, CRows{mo.base, mo.stride}, CRows{po.base, po.stride});
       return 0;
     }
     st->snap_active = false;
@@ -956,11 +714,7 @@ int launch_prep_xof(prio3gpu_ctx* c, prio3gpu_state* st, size_t n, const uint8_t
     }
   }
   HIPCHK(hipGetLastError());
-  st->meas_rows = meas;
-  st->proof_rows = proof;
-  st->n = n;
-  st->xof_done = true;
-  st->weights_done = false;
+  xof_phase_done(st, n, meas, proof);
   return 0;
 }
 
@@ -1123,138 +877,72 @@ int launch_decide(prio3gpu_ctx* c, size_t n, const uint8_t* d_l, const uint8_t* 
   return 0;
 }
 
-// Segmented accumulation of the batch's output shares into agg slots.
+// Segmented accumulation of the batch's output shares into agg slots: the chunk plan
+// (plan_accum.h) on the device, then the partial sums of every chunk and their merge per slot.
 template <class FO>
 int launch_accumulate(prio3gpu_ctx* c, prio3gpu_state* st, size_t n, const uint32_t* slots,
                       const uint8_t* d_status, prio3gpu_agg* agg) {
   const Cfg& g = c->cfg;
-  const uint32_t S = agg->slots;
-  const bool spec = st->spec_ok && st->spec_n == n && FO::ES == 16;
-  const uint32_t epb = std::min<uint32_t>(256, std::max<uint32_t>(1, g.meas_len));
-  const uint32_t tiles = (g.meas_len + epb - 1) / epb;
+  AccumKey key;
+  key.n = n;
+  key.slots = agg->slots;
+  key.spec = st->spec_ok && st->spec_n == n && FO::ES == 16;
+  if (key.spec) {
+    key.nd = st->spec_nd;
+    key.e0 = st->spec_e0;
+    key.e1 = st->spec_e1;
+  }
+  const uint32_t epb = accum_epb(g.meas_len), tiles = accum_tiles(g.meas_len);
+  AccumPlan& p = c->plan;
   // One batch slot and the same batch shape as the last call: the plan on the device still holds
   // (no host planning, no upload, no stream synchronisation).
-  const bool reuse = !slots && c->plan_valid && c->plan_n == n && c->plan_slots == S &&
-                     c->plan_spec == spec &&
-                     (!spec || (c->plan_nd == st->spec_nd && c->plan_e0 == st->spec_e0 &&
-                                c->plan_e1 == st->spec_e1));
-  if (!reuse) {
+  if (slots || !c->plan_valid || !(c->plan_key == key)) {
     c->plan_valid = false;
     std::vector<uint32_t> hslots;
-    const uint32_t* sl = slots;
     if (slots && is_device_ptr(slots)) {
       hslots.resize(n);
       HIPCHK(hipMemcpyAsync(hslots.data(), slots, n * 4, hipMemcpyDeviceToHost, c->stream));
       HIPCHK(hipStreamSynchronize(c->stream));
-      sl = hslots.data();
+      slots = hslots.data();
     }
-    for (size_t r = 0; r < n; ++r) {
-      const uint32_t s = sl ? sl[r] : 0;
-      if (s >= S) {
-        set_err("batch slot %u out of range (%u slots)", s, S);
-        return PRIO3GPU_E_ARG;
-      }
+    std::string err;
+    if (const int rc = plan_accumulate(n, slots, key.slots, g.meas_len, key.spec, &p, &err)) {
+      set_err("%s", err.c_str());
+      return rc;
     }
-    auto slot_of = [&](size_t r) -> uint32_t { return sl ? sl[r] : 0u; };
-    // Chunks (runs of reports of one slot, contiguous per slot in chunk order) of two kinds:
-    //  * direct: k_accum_partial sums every measurement element of the chunk's reports;
-    //  * speculative (whole waves of 64 reports whose slots agree, when k_jr left column sums):
-    //    k_accum_spec folds the per-wave sums of elements [e0, e1) and corrects the rejected
-    //    rows, k_accum_partial adds the few edge elements outside that range.
-    const size_t nw = (n + 63) / 64;
-    std::vector<std::vector<uint32_t>> spec_w(S), direct_r(S);
-    if (spec) {
-      for (size_t w = 0; w < nw; ++w) {
-        const size_t r0 = 64 * w, r1 = std::min(n, r0 + 64);
-        const uint32_t s = slot_of(r0);
-        bool uni = true;
-        for (size_t r = r0 + 1; r < r1 && uni; ++r) uni = slot_of(r) == s;
-        if (uni) {
-          spec_w[s].push_back((uint32_t)w);
-        } else {
-          for (size_t r = r0; r < r1; ++r) direct_r[slot_of(r)].push_back((uint32_t)r);
-        }
-      }
-    } else {
-      for (size_t r = 0; r < n; ++r) direct_r[slot_of(r)].push_back((uint32_t)r);
+    if (p.nch == 0) return 0;
+    const AccumLayout l = accum_layout(p);
+    CHK(c->perm.ensure(std::max<size_t>(1, p.perm.size()) * 4));
+    CHK(c->chunks.ensure(l.chunks_len * 4));
+    CHK(c->partials.ensure((size_t)p.nch * g.meas_len * g.es));
+    CHK(c->pcounts.ensure((size_t)p.nch * 4));
+    CHK(c->spec_idx.ensure(l.spec_idx_len * 4));
+    auto put = [&](DevBuf& buf, size_t at, const std::vector<uint32_t>& v) -> int {
+      HIPCHK(hipMemcpyAsync(static_cast<uint32_t*>(buf.p) + at, v.data(), v.size() * 4,
+                            hipMemcpyHostToDevice, c->stream));
+      return 0;
+    };
+    CHK(put(c->perm, 0, p.perm));
+    CHK(put(c->chunks, l.chunk_begin, p.chunk_begin));
+    CHK(put(c->chunks, l.chunk_slot, p.chunk_slot));
+    if (p.ndir) CHK(put(c->spec_idx, l.dir_ids, p.dir_ids));
+    if (p.nspec) {
+      CHK(put(c->spec_idx, l.spec_ids, p.spec_ids));
+      CHK(put(c->spec_idx, l.spec_wave_begin, p.spec_wave_begin));
+      CHK(put(c->spec_idx, l.wave_list, p.wave_list));
     }
-    const uint32_t G = 256 / epb;
-    const size_t target_chunks = std::max<size_t>(1, 2048 / tiles);
-    const size_t CH = std::max<size_t>((size_t)G * 4, (n + target_chunks - 1) / target_chunks);
-    const size_t WCH = 32;  // waves per speculative chunk
-    auto& perm = c->h_perm;
-    auto& cb = c->h_chunk_begin;
-    auto& cs = c->h_chunk_slot;
-    perm.clear();
-    cb.clear();
-    cs.clear();
-    std::vector<uint32_t> dir_ids, spec_ids, swb, wl;
-    for (uint32_t s = 0; s < S; ++s) {
-      const auto& sw = spec_w[s];
-      for (size_t i = 0; i < sw.size(); i += WCH) {
-        spec_ids.push_back((uint32_t)cs.size());
-        cb.push_back((uint32_t)perm.size());
-        cs.push_back(s);
-        swb.push_back((uint32_t)wl.size());
-        for (size_t q = i; q < std::min(sw.size(), i + WCH); ++q) {
-          wl.push_back(sw[q]);
-          for (size_t r = 64 * (size_t)sw[q]; r < std::min(n, 64 * (size_t)sw[q] + 64); ++r)
-            perm.push_back((uint32_t)r);
-        }
-      }
-      const auto& dr = direct_r[s];
-      for (size_t i = 0; i < dr.size(); i += CH) {
-        dir_ids.push_back((uint32_t)cs.size());
-        cb.push_back((uint32_t)perm.size());
-        cs.push_back(s);
-        perm.insert(perm.end(), dr.begin() + i, dr.begin() + std::min(dr.size(), i + CH));
-      }
-    }
-    const uint32_t nch = (uint32_t)cs.size();
-    if (nch == 0) return 0;
-    cb.push_back((uint32_t)perm.size());
-    swb.push_back((uint32_t)wl.size());
-    const uint32_t ndir = (uint32_t)dir_ids.size(), nspec = (uint32_t)spec_ids.size();
-    CHK(c->perm.ensure(std::max<size_t>(1, perm.size()) * 4));
-    CHK(c->chunks.ensure((size_t)(2 * nch + 1) * 4));
-    CHK(c->partials.ensure((size_t)nch * g.meas_len * g.es));
-    CHK(c->pcounts.ensure((size_t)nch * 4));
-    CHK(c->spec_idx.ensure((size_t)(ndir + 2 * nspec + 1 + wl.size() + 1) * 4));
-    HIPCHK(hipMemcpyAsync(c->perm.p, perm.data(), perm.size() * 4, hipMemcpyHostToDevice, c->stream));
-    uint32_t* d_cb = reinterpret_cast<uint32_t*>(c->chunks.p);
-    uint32_t* d_cs = d_cb + nch + 1;
-    HIPCHK(hipMemcpyAsync(d_cb, cb.data(), (nch + 1) * 4, hipMemcpyHostToDevice, c->stream));
-    HIPCHK(hipMemcpyAsync(d_cs, cs.data(), nch * 4, hipMemcpyHostToDevice, c->stream));
-    uint32_t* d_dir = reinterpret_cast<uint32_t*>(c->spec_idx.p);
-    uint32_t* d_sid = d_dir + ndir;
-    uint32_t* d_swb = d_sid + nspec;
-    uint32_t* d_wl = d_swb + nspec + 1;
-    if (ndir) HIPCHK(hipMemcpyAsync(d_dir, dir_ids.data(), ndir * 4, hipMemcpyHostToDevice, c->stream));
-    if (nspec) {
-      HIPCHK(hipMemcpyAsync(d_sid, spec_ids.data(), nspec * 4, hipMemcpyHostToDevice, c->stream));
-      HIPCHK(hipMemcpyAsync(d_swb, swb.data(), (nspec + 1) * 4, hipMemcpyHostToDevice, c->stream));
-      HIPCHK(hipMemcpyAsync(d_wl, wl.data(), wl.size() * 4, hipMemcpyHostToDevice, c->stream));
-    }
-    // the host vectors must outlive the async copies (and a later re-plan rewrites them)
+    // the plan's host vectors are rewritten by the next re-plan: the copies must have read them
     HIPCHK(hipStreamSynchronize(c->stream));
-    c->plan_ndir = ndir;
-    c->plan_nspec = nspec;
-    c->plan_nch = nch;
+    c->plan_key = key;
     c->plan_valid = !slots;
-    c->plan_n = n;
-    c->plan_slots = S;
-    c->plan_spec = spec;
-    c->plan_nd = st->spec_nd;
-    c->plan_e0 = st->spec_e0;
-    c->plan_e1 = st->spec_e1;
   }
-  const uint32_t ndir = c->plan_ndir, nspec = c->plan_nspec, nch = c->plan_nch;
-  const uint32_t* d_cb = reinterpret_cast<const uint32_t*>(c->chunks.p);
-  const uint32_t* d_cs = d_cb + nch + 1;
-  const uint32_t* d_dir = reinterpret_cast<const uint32_t*>(c->spec_idx.p);
-  const uint32_t* d_sid = d_dir + ndir;
-  const uint32_t* d_swb = d_sid + nspec;
-  const uint32_t* d_wl = d_swb + nspec + 1;
+  const uint32_t ndir = p.ndir, nspec = p.nspec, nch = p.nch;
+  const AccumLayout l = accum_layout(p);
+  const uint32_t* d_chunks = reinterpret_cast<const uint32_t*>(c->chunks.p);
+  const uint32_t* d_idx = reinterpret_cast<const uint32_t*>(c->spec_idx.p);
+  const uint32_t *d_cb = d_chunks + l.chunk_begin, *d_cs = d_chunks + l.chunk_slot;
+  const uint32_t *d_dir = d_idx + l.dir_ids, *d_sid = d_idx + l.spec_ids;
+  const uint32_t *d_swb = d_idx + l.spec_wave_begin, *d_wl = d_idx + l.wave_list;
   const uint32_t* d_perm = reinterpret_cast<const uint32_t*>(c->perm.p);
   uint32_t* d_pc = reinterpret_cast<uint32_t*>(c->pcounts.p);
   const size_t red_lds = 256 * sizeof(typename FO::T) + 16;
@@ -1366,8 +1054,11 @@ int out_shares_batch(prio3gpu_ctx* c, prio3gpu_state* st, size_t n, const uint8_
   return rc;
 }
 
-bool is_f64(const prio3gpu_ctx* c) { return c->cfg.es == 8; }
-
+// f(Field64Ops{}) or f(Field128Ops{}): the field of the context's VDAF, as a type.
+template <class F>
+auto with_field(const prio3gpu_ctx* c, F&& f) {
+  return c->cfg.es == 8 ? f(Field64Ops{}) : f(Field128Ops{});
+}
 
 int check_state(prio3gpu_ctx* c, prio3gpu_state* st, size_t n) {
   if (!c || !st || st->ctx != c) {
@@ -1395,6 +1086,29 @@ int stage_status(prio3gpu_ctx* c, DevBuf& buf, uint8_t* status, size_t n, uint8_
   HIPCHK(hipMemcpyAsync(buf.p, status, n, hipMemcpyHostToDevice, c->stream));
   *d_status = buf.u8();
   return 0;
+}
+
+// The inputs of prepare_init / prepare_init_xof / helper_init on the device: null checks, the
+// context's device made current, host pointers staged into the state (the input shares at the
+// state's pitch).
+struct PrepInputs {
+  const uint8_t *nonces, *pub, *in;
+  uint8_t* status;
+};
+int stage_prepare_inputs(prio3gpu_ctx* c, prio3gpu_state* st, size_t n, const uint8_t* nonces,
+                         const uint8_t* public_shares, const uint8_t* input_shares,
+                         uint8_t* status, PrepInputs* d) {
+  const Cfg& g = c->cfg;
+  if (!nonces || !input_shares || (g.jr_len && !public_shares)) {
+    set_err("null input");
+    return PRIO3GPU_E_ARG;
+  }
+  HIPCHK(hipSetDevice(c->device));
+  CHK(stage_in(c, st->nonces, nonces, n * 16, &d->nonces));
+  CHK(stage_in(c, st->pub, public_shares, n * g.public_share_len, &d->pub));
+  const size_t in_len = st->agg_id == 0 ? g.leader_share_len : g.helper_share_len;
+  CHK(stage_in(c, st->input, input_shares, (n - 1) * input_pitch(st) + in_len, &d->in));
+  return stage_status(c, st->status, status, n, &d->status);
 }
 
 // End of an ABI call: wait for the context's stream unless the context is in async mode and every
@@ -1617,11 +1331,7 @@ int prio3gpu_state_set_input_pitch(prio3gpu_state* st, size_t pitch) {
 int prio3gpu_state_destroy(prio3gpu_state* st) {
   if (!st) return 0;
   if (st->ctx) (void)hipStreamSynchronize(st->ctx->stream);
-  for (DevBuf* b : {&st->t, &st->jr, &st->part, &st->seed, &st->meas, &st->proof, &st->prep,
-                    &st->msg, &st->status, &st->nonces, &st->pub, &st->input, &st->w,
-                    &st->spec_lo, &st->spec_cy})
-    b->release();
-  delete st;
+  delete st;  // the DevBuf destructors free the buffers
   return 0;
 }
 
@@ -1801,16 +1511,13 @@ int prio3gpu_agg_merge_bytes(prio3gpu_agg* a, uint32_t slot, const uint8_t* shar
   const uint8_t* d_src;
   CHK(stage_in(c, c->io[0], share, bytes, &d_src));
   uint8_t* dst = a->share.u8() + slot * bytes;
-  if (is_f64(c))
-    {
-      PROF(KID_MERGE);
-      hipLaunchKernelGGL(k_merge<Field64Ops>, grid1(nel, 256), dim3(256), 0, c->stream, dst, d_src, nel);
-    }
-  else
-    {
-      PROF(KID_MERGE);
-      hipLaunchKernelGGL(k_merge<Field128Ops>, grid1(nel, 256), dim3(256), 0, c->stream, dst, d_src, nel);
-    }
+  {
+    PROF(KID_MERGE);
+    with_field(c, [&](auto fo) {
+      hipLaunchKernelGGL(k_merge<decltype(fo)>, grid1(nel, 256), dim3(256), 0, c->stream, dst,
+                         d_src, nel);
+    });
+  }
   HIPCHK(hipGetLastError());
   uint64_t cur = 0;
   HIPCHK(hipMemcpyAsync(&cur, a->counts.u8() + (size_t)slot * 8, 8, hipMemcpyDeviceToHost, c->stream));
@@ -1826,25 +1533,13 @@ int prio3gpu_prepare_init(prio3gpu_ctx* c, prio3gpu_state* st, size_t n, const u
                           uint8_t* out_prep_shares, uint8_t* status) {
   CHK(check_state(c, st, n));
   if (n == 0) return 0;
-  if (!nonces || !input_shares || (c->cfg.jr_len && !public_shares)) {
-    set_err("null input");
-    return PRIO3GPU_E_ARG;
-  }
-  HIPCHK(hipSetDevice(c->device));
-  const Cfg& g = c->cfg;
-  const uint8_t *d_nonces, *d_pub, *d_in;
-  CHK(stage_in(c, st->nonces, nonces, n * 16, &d_nonces));
-  CHK(stage_in(c, st->pub, public_shares, n * g.public_share_len, &d_pub));
-  const size_t in_len = st->agg_id == 0 ? g.leader_share_len : g.helper_share_len;
-  CHK(stage_in(c, st->input, input_shares, (n - 1) * input_pitch(st) + in_len, &d_in));
-  uint8_t* d_status;
-  CHK(stage_status(c, st->status, status, n, &d_status));
-  if (is_f64(c))
-    CHK(launch_prepare_init<Field64Ops>(c, st, n, d_nonces, d_pub, d_in, d_status));
-  else
-    CHK(launch_prepare_init<Field128Ops>(c, st, n, d_nonces, d_pub, d_in, d_status));
-  CHK(copy_out(c, out_prep_shares, st->prep.p, n * g.prep_share_len));
-  CHK(copy_out(c, status, d_status, n));
+  PrepInputs d;
+  CHK(stage_prepare_inputs(c, st, n, nonces, public_shares, input_shares, status, &d));
+  CHK(with_field(c, [&](auto fo) {
+    return launch_prepare_init<decltype(fo)>(c, st, n, d.nonces, d.pub, d.in, d.status);
+  }));
+  CHK(copy_out(c, out_prep_shares, st->prep.p, n * c->cfg.prep_share_len));
+  CHK(copy_out(c, status, d.status, n));
   return finish_call(c, {nonces, public_shares, input_shares, out_prep_shares, status});
 }
 
@@ -1853,24 +1548,12 @@ int prio3gpu_prepare_init_xof(prio3gpu_ctx* c, prio3gpu_state* st, size_t n, con
                               uint8_t* status) {
   CHK(check_state(c, st, n));
   if (n == 0) return 0;
-  if (!nonces || !input_shares || (c->cfg.jr_len && !public_shares)) {
-    set_err("null input");
-    return PRIO3GPU_E_ARG;
-  }
-  HIPCHK(hipSetDevice(c->device));
-  const Cfg& g = c->cfg;
-  const uint8_t *d_nonces, *d_pub, *d_in;
-  CHK(stage_in(c, st->nonces, nonces, n * 16, &d_nonces));
-  CHK(stage_in(c, st->pub, public_shares, n * g.public_share_len, &d_pub));
-  const size_t in_len = st->agg_id == 0 ? g.leader_share_len : g.helper_share_len;
-  CHK(stage_in(c, st->input, input_shares, (n - 1) * input_pitch(st) + in_len, &d_in));
-  uint8_t* d_status;
-  CHK(stage_status(c, st->status, status, n, &d_status));
-  if (is_f64(c))
-    CHK(launch_prep_xof<Field64Ops>(c, st, n, d_nonces, d_pub, d_in, d_status));
-  else
-    CHK(launch_prep_xof<Field128Ops>(c, st, n, d_nonces, d_pub, d_in, d_status));
-  CHK(copy_out(c, status, d_status, n));
+  PrepInputs d;
+  CHK(stage_prepare_inputs(c, st, n, nonces, public_shares, input_shares, status, &d));
+  CHK(with_field(c, [&](auto fo) {
+    return launch_prep_xof<decltype(fo)>(c, st, n, d.nonces, d.pub, d.in, d.status);
+  }));
+  CHK(copy_out(c, status, d.status, n));
   return finish_call(c, {nonces, public_shares, input_shares, status});
 }
 
@@ -1881,10 +1564,7 @@ int prio3gpu_prepare_init_query(prio3gpu_ctx* c, prio3gpu_state* st, size_t n,
   HIPCHK(hipSetDevice(c->device));
   uint8_t* d_status;
   CHK(stage_status(c, st->status, status, n, &d_status));
-  if (is_f64(c))
-    CHK(launch_prep_query<Field64Ops>(c, st, n, d_status));
-  else
-    CHK(launch_prep_query<Field128Ops>(c, st, n, d_status));
+  CHK(with_field(c, [&](auto fo) { return launch_prep_query<decltype(fo)>(c, st, n, d_status); }));
   CHK(copy_out(c, out_prep_shares, st->prep.p, n * c->cfg.prep_share_len));
   CHK(copy_out(c, status, d_status, n));
   return finish_call(c, {out_prep_shares, status});
@@ -1896,10 +1576,8 @@ int prio3gpu_prepare_init_weights(prio3gpu_ctx* c, prio3gpu_state* st, size_t n,
   HIPCHK(hipSetDevice(c->device));
   uint8_t* d_status;
   CHK(stage_status(c, st->status, status, n, &d_status));
-  if (is_f64(c))
-    CHK(launch_prep_query<Field64Ops>(c, st, n, d_status, true));
-  else
-    CHK(launch_prep_query<Field128Ops>(c, st, n, d_status, true));
+  CHK(with_field(
+      c, [&](auto fo) { return launch_prep_query<decltype(fo)>(c, st, n, d_status, true); }));
   CHK(copy_out(c, status, d_status, n));
   return finish_call(c, {status});
 }
@@ -2064,10 +1742,8 @@ int prio3gpu_prepare_shares_to_prepare_message(prio3gpu_ctx* c, size_t n,
     CHK(c->io[3].ensure(n * 16));
     d_msg = c->io[3].u8();
   }
-  if (is_f64(c))
-    CHK(launch_decide<Field64Ops>(c, n, d_l, d_h, d_msg, d_status));
-  else
-    CHK(launch_decide<Field128Ops>(c, n, d_l, d_h, d_msg, d_status));
+  CHK(with_field(
+      c, [&](auto fo) { return launch_decide<decltype(fo)>(c, n, d_l, d_h, d_msg, d_status); }));
   CHK(copy_out(c, out_prep_msgs, d_msg, n * g.prep_msg_len));
   CHK(copy_out(c, status, d_status, n));
   return finish_call(c, {leader_prep_shares, helper_prep_shares, out_prep_msgs, status});
@@ -2113,18 +1789,14 @@ int prio3gpu_prepare_next(prio3gpu_ctx* c, prio3gpu_state* st, size_t n, const u
       CHK(c->io[5].ensure(bytes));
       d_out = c->io[5].u8();
     }
-    if (is_f64(c))
-      CHK(out_shares_batch<Field64Ops>(c, st, n, d_status, d_out));
-    else
-      CHK(out_shares_batch<Field128Ops>(c, st, n, d_status, d_out));
+    CHK(with_field(
+        c, [&](auto fo) { return out_shares_batch<decltype(fo)>(c, st, n, d_status, d_out); }));
     CHK(copy_out(c, out_output_shares, d_out, bytes));
   }
-  if (agg) {
-    if (is_f64(c))
-      CHK(accumulate_batch<Field64Ops>(c, st, n, batch_slots, d_status, agg));
-    else
-      CHK(accumulate_batch<Field128Ops>(c, st, n, batch_slots, d_status, agg));
-  }
+  if (agg)
+    CHK(with_field(c, [&](auto fo) {
+      return accumulate_batch<decltype(fo)>(c, st, n, batch_slots, d_status, agg);
+    }));
   CHK(copy_out(c, status, d_status, n));
   return finish_call(c, {prep_msgs, status, out_output_shares, batch_slots});
 }
@@ -2139,30 +1811,22 @@ int prio3gpu_helper_init(prio3gpu_ctx* c, prio3gpu_state* st, size_t n, const ui
     return PRIO3GPU_E_ARG;
   }
   if (n == 0) return 0;
-  if (!nonces || !helper_input_shares || !leader_prep_shares || (c->cfg.jr_len && !public_shares)) {
+  if (!leader_prep_shares) {
     set_err("null input");
     return PRIO3GPU_E_ARG;
   }
-  HIPCHK(hipSetDevice(c->device));
   const Cfg& g = c->cfg;
-  const uint8_t *d_nonces, *d_pub, *d_in, *d_lps;
-  CHK(stage_in(c, st->nonces, nonces, n * 16, &d_nonces));
-  CHK(stage_in(c, st->pub, public_shares, n * g.public_share_len, &d_pub));
-  CHK(stage_in(c, st->input, helper_input_shares, (n - 1) * input_pitch(st) + g.helper_share_len,
-               &d_in));
+  PrepInputs d;
+  CHK(stage_prepare_inputs(c, st, n, nonces, public_shares, helper_input_shares, status, &d));
+  uint8_t* const d_status = d.status;
+  const uint8_t* d_lps;
   CHK(stage_in(c, c->io[0], leader_prep_shares, n * g.prep_share_len, &d_lps));
-  uint8_t* d_status;
-  CHK(stage_status(c, st->status, status, n, &d_status));
-  const bool f64 = is_f64(c);
-  if (f64)
-    CHK(launch_prepare_init<Field64Ops>(c, st, n, d_nonces, d_pub, d_in, d_status));
-  else
-    CHK(launch_prepare_init<Field128Ops>(c, st, n, d_nonces, d_pub, d_in, d_status));
   uint8_t* d_msg = st->msg.u8();
-  if (f64)
-    CHK(launch_decide<Field64Ops>(c, n, d_lps, st->prep.u8(), d_msg, d_status));
-  else
-    CHK(launch_decide<Field128Ops>(c, n, d_lps, st->prep.u8(), d_msg, d_status));
+  CHK(with_field(c, [&](auto fo) {
+    using FO = decltype(fo);
+    CHK(launch_prepare_init<FO>(c, st, n, d.nonces, d.pub, d.in, d_status));
+    return launch_decide<FO>(c, n, d_lps, st->prep.u8(), d_msg, d_status);
+  }));
   if (g.jr_len) {
     {
       PROF(KID_PNEXT);
@@ -2171,12 +1835,10 @@ int prio3gpu_helper_init(prio3gpu_ctx* c, prio3gpu_state* st, size_t n, const ui
     }
     HIPCHK(hipGetLastError());
   }
-  if (agg) {
-    if (f64)
-      CHK(accumulate_batch<Field64Ops>(c, st, n, batch_slots, d_status, agg));
-    else
-      CHK(accumulate_batch<Field128Ops>(c, st, n, batch_slots, d_status, agg));
-  }
+  if (agg)
+    CHK(with_field(c, [&](auto fo) {
+      return accumulate_batch<decltype(fo)>(c, st, n, batch_slots, d_status, agg);
+    }));
   CHK(copy_out(c, out_prep_msgs, d_msg, n * g.prep_msg_len));
   CHK(copy_out(c, status, d_status, n));
   return finish_call(c, {nonces, public_shares, helper_input_shares, leader_prep_shares,
@@ -2303,14 +1965,10 @@ int prio3gpu_shard(prio3gpu_ctx* c, prio3gpu_state* st, size_t n, const uint8_t*
       d_out[i] = c->io[i].u8();
     }
   }
-  int rc;
-  if (is_f64(c))
-    rc = launch_shard<Field64Ops>(c, st, n, d_nonces, reinterpret_cast<const uint64_t*>(d_meas),
-                                  mw, d_rand, d_out[0], d_out[1], d_out[2]);
-  else
-    rc = launch_shard<Field128Ops>(c, st, n, d_nonces, reinterpret_cast<const uint64_t*>(d_meas),
-                                   mw, d_rand, d_out[0], d_out[1], d_out[2]);
-  if (rc) return rc;
+  CHK(with_field(c, [&](auto fo) {
+    return launch_shard<decltype(fo)>(c, st, n, d_nonces, reinterpret_cast<const uint64_t*>(d_meas),
+                                      mw, d_rand, d_out[0], d_out[1], d_out[2]);
+  }));
   for (int i = 0; i < 3; ++i)
     if (d_out[i] && d_out[i] != host_out[i]) CHK(copy_out(c, host_out[i], d_out[i], out_len[i]));
   HIPCHK(hipStreamSynchronize(c->stream));
@@ -2404,20 +2062,14 @@ int prio3gpu_agg_allreduce(prio3gpu_comm* cm, prio3gpu_ctx* c, prio3gpu_agg* loc
   {
     PROF(KID_MERGE);
     const uint32_t nb = (uint32_t)std::min<size_t>((nel + 255) / 256, 4096);
-    if (is_f64(c))
-      hipLaunchKernelGGL(k_merge_ranks<Field64Ops>, dim3(nb + 1), dim3(256), 0, c->stream,
+    with_field(c, [&](auto fo) {
+      hipLaunchKernelGGL(k_merge_ranks<decltype(fo)>, dim3(nb + 1), dim3(256), 0, c->stream,
                          dst->share.u8(), cm->gather.u8(), nel, (uint32_t)cm->nranks,
                          total ? 1u : 0u, reinterpret_cast<unsigned long long*>(dst->counts.p),
                          reinterpret_cast<const unsigned long long*>(cm->cgather.p),
                          reinterpret_cast<SlotMeta*>(dst->meta.p),
                          reinterpret_cast<const SlotMeta*>(cm->mgather.p), local->slots, nb);
-    else
-      hipLaunchKernelGGL(k_merge_ranks<Field128Ops>, dim3(nb + 1), dim3(256), 0, c->stream,
-                         dst->share.u8(), cm->gather.u8(), nel, (uint32_t)cm->nranks,
-                         total ? 1u : 0u, reinterpret_cast<unsigned long long*>(dst->counts.p),
-                         reinterpret_cast<const unsigned long long*>(cm->cgather.p),
-                         reinterpret_cast<SlotMeta*>(dst->meta.p),
-                         reinterpret_cast<const SlotMeta*>(cm->mgather.p), local->slots, nb);
+    });
   }
   HIPCHK(hipGetLastError());
   HIPCHK(hipEventRecord(cm->done, c->stream));
@@ -2681,10 +2333,8 @@ int prio3gpu_test_flp_query(prio3gpu_ctx* c, size_t n, const uint8_t* leader_inp
     st->proof_rows = CRows{st->input.u8() + (size_t)g.meas_len * g.es, g.leader_share_len};
     st->n = n;
     st->xof_done = true;
-    if (is_f64(c))
-      CHK(launch_prep_query<Field64Ops>(c, st, n, st->status.u8()));
-    else
-      CHK(launch_prep_query<Field128Ops>(c, st, n, st->status.u8()));
+    CHK(with_field(
+        c, [&](auto fo) { return launch_prep_query<decltype(fo)>(c, st, n, st->status.u8()); }));
     CHK(copy_out(c, out_prep_shares, st->prep.p, n * g.prep_share_len));
     CHK(copy_out(c, status, st->status.p, n));
     HIPCHK(hipStreamSynchronize(c->stream));
@@ -2700,18 +2350,9 @@ int prio3gpu_test_flp_query(prio3gpu_ctx* c, size_t n, const uint8_t* leader_inp
 // ---- batched HPKE open on the GPU (hpke_gpu.h) --------------------------------------------------
 namespace {
 
-// A host buffer is copied into the context's scratch (grown on demand); a device buffer is used
-// where it is.
-int hpke_stage_in(prio3gpu_ctx* c, DevBuf& buf, const void* src, size_t bytes, const void** d) {
-  if (src && is_device_ptr(src)) {
-    *d = src;
-    return 0;
-  }
-  CHK(buf.ensure(std::max<size_t>(bytes, 16)));
-  if (bytes) HIPCHK(hipMemcpyAsync(buf.p, src, bytes, hipMemcpyHostToDevice, c->stream));
-  *d = buf.p;
-  return 0;
-}
+// stage_in's min_bytes for the HPKE inputs: a host buffer is copied into the context's scratch
+// (grown on demand), an empty one included; a device buffer is used where it is.
+constexpr size_t kHpkeMinStage = 16;
 
 int hpke_fetch_u64(prio3gpu_ctx* c, const uint64_t* p, uint64_t* out) {
   if (is_device_ptr(p)) {
@@ -2789,15 +2430,15 @@ int hpke_open_batch_impl(prio3gpu_ctx* c, const uint8_t* sk, const uint8_t* pk, 
     set_err("HPKE open: null data buffer or offsets out of order");
     return PRIO3GPU_E_ARG;
   }
-  const void *d_enc, *d_aad, *d_aoff, *d_ct, *d_coff, *d_poff, *d_st_in;
-  CHK(hpke_stage_in(c, c->hpke[0], encs, n * 32, &d_enc));
-  CHK(hpke_stage_in(c, c->hpke[1], aads, aad_total, &d_aad));
-  CHK(hpke_stage_in(c, c->hpke[2], aad_offsets, (n + 1) * 8, &d_aoff));
-  CHK(hpke_stage_in(c, c->hpke[3], cts, ct_total, &d_ct));
-  CHK(hpke_stage_in(c, c->hpke[4], ct_offsets, (n + 1) * 8, &d_coff));
-  CHK(hpke_stage_in(c, c->hpke[6], pt_offsets, (n + 1) * 8, &d_poff));
-  CHK(hpke_stage_in(c, c->hpke[7], status, n, &d_st_in));
-  uint8_t* d_st = static_cast<uint8_t*>(const_cast<void*>(d_st_in));
+  const uint8_t *d_enc, *d_aad, *d_aoff, *d_ct, *d_coff, *d_poff, *d_st_in;
+  CHK(stage_in(c, c->hpke[0], encs, n * 32, &d_enc, kHpkeMinStage));
+  CHK(stage_in(c, c->hpke[1], aads, aad_total, &d_aad, kHpkeMinStage));
+  CHK(stage_in(c, c->hpke[2], aad_offsets, (n + 1) * 8, &d_aoff, kHpkeMinStage));
+  CHK(stage_in(c, c->hpke[3], cts, ct_total, &d_ct, kHpkeMinStage));
+  CHK(stage_in(c, c->hpke[4], ct_offsets, (n + 1) * 8, &d_coff, kHpkeMinStage));
+  CHK(stage_in(c, c->hpke[6], pt_offsets, (n + 1) * 8, &d_poff, kHpkeMinStage));
+  CHK(stage_in(c, c->hpke[7], status, n, &d_st_in, kHpkeMinStage));
+  uint8_t* d_st = const_cast<uint8_t*>(d_st_in);
   uint8_t* d_pt = pts;
   const bool pt_host = !(pts && is_device_ptr(pts));
   if (pt_host) {
@@ -2808,15 +2449,14 @@ int hpke_open_batch_impl(prio3gpu_ctx* c, const uint8_t* sk, const uint8_t* pk, 
   CHK(c->hpke[8].ensure(n * 32));
   uint32_t* d_dh = static_cast<uint32_t*>(c->hpke[8].p);
   auto run = [&]() -> int {
-    CHK(launch_x25519(c, sk, n, static_cast<const uint8_t*>(d_enc), d_dh));
+    CHK(launch_x25519(c, sk, n, d_enc, d_dh));
     {
       PROF(KID_HPKE_OPEN);
       hipLaunchKernelGGL(k_hpke_open, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, c->stream,
-                         (uint32_t)n, bc, d_dh, static_cast<const uint8_t*>(d_enc),
-                         static_cast<const uint8_t*>(d_aad), static_cast<const uint64_t*>(d_aoff),
-                         aad_total, static_cast<const uint8_t*>(d_ct),
-                         static_cast<const uint64_t*>(d_coff), ct_total, d_pt,
-                         static_cast<const uint64_t*>(d_poff), pt_total, d_st);
+                         (uint32_t)n, bc, d_dh, d_enc, d_aad,
+                         reinterpret_cast<const uint64_t*>(d_aoff), aad_total, d_ct,
+                         reinterpret_cast<const uint64_t*>(d_coff), ct_total, d_pt,
+                         reinterpret_cast<const uint64_t*>(d_poff), pt_total, d_st);
     }
     HIPCHK(hipGetLastError());
     return 0;
@@ -2997,15 +2637,14 @@ int prio3gpu_test_x25519_gpu(prio3gpu_ctx* c, const uint8_t* sk, const uint8_t* 
   }
   if (n == 0) return 0;
   HIPCHK(hipSetDevice(c->device));
-  const void* d_pts;
-  CHK(hpke_stage_in(c, c->hpke[0], points, n * 32, &d_pts));
+  const uint8_t* d_pts;
+  CHK(stage_in(c, c->hpke[0], points, n * 32, &d_pts, kHpkeMinStage));
   uint8_t* d_out = out;
   if (!is_device_ptr(out)) {
     CHK(c->hpke[8].ensure(n * 32));
     d_out = c->hpke[8].u8();
   }
-  CHK(launch_x25519(c, sk, n, static_cast<const uint8_t*>(d_pts),
-                    reinterpret_cast<uint32_t*>(d_out)));
+  CHK(launch_x25519(c, sk, n, d_pts, reinterpret_cast<uint32_t*>(d_out)));
   if (d_out != out) {
     HIPCHK(hipMemcpyAsync(out, d_out, n * 32, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(hipMemsetAsync(d_out, 0, n * 32, c->stream));

@@ -13,6 +13,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "cfg.h"  // Xof, kXofShake128, kXofTurboShake128
+
 #ifndef DEVI
 #define DEVI __device__ __forceinline__
 #endif
@@ -136,16 +138,6 @@ DEVI void keccak_p(uint64_t a[25]) {
 #pragma unroll
   for (int i = 0; i < 25; ++i) a[i] = ((uint64_t)h[i] << 32) | l[i];
 }
-
-// The XOF of a context: XofShake128 (Keccak-f[1600] = 24 rounds, SHAKE padding byte 0x1F; prio
-// 0.15.1 / VDAF-07, Janus 0.6) or XofTurboShake128 (Keccak-p[1600, 12], domain byte 0x01;
-// draft-irtf-cfrg-vdaf-08+).  Both absorb the same message u8(len(dst)) || dst || seed || binder.
-struct Xof {
-  uint32_t full;  // 1: 24 rounds (SHAKE128), 0: 12 rounds (TurboSHAKE128)
-  uint32_t pad;   // first padding byte: 0x1F (SHAKE128) or the TurboSHAKE domain byte 0x01
-};
-constexpr Xof kXofShake128{1u, 0x1Fu};
-constexpr Xof kXofTurboShake128{0u, 0x01u};
 
 DEVI void keccak_x(uint64_t a[25], const Xof& x) {
   uint32_t l[25], h[25];
