@@ -549,6 +549,47 @@ int prio3gpu_hpke_open_report_shares_gpu(prio3gpu_ctx* ctx, const uint8_t* task_
                                          uint8_t* plaintexts, uint64_t* offsets, uint8_t* status,
                                          int threads);
 
+/* ---- Helper aggregate-init from the request's bytes (janus_amd/csrc/helper_request.h) -----------
+ * One call per aggregation job, on one context: the decoded AggregationJobInitializeReq in, prep
+ * messages out.  Equivalent, with agg_id = 1, to
+ *   prio3gpu_gather_prepare_inits -> prio3gpu_hpke_open_report_shares_gpu ->
+ *   prio3gpu_decode_plaintext_input_shares -> prio3gpu_apply_faults -> prio3gpu_helper_init
+ * with the same per-report statuses and precedence (HPKE 3 / 4, then plaintext or input-share
+ * decode 8, then public-share length 8, then ping-pong 5; aggregator.rs:1663-1797) and
+ * byte-identical prep messages, aggregate shares and counts.
+ *   msg, msg_len   the request: host memory (pinned or pageable) or device memory (detected).  It
+ *                  crosses PCIe once; no packed enc / aad / ciphertext arrays are built on the
+ *                  host for the reports the GPU opens, and their plaintexts and decoded input
+ *                  shares never leave the device.
+ *   views, n       prio3gpu_decode_agg_init_req's views, host memory.  Every offset and length is
+ *                  checked against msg_len before anything reads through it: a view that does not
+ *                  fit is PRIO3GPU_E_ARG for the call with nothing launched, and no kernel reads
+ *                  past msg.  n == 0 returns 0 and launches nothing.
+ *   status         n bytes, host memory, in/out as in prio3gpu_hpke_open_report_shares: a report
+ *                  whose status is non-zero on entry is skipped and keeps that status.
+ *   out_nonces     n x 16 report IDs (may be NULL); out_prep_msgs n x prep_msg (may be NULL); host
+ *                  or device memory.  batch_slots / agg as in prio3gpu_helper_init.
+ * Reports whose first-choice key (task key by config id, else global key) is X25519 / HKDF-SHA256
+ * / AES-128-GCM are opened and decoded on the GPU, one kernel pair per key.  The host path
+ * (prio3gpu_hpke_open_report_shares + prio3gpu_decode_plaintext_input_shares on `threads`
+ * threads) takes, inside the call, the reports whose first choice is another suite or a malformed
+ * key, the global-key second trial after a failed task-key open, and the plaintexts whose
+ * extension list is longer than 256 bytes (the device parser's duplicate check is quadratic in
+ * the item count, so a lane is never given more than 64 items); only those reports' input shares
+ * and statuses are uploaded.  A job with no such report does no host crypto.
+ * Secrets: a private key reaches the GPU only as a kernel argument; the device buffers that held
+ * the DH values and the plaintexts are zeroed before the call returns, on the error paths too.
+ * Scratch belongs to the context and grows to the largest job seen (PRIO3GPU_E_CAPACITY if the
+ * device cannot hold it).  `st` is a helper (agg_id 1) state of capacity >= n.  Synchronous. */
+int prio3gpu_helper_init_request(prio3gpu_ctx* ctx, prio3gpu_state* st, const uint8_t* task_id,
+                                 const prio3gpu_hpke_keypair* task_keys, size_t n_task_keys,
+                                 const prio3gpu_hpke_keypair* global_keys, size_t n_global_keys,
+                                 uint8_t sender_role, uint8_t recipient_role, const uint8_t* msg,
+                                 size_t msg_len, const prio3gpu_prepare_init_view* views, size_t n,
+                                 const uint32_t* batch_slots, uint8_t* out_nonces,
+                                 uint8_t* out_prep_msgs, uint8_t* status, prio3gpu_agg* agg,
+                                 int threads);
+
 /* Last error message for this thread (static storage). */
 const char* prio3gpu_last_error(void);
 /* Build identity: the SHA-256 (hex) of the sources, headers and compiler flags the library was

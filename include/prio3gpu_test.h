@@ -79,6 +79,17 @@ int prio3gpu_test_x25519_gpu(prio3gpu_ctx* ctx, const uint8_t* sk, const uint8_t
 int prio3gpu_test_field_op(int field_size, int op, uint32_t param, const uint8_t* in, size_t n,
                            uint8_t* out);
 
+/* k_req_gather alone (janus_amd/csrc/helper_request.h): the gather stage of
+ * prio3gpu_helper_init_request over the n views of `msg` (host or device memory; the views are
+ * host memory and are checked against msg_len first, PRIO3GPU_E_ARG if one does not fit), with the
+ * outputs of prio3gpu_gather_prepare_inits copied back to host memory: nonces n x 16, public
+ * shares n x public_share, leader prep shares n x prep_share (rows of faulty reports zeroed) and
+ * faults n bytes.  n == 0 returns 0 and launches nothing. */
+int prio3gpu_test_req_gather(prio3gpu_ctx* ctx, const uint8_t* msg, size_t msg_len,
+                             const prio3gpu_prepare_init_view* views, size_t n, uint8_t* nonces,
+                             uint8_t* public_shares, uint8_t* leader_prep_shares,
+                             uint8_t* faults);
+
 #ifdef __cplusplus
 }
 #endif

@@ -188,7 +188,13 @@ def _declare(lib):
         "prio3gpu_hpke_open_report_shares_gpu": (c.c_int, [P, u8p, P, c.c_size_t, P, c.c_size_t,
                                                            c.c_uint8, c.c_uint8, u8p, P,
                                                            c.c_size_t, u8p, P, u8p, c.c_int]),
+        # helper aggregate-init from the request's bytes (helper_request.h)
+        "prio3gpu_helper_init_request": (c.c_int, [P, P, u8p, P, c.c_size_t, P, c.c_size_t,
+                                                   c.c_uint8, c.c_uint8, u8p, c.c_size_t, P,
+                                                   c.c_size_t, P, u8p, u8p, u8p, P, c.c_int]),
         "prio3gpu_test_x25519_gpu": (c.c_int, [P, u8p, u8p, c.c_size_t, u8p]),
+        "prio3gpu_test_req_gather": (c.c_int, [P, u8p, c.c_size_t, P, c.c_size_t, u8p, u8p, u8p,
+                                               u8p]),
         "prio3gpu_test_field_op": (c.c_int, [c.c_int, c.c_int, c.c_uint32, u8p, c.c_size_t, u8p]),
     }
     for name, (res, args) in sigs.items():
@@ -222,12 +228,13 @@ EXPORTED = [
     "prio3gpu_hpke_open", "prio3gpu_hpke_seal", "prio3gpu_hpke_public_key",
     "prio3gpu_hpke_open_report_shares", "prio3gpu_x25519_batch",
     "prio3gpu_hpke_open_batch", "prio3gpu_hpke_open_report_shares_gpu",
+    "prio3gpu_helper_init_request",
 ]
 # The test / benchmark hooks of include/prio3gpu_test.h (same library, not part of the product ABI).
 TEST_EXPORTED = [
     "prio3gpu_test_squeeze", "prio3gpu_test_flp_query", "prio3gpu_dev_alloc", "prio3gpu_dev_free",
     "prio3gpu_memcpy", "prio3gpu_test_hpke_set_ifma", "prio3gpu_test_x25519_gpu",
-    "prio3gpu_test_field_op",
+    "prio3gpu_test_field_op", "prio3gpu_test_req_gather",
 ]
 
 

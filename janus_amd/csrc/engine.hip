@@ -25,6 +25,7 @@
 #include "fpvec_mfma.h"
 #include "fpvec_pair.h"
 #include "hpke_gpu.h"
+#include "helper_request.h"
 #include "field_test_kernels.h"
 
 using namespace p3g;
@@ -132,7 +133,8 @@ enum KernelId {
   KID_PNEXT, KID_ACC_PART, KID_ACC_SPEC, KID_ACC_MERGE, KID_OUT, KID_MERGE, KID_SHARD_SEEDS,
   KID_SHARD_MEAS, KID_SHARD_JR, KID_PROVE, KID_SHARD_PROOF, KID_REPORT_META, KID_REPORT_META_FOLD,
   KID_SHARD_NORM, KID_JR_RING, KID_FLP_QUERY_LANE, KID_FLP_WIRES_COLS, KID_FLP_WIRES_MFMA,
-  KID_FPV_REGEN, KID_X25519, KID_HPKE_OPEN, KID_COUNT
+  KID_FPV_REGEN, KID_X25519, KID_HPKE_OPEN, KID_REQ_GATHER, KID_X25519_IDX, KID_HPKE_OPEN_REQ,
+  KID_DECODE_PT, KID_REQ_SCATTER, KID_REQ_COPY, KID_COUNT
 };
 const char* const kKernelNames[KID_COUNT] = {
     "k_query_rand", "k_expand", "k_helper_xof", "k_jr", "k_flp_weights", "k_flp_wires",
@@ -140,7 +142,10 @@ const char* const kKernelNames[KID_COUNT] = {
     "k_prepare_next", "k_accum_partial", "k_accum_spec", "k_accum_merge", "k_out_shares", "k_merge",
     "k_shard_seeds", "k_shard_meas", "k_shard_jr", "k_flp_prove", "k_shard_proof", "k_report_meta",
     "k_report_meta_fold", "k_shard_norm", "k_jr_ring", "k_flp_query_lane", "k_flp_wires_cols",
-    "k_flp_wires_mfma", "k_fpv_regen", "k_x25519", "k_hpke_open"};
+    "k_flp_wires_mfma", "k_fpv_regen", "k_x25519", "k_hpke_open", "k_req_gather", "k_x25519_idx",
+    "k_hpke_open_req", "k_decode_plaintext_input_shares", "k_req_scatter",
+    // not a kernel: the request's one host-to-device copy in prio3gpu_helper_init_request
+    "copy_request"};
 
 // Per-kernel HIP-event timing on the context's stream (opt-in; used by bench.py).
 struct Prof {
@@ -183,6 +188,10 @@ struct prio3gpu_ctx {
   // prio3gpu_hpke_open_batch: staging of host inputs / outputs (enc, aad, aad offsets, ct, ct
   // offsets, pt, pt offsets, status) and the ladder's DH values; grown on demand
   DevBuf hpke[9];
+  // prio3gpu_helper_init_request: the request, its views, key-group index lists, DH values,
+  // plaintexts, plaintext offsets, faults, and the host-fallback reports' compact rows; grown on
+  // demand to the largest job seen
+  DevBuf req[8];
   // Engine options (prio3gpu_ctx_set_option; include/prio3gpu.h lists them).  The defaults are the
   // measured-fastest paths; every alternative is parity-tested against the oracle.
   bool speculate = true;     // "speculate": accumulation from k_jr's column sums (0: direct)
@@ -2390,22 +2399,87 @@ void host_parallel(size_t n, int threads, F&& f) {
 
 // d_out[r] = X25519(sk, d_points[r]); the clamped scalar travels as a kernel argument, so no
 // device buffer ever holds the private key.
-int launch_x25519(prio3gpu_ctx* c, const uint8_t* sk, size_t n, const uint8_t* d_points,
-                  uint32_t* d_out) {
+void clamp_scalar(const uint8_t* sk, X25519Scalar* ks) {
   uint8_t k[32];
   memcpy(k, sk, 32);
   k[0] &= 248;  // decodeScalar25519
   k[31] &= 127;
   k[31] |= 64;
+  memcpy(ks->w, k, 32);  // little-endian host
+  wipe(k, sizeof k);
+}
+
+int launch_x25519(prio3gpu_ctx* c, const uint8_t* sk, size_t n, const uint8_t* d_points,
+                  uint32_t* d_out) {
   X25519Scalar ks;
-  memcpy(ks.w, k, 32);  // little-endian host
+  clamp_scalar(sk, &ks);
   {
     PROF(KID_X25519);
     hipLaunchKernelGGL(k_x25519, dim3((unsigned)((n + 63) / 64)), dim3(64), 0, c->stream,
                        (uint32_t)n, ks, d_points, d_out);
   }
-  wipe(k, sizeof k);
   wipe(&ks, sizeof ks);
+  HIPCHK(hipGetLastError());
+  return 0;
+}
+
+// The same over a key group of the request in device memory: d_dh[idx[j]] for j < m.
+int launch_x25519_idx(prio3gpu_ctx* c, const uint8_t* sk, size_t m, const uint32_t* d_idx,
+                      const uint8_t* d_msg, const ReqView* d_views, uint32_t* d_dh) {
+  X25519Scalar ks;
+  clamp_scalar(sk, &ks);
+  {
+    PROF(KID_X25519_IDX);
+    hipLaunchKernelGGL(k_x25519_idx, dim3((unsigned)((m + 63) / 64)), dim3(64), 0, c->stream,
+                       (uint32_t)m, ks, d_idx, d_msg, d_views, d_dh);
+  }
+  wipe(&ks, sizeof ks);
+  HIPCHK(hipGetLastError());
+  return 0;
+}
+
+bool span_fits(uint64_t off, uint64_t len, uint64_t total) {
+  return off <= total && len <= total - off;
+}
+
+// Every offset a kernel (or the host fallback) reads through, against the message length; and
+// the gather's grid, which must fit one launch.
+int check_request_views(const Cfg& g, const prio3gpu_prepare_init_view* views, size_t n,
+                        size_t msg_len) {
+  for (size_t i = 0; i < n; ++i) {
+    const prio3gpu_prepare_init_view& v = views[i];
+    if (!span_fits(v.report_id_off, 16, msg_len) ||
+        !span_fits(v.public_share_off, v.public_share_len, msg_len) ||
+        !span_fits(v.enc_off, v.enc_len, msg_len) ||
+        !span_fits(v.payload_off, v.payload_len, msg_len) ||
+        !span_fits(v.prep_share_off, v.prep_share_len, msg_len) ||
+        !span_fits(v.prep_msg_off, v.prep_msg_len, msg_len)) {
+      set_err("view %zu does not fit the %zu-byte message", i, msg_len);
+      return PRIO3GPU_E_ARG;
+    }
+  }
+  const uint64_t max_ppr =
+      std::max<uint64_t>(1, (std::max(g.public_share_len, g.prep_share_len) + 15u) / 16u);
+  if ((n * max_ppr + 255) / 256 > 0x7FFFFFFFull) {
+    set_err("job too large for one gather launch");
+    return PRIO3GPU_E_CAPACITY;
+  }
+  return 0;
+}
+
+// k_req_gather over n checked views: rows of 16 / public_share_len / prep_share_len bytes.
+int launch_req_gather(prio3gpu_ctx* c, size_t n, const uint8_t* d_msg, size_t msg_len,
+                      const ReqView* d_views, uint8_t* d_nonces, uint8_t* d_pub, uint8_t* d_lps,
+                      uint8_t* d_faults) {
+  const Cfg& g = c->cfg;
+  const uint64_t max_ppr =
+      std::max<uint64_t>(1, (std::max(g.public_share_len, g.prep_share_len) + 15u) / 16u);
+  {
+    PROF(KID_REQ_GATHER);
+    hipLaunchKernelGGL(k_req_gather, dim3((unsigned)((n * max_ppr + 255) / 256), 3), dim3(256), 0,
+                       c->stream, (uint32_t)n, d_msg, (uint64_t)msg_len, d_views,
+                       g.public_share_len, g.prep_share_len, d_nonces, d_pub, d_lps, d_faults);
+  }
   HIPCHK(hipGetLastError());
   return 0;
 }
@@ -2626,6 +2700,276 @@ int prio3gpu_hpke_open_report_shares_gpu(
     for (size_t i = 0; i < n; ++i)
       if (!was_retry[i]) status[i] = st_retry[i];
   }
+  return 0;
+}
+
+int prio3gpu_helper_init_request(
+    prio3gpu_ctx* c, prio3gpu_state* st, const uint8_t* task_id,
+    const prio3gpu_hpke_keypair* task_keys, size_t n_task_keys,
+    const prio3gpu_hpke_keypair* global_keys, size_t n_global_keys, uint8_t sender_role,
+    uint8_t recipient_role, const uint8_t* msg, size_t msg_len,
+    const prio3gpu_prepare_init_view* views, size_t n, const uint32_t* batch_slots,
+    uint8_t* out_nonces, uint8_t* out_prep_msgs, uint8_t* status, prio3gpu_agg* agg, int threads) {
+  CHK(check_state(c, st, n));
+  if (st->agg_id != 1) {
+    set_err("helper_init_request needs a helper (agg_id 1) state");
+    return PRIO3GPU_E_ARG;
+  }
+  if (n == 0) return 0;
+  if (!task_id || !msg || !views || !status || (n_task_keys && !task_keys) ||
+      (n_global_keys && !global_keys) || n > 0x7FFFFFFFu) {
+    set_err("helper_init_request: null argument");
+    return PRIO3GPU_E_ARG;
+  }
+  if (agg && agg->ctx != c) {
+    set_err("aggregate belongs to another context");
+    return PRIO3GPU_E_ARG;
+  }
+  if (is_device_ptr(views) || is_device_ptr(status)) {
+    set_err("helper_init_request: views and status are host memory");
+    return PRIO3GPU_E_ARG;
+  }
+  const Cfg& g = c->cfg;
+  const uint32_t pub_len = g.public_share_len, prep_len = g.prep_share_len;
+  const uint32_t want = g.helper_share_len;
+  CHK(check_request_views(g, views, n, msg_len));
+  auto find = [](const prio3gpu_hpke_keypair* ks, size_t nk, uint8_t id) {
+    for (size_t k = 0; k < nk; ++k)
+      if (ks[k].config_id == id) return &ks[k];
+    return static_cast<const prio3gpu_hpke_keypair*>(nullptr);
+  };
+  // Key selection as in prio3gpu_hpke_open_report_shares_gpu: the first-choice key of every report
+  // (task key, else global key, by config id).  Reports whose first choice is an X25519 /
+  // HKDF-SHA256 / AES-128-GCM key form one group per key for the GPU; an unknown id is status 3
+  // here; every other key is the host path's (REQ_HOST in the device status image).
+  std::vector<const prio3gpu_hpke_keypair*> groups;
+  std::vector<int32_t> grp(n, -1);
+  std::vector<uint8_t> dst(status, status + n);
+  std::vector<uint64_t> poff(n + 1, 0);
+  for (size_t i = 0; i < n; ++i) {
+    const prio3gpu_prepare_init_view& v = views[i];
+    poff[i + 1] = poff[i] + (v.payload_len >= 16 ? v.payload_len - 16 : 0);
+    if (status[i]) continue;
+    const prio3gpu_hpke_keypair* tk = find(task_keys, n_task_keys, v.hpke_config_id);
+    const prio3gpu_hpke_keypair* kp = tk ? tk : find(global_keys, n_global_keys, v.hpke_config_id);
+    if (!kp) {
+      dst[i] = PRIO3GPU_HPKE_UNKNOWN_CONFIG_ID;
+      continue;
+    }
+    if (!hpke_gpu_suite(kp->kem_id, kp->kdf_id, kp->aead_id) || !kp->private_key ||
+        kp->private_key_len != 32 || !kp->public_key || kp->public_key_len != 32) {
+      dst[i] = REQ_HOST;
+      continue;
+    }
+    size_t k = std::find(groups.begin(), groups.end(), kp) - groups.begin();
+    if (k == groups.size()) groups.push_back(kp);
+    grp[i] = (int32_t)k;
+  }
+  std::vector<uint32_t> idx;
+  std::vector<size_t> gbeg(groups.size() + 1, 0);
+  for (size_t k = 0; k < groups.size(); ++k) {
+    for (size_t i = 0; i < n; ++i)
+      if (grp[i] == (int32_t)k) idx.push_back((uint32_t)i);
+    gbeg[k + 1] = idx.size();
+  }
+  const uint8_t info[20] = {'d', 'a', 'p', '-', '0', '7', ' ', 'i', 'n', 'p', 'u', 't', ' ', 's',
+                            'h', 'a', 'r', 'e', sender_role, recipient_role};  // hpke.rs:52-77
+  std::vector<HpkeBatchConsts> bcs(groups.size());
+  for (size_t k = 0; k < groups.size(); ++k)
+    if (!hpke_batch_consts(groups[k]->public_key, info, sizeof info, &bcs[k])) {
+      set_err("HPKE primitives unavailable");
+      return PRIO3GPU_E_UNSUPPORTED;
+    }
+  ReqTaskId tid;
+  memcpy(tid.w, task_id, 32);  // little-endian host: byte j at bits 8 (j & 3) of word j >> 2
+
+  HIPCHK(hipSetDevice(c->device));
+  const size_t in_pitch = input_pitch(st);
+  const uint64_t pt_total = poff[n];
+  CHK(c->req[1].ensure(n * sizeof(ReqView)));
+  CHK(c->req[2].ensure(std::max<size_t>(idx.size(), 1) * 4));
+  CHK(c->req[3].ensure(n * 32));
+  CHK(c->req[4].ensure(std::max<uint64_t>(pt_total, 16)));
+  CHK(c->req[5].ensure((n + 1) * 8));
+  CHK(c->req[6].ensure(n));
+  CHK(st->status.ensure(n));
+  CHK(st->nonces.ensure(n * 16));
+  CHK(st->pub.ensure(std::max<size_t>(n * pub_len, 16)));
+  CHK(st->input.ensure((n - 1) * in_pitch + want));
+  CHK(c->io[0].ensure(std::max<size_t>(n * prep_len, 16)));
+  const uint8_t* d_msg;
+  {
+    PROF(KID_REQ_COPY);
+    CHK(stage_in(c, c->req[0], msg, msg_len, &d_msg, 16));
+  }
+  const ReqView* d_views = static_cast<const ReqView*>(c->req[1].p);
+  const uint32_t* d_idx = static_cast<const uint32_t*>(c->req[2].p);
+  uint32_t* d_dh = static_cast<uint32_t*>(c->req[3].p);
+  uint8_t* d_pts = c->req[4].u8();
+  const uint64_t* d_poff = static_cast<const uint64_t*>(c->req[5].p);
+  uint8_t* d_faults = c->req[6].u8();
+  uint8_t* d_status = st->status.u8();
+  uint8_t* d_in = st->input.u8();
+  std::vector<uint8_t> host_msg, hp, hin, fb;  // host fallback: message copy, plaintexts, rows
+  auto run = [&]() -> int {
+    HIPCHK(hipMemcpyAsync(c->req[1].p, views, n * sizeof(ReqView), hipMemcpyHostToDevice,
+                          c->stream));
+    if (!idx.empty())
+      HIPCHK(hipMemcpyAsync(c->req[2].p, idx.data(), idx.size() * 4, hipMemcpyHostToDevice,
+                            c->stream));
+    HIPCHK(hipMemcpyAsync(c->req[5].p, poff.data(), (n + 1) * 8, hipMemcpyHostToDevice,
+                          c->stream));
+    HIPCHK(hipMemcpyAsync(d_status, dst.data(), n, hipMemcpyHostToDevice, c->stream));
+    CHK(launch_req_gather(c, n, d_msg, msg_len, d_views, st->nonces.u8(), st->pub.u8(),
+                          c->io[0].u8(), d_faults));
+    for (size_t k = 0; k < groups.size(); ++k) {
+      const size_t m = gbeg[k + 1] - gbeg[k];
+      CHK(launch_x25519_idx(c, groups[k]->private_key, m, d_idx + gbeg[k], d_msg, d_views, d_dh));
+      {
+        PROF(KID_HPKE_OPEN_REQ);
+        hipLaunchKernelGGL(k_hpke_open_req, dim3((unsigned)((m + 255) / 256)), dim3(256), 0,
+                           c->stream, (uint32_t)m, bcs[k], tid, d_idx + gbeg[k], d_dh, d_msg,
+                           d_views, d_pts, d_poff, d_status);
+      }
+      HIPCHK(hipGetLastError());
+    }
+    {
+      PROF(KID_DECODE_PT);
+      hipLaunchKernelGGL(k_decode_plaintext_input_shares, grid1(n, 256), dim3(256), 0, c->stream,
+                         (uint32_t)n, d_pts, d_poff, want, d_in, (uint64_t)in_pitch, d_faults,
+                         d_status);
+    }
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpyAsync(dst.data(), d_status, n, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    // The host's share: other suites and malformed keys (REQ_HOST), long extension lists
+    // (REQ_DEFER), both with the full key order; and the global-key second trial after a failed
+    // task-key open, with the global keys alone.
+    std::vector<uint8_t> st_host(n, 1), st_retry(n, 1);
+    size_t n_host = 0, n_retry = 0;
+    for (size_t i = 0; i < n; ++i) {
+      if (dst[i] == REQ_HOST || dst[i] == REQ_DEFER) {
+        st_host[i] = 0;
+        ++n_host;
+      } else if (grp[i] >= 0 && dst[i] == PRIO3GPU_HPKE_DECRYPT_ERROR) {
+        const prio3gpu_hpke_keypair* kp = groups[grp[i]];
+        const bool is_task_key = kp >= task_keys && kp < task_keys + n_task_keys;
+        if (is_task_key && find(global_keys, n_global_keys, views[i].hpke_config_id)) {
+          st_retry[i] = 0;
+          ++n_retry;
+        }
+      }
+    }
+    if (n_host + n_retry == 0) return 0;
+    const uint8_t* h_msg = msg;
+    if (is_device_ptr(msg)) {
+      host_msg.resize(msg_len);
+      HIPCHK(hipMemcpyAsync(host_msg.data(), msg, msg_len, hipMemcpyDeviceToHost, c->stream));
+      HIPCHK(hipStreamSynchronize(c->stream));
+      h_msg = host_msg.data();
+    }
+    hp.assign(std::max<uint64_t>(pt_total, 1), 0);
+    std::vector<uint64_t> offs(n + 1);
+    std::vector<uint8_t> st_fb(n, 1);
+    if (n_host) {
+      st_fb = st_host;
+      CHK(prio3gpu_hpke_open_report_shares(task_id, task_keys, n_task_keys, global_keys,
+                                           n_global_keys, sender_role, recipient_role, h_msg,
+                                           views, n, hp.data(), offs.data(), st_fb.data(),
+                                           threads));
+    }
+    if (n_retry) {
+      std::vector<uint8_t> s2(st_retry);
+      CHK(prio3gpu_hpke_open_report_shares(task_id, nullptr, 0, global_keys, n_global_keys,
+                                           sender_role, recipient_role, h_msg, views, n, hp.data(),
+                                           offs.data(), s2.data(), threads));
+      for (size_t i = 0; i < n; ++i)
+        if (!st_retry[i]) st_fb[i] = s2[i];
+    }
+    hin.assign(n * (size_t)want, 0);
+    CHK(prio3gpu_decode_plaintext_input_shares(&c->sz, hp.data(), offs.data(), n, 1, hin.data(),
+                                               st_fb.data()));
+    // compact: indices | rows | statuses of the fallback reports, one upload
+    const size_t kf = n_host + n_retry;
+    const size_t o_rows = (kf * 4 + 15) / 16 * 16, o_st = o_rows + kf * want;
+    fb.assign(o_st + kf, 0);
+    size_t j = 0;
+    for (size_t i = 0; i < n; ++i) {
+      if (st_host[i] && st_retry[i]) continue;
+      const uint32_t r = (uint32_t)i;
+      memcpy(&fb[4 * j], &r, 4);
+      memcpy(&fb[o_rows + j * want], &hin[i * (size_t)want], want);
+      fb[o_st + j] = st_fb[i];
+      ++j;
+    }
+    CHK(c->req[7].ensure(fb.size()));
+    uint8_t* d_fb = c->req[7].u8();
+    HIPCHK(hipMemcpyAsync(d_fb, fb.data(), fb.size(), hipMemcpyHostToDevice, c->stream));
+    {
+      PROF(KID_REQ_SCATTER);
+      hipLaunchKernelGGL(k_req_scatter, grid1(kf, 256), dim3(256), 0, c->stream, (uint32_t)kf,
+                         reinterpret_cast<const uint32_t*>(d_fb), d_fb + o_rows, d_fb + o_st, want,
+                         d_in, (uint64_t)in_pitch, d_faults, d_status);
+    }
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemsetAsync(d_fb, 0, fb.size(), c->stream));  // input shares are secrets too
+    return 0;
+  };
+  int rc = run();
+  // the per-report secrets outside the engine's rows: the DH values and the plaintexts
+  bool cleared = hipMemsetAsync(d_dh, 0, n * 32, c->stream) == hipSuccess;
+  if (pt_total) cleared &= hipMemsetAsync(d_pts, 0, pt_total, c->stream) == hipSuccess;
+  if (!cleared && !rc) {
+    set_err("clearing the request's secrets failed");
+    rc = PRIO3GPU_E_HIP;
+  }
+  if (rc || !fb.empty()) (void)hipStreamSynchronize(c->stream);  // fb, hp, hin are read by copies
+  wipe(hp.data(), hp.size());
+  wipe(hin.data(), hin.size());
+  wipe(fb.data(), fb.size());
+  if (rc) return rc;
+  CHK(copy_out(c, out_nonces, st->nonces.u8(), n * 16));
+  rc = prio3gpu_helper_init(c, st, n, st->nonces.u8(), st->pub.u8(), d_in, c->io[0].u8(),
+                            batch_slots, out_prep_msgs, d_status, agg);
+  if (rc) {
+    (void)hipStreamSynchronize(c->stream);
+    return rc;
+  }
+  HIPCHK(hipMemcpyAsync(status, d_status, n, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(hipStreamSynchronize(c->stream));
+  return 0;
+}
+
+int prio3gpu_test_req_gather(prio3gpu_ctx* c, const uint8_t* msg, size_t msg_len,
+                             const prio3gpu_prepare_init_view* views, size_t n, uint8_t* nonces,
+                             uint8_t* public_shares, uint8_t* leader_prep_shares,
+                             uint8_t* faults) {
+  if (!c || (n && (!msg || !views || !nonces || !public_shares || !leader_prep_shares ||
+                   !faults)) || n > 0x7FFFFFFFu) {
+    set_err("null argument");
+    return PRIO3GPU_E_ARG;
+  }
+  if (n == 0) return 0;
+  const Cfg& g = c->cfg;
+  CHK(check_request_views(g, views, n, msg_len));
+  HIPCHK(hipSetDevice(c->device));
+  const size_t nb_pub = n * (size_t)g.public_share_len, nb_lps = n * (size_t)g.prep_share_len;
+  const uint8_t* d_msg;
+  CHK(stage_in(c, c->req[0], msg, msg_len, &d_msg, 16));
+  CHK(c->req[1].ensure(n * sizeof(ReqView)));
+  CHK(c->req[6].ensure(n));
+  CHK(c->io[0].ensure(std::max<size_t>(nb_lps, 16)));
+  CHK(c->io[1].ensure(std::max<size_t>(nb_pub, 16)));
+  CHK(c->io[2].ensure(n * 16));
+  HIPCHK(hipMemcpyAsync(c->req[1].p, views, n * sizeof(ReqView), hipMemcpyHostToDevice,
+                        c->stream));
+  CHK(launch_req_gather(c, n, d_msg, msg_len, static_cast<const ReqView*>(c->req[1].p),
+                        c->io[2].u8(), c->io[1].u8(), c->io[0].u8(), c->req[6].u8()));
+  CHK(copy_out(c, nonces, c->io[2].u8(), n * 16));
+  CHK(copy_out(c, public_shares, c->io[1].u8(), nb_pub));
+  CHK(copy_out(c, leader_prep_shares, c->io[0].u8(), nb_lps));
+  CHK(copy_out(c, faults, c->req[6].u8(), n));
+  HIPCHK(hipStreamSynchronize(c->stream));
   return 0;
 }
 

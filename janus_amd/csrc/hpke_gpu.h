@@ -4,6 +4,8 @@
 // One lane per report, every report of a launch under ONE private key:
 //   k_x25519     dh = X25519(skR, enc)                       RFC 7748 §5
 //   k_hpke_open  shared_secret, key schedule, AES-128-GCM    RFC 9180 §4.1, §5.1; NIST SP 800-38D
+// Each kernel is a thin shell around a per-lane device function (x25519_lane, hpke_open_lane over
+// a GHASH byte source) that helper_request.h's kernels call too, with the request read in place.
 // Included by engine.hip after prio3_kernels.h (SHA-256 is sha256_compress from there).
 #pragma once
 #include "hpke_shared.h"
@@ -202,19 +204,18 @@ DEVI void fe_to_words(uint32_t w[8], const Fe25& f) {
   }
 }
 
-// out[r] = X25519(k, points[r]), one lane per point.  The Montgomery ladder of RFC 7748 §5; the
-// scalar is wave-uniform, its bits are read with uniform selects and used only as swap masks, so
-// no branch and no address depends on the scalar or on a field value.
-__global__ void __launch_bounds__(64) k_x25519(uint32_t n, X25519Scalar k, const uint8_t* points,
-                                               uint32_t* out) {
-  const uint32_t r = blockIdx.x * blockDim.x + threadIdx.x;
-  const bool live = r < n;
-  const uint8_t* p = points + (size_t)(live ? r : n - 1) * 32;
-  uint32_t w[8];
+// 32 bytes at p (any alignment) as little-endian words
+DEVI void load_le_words8(const uint8_t* p, uint32_t w[8]) {
 #pragma unroll
   for (int i = 0; i < 8; ++i)
     w[i] = (uint32_t)p[4 * i] | ((uint32_t)p[4 * i + 1] << 8) | ((uint32_t)p[4 * i + 2] << 16) |
            ((uint32_t)p[4 * i + 3] << 24);
+}
+
+// w = X25519(k, w) for this lane's point (little-endian words).  The Montgomery ladder of RFC 7748
+// §5; the scalar is wave-uniform, its bits are read with uniform selects and used only as swap
+// masks, so no branch and no address depends on the scalar or on a field value.
+DEVI void x25519_lane(const X25519Scalar& k, uint32_t w[8]) {
   Fe25 x1, x2, z2, x3, z3;
   fe_from_words(x1, w);
 #pragma unroll
@@ -261,6 +262,16 @@ __global__ void __launch_bounds__(64) k_x25519(uint32_t n, X25519Scalar k, const
   fe_invert(inv, z2);
   fe_mul(x2, x2, inv);
   fe_to_words(w, x2);
+}
+
+// out[r] = X25519(k, points[r]), one lane per point.
+__global__ void __launch_bounds__(64) k_x25519(uint32_t n, X25519Scalar k, const uint8_t* points,
+                                               uint32_t* out) {
+  const uint32_t r = blockIdx.x * blockDim.x + threadIdx.x;
+  const bool live = r < n;
+  uint32_t w[8];
+  load_le_words8(points + (size_t)(live ? r : n - 1) * 32, w);
+  x25519_lane(k, w);
   if (live) {
 #pragma unroll
     for (int i = 0; i < 8; ++i) out[(size_t)r * 8 + i] = w[i];
@@ -519,22 +530,95 @@ DEVI void load_block(const uint8_t* p, uint64_t rem, uint32_t d[4]) {
   }
 }
 
-// GHASH the `len` bytes at p into y (zero-padded to whole blocks).
-DEVI void ghash_bytes(uint32_t y[4], const uint32_t h[4], const uint8_t* p, uint64_t len) {
+// A byte source for GHASH: len() bytes, block(o, d) = the 16 bytes at offset o (a multiple of 16)
+// as block words, zero past the end.  PackedBytes is the contiguous one.
+struct PackedBytes {
+  const uint8_t* p;
+  uint64_t n;
+  DEVI uint64_t len() const { return n; }
+  DEVI void block(uint64_t o, uint32_t d[4]) const { load_block(p + o, n - o, d); }
+};
+
+// GHASH the source's bytes into y (zero-padded to whole blocks).
+template <class Src>
+DEVI void ghash_bytes(uint32_t y[4], const uint32_t h[4], const Src& src) {
+  const uint64_t len = src.len();
   for (uint64_t o = 0; o < len; o += 16) {
     uint32_t d[4], x[4];
-    load_block(p + o, len - o, d);
+    src.block(o, d);
 #pragma unroll
     for (int i = 0; i < 4; ++i) x[i] = bswap32(d[i]);
     ghash_step(y, x, h);
   }
 }
 
-// One lane per report: derive (key, base_nonce) from the lane's dh and enc, check the GCM tag
-// over aad || ct, then write the plaintext -- or zeros and status 4 when anything fails (a short
-// ciphertext, offsets that do not fit, an all-zero dh (RFC 9180 §7.1.4), a tag mismatch).  A
-// report whose status is non-zero on entry keeps it and gets zeros.  Lanes have their own
-// lengths; the only barrier is the one after the S-box is built, before any lane diverges.
+// A report that is not opened: its slot is zeroed; status 4 unless it was skipped on entry.
+DEVI void hpke_open_reject(uint8_t* pt, uint64_t pt_cap, uint8_t* status, bool skip) {
+  for (uint64_t j = 0; j < pt_cap; ++j) pt[j] = 0;
+  if (!skip) *status = ST_HPKE_DECRYPT;
+}
+
+// One report, one lane: derive (key, base_nonce) from the lane's dh (8 words as k_x25519 wrote
+// them) and enc (32 bytes), check the GCM tag over aad || ct[0 .. body), then write the plaintext
+// to pt[0 .. body) and zeros up to pt_cap -- or zeros and status 4 when the tag does not match or
+// dh is all zero (RFC 9180 §7.1.4): never unauthenticated plaintext.  ct holds body + 16 bytes.
+template <class Aad>
+DEVI void hpke_open_lane(const uint8_t* sbox, const HpkeBatchConsts& bc, const uint32_t* dh,
+                         const uint8_t* enc, const Aad& aad, const uint8_t* ct, uint64_t body,
+                         uint8_t* pt, uint64_t pt_cap, uint8_t* status) {
+  uint32_t dhw[8], encw[8], nz = 0;
+#pragma unroll
+  for (int i = 0; i < 8; ++i) {
+    const uint32_t d = dh[i];
+    nz |= d;
+    dhw[i] = bswap32(d);
+    const uint8_t* e = enc + 4 * i;
+    encw[i] = ((uint32_t)e[0] << 24) | ((uint32_t)e[1] << 16) | ((uint32_t)e[2] << 8) | e[3];
+  }
+  uint32_t key[4], nonce[3];
+  hpke_key_nonce(bc, dhw, encw, key, nonce);
+  uint32_t rk[44];
+  aes128_expand(sbox, key, rk);
+  const uint32_t zero[4] = {0, 0, 0, 0};
+  uint32_t hle[4], h[4], ctr[4], ek[4];
+  aes128_encrypt(sbox, rk, zero, hle);  // H = E(K, 0)
+#pragma unroll
+  for (int i = 0; i < 4; ++i) h[i] = bswap32(hle[i]);
+  uint32_t y[4] = {0, 0, 0, 0};
+  ghash_bytes(y, h, aad);
+  ghash_bytes(y, h, PackedBytes{ct, body});
+  const uint64_t abits = aad.len() * 8, cbits = body * 8;
+  const uint32_t lens[4] = {(uint32_t)(abits >> 32), (uint32_t)abits, (uint32_t)(cbits >> 32),
+                            (uint32_t)cbits};
+  ghash_step(y, lens, h);
+#pragma unroll
+  for (int i = 0; i < 3; ++i) ctr[i] = bswap32(nonce[i]);
+  ctr[3] = bswap32(1u);  // J0 = nonce || 1 (seq 0: the nonce is base_nonce)
+  aes128_encrypt(sbox, rk, ctr, ek);
+  uint32_t tag[4], diff = 0;
+  load_block(ct + body, 16, tag);
+#pragma unroll
+  for (int i = 0; i < 4; ++i) diff |= (bswap32(y[i]) ^ ek[i]) ^ tag[i];  // no early exit
+  if (diff != 0u || nz == 0u) {
+    hpke_open_reject(pt, pt_cap, status, false);
+    return;
+  }
+  for (uint64_t o = 0; o < body; o += 16) {  // CTR from counter 2
+    uint32_t d[4];
+    load_block(ct + o, body - o, d);
+    ctr[3] = bswap32((uint32_t)(o >> 4) + 2u);
+    aes128_encrypt(sbox, rk, ctr, ek);
+#pragma unroll
+    for (int j = 0; j < 16; ++j)
+      if (o + j < body) pt[o + j] = (uint8_t)((d[j >> 2] ^ ek[j >> 2]) >> (8 * (j & 3)));
+  }
+  for (uint64_t j = body; j < pt_cap; ++j) pt[j] = 0;
+}
+
+// One lane per report: hpke_open_lane over packed inputs, or zeros and status 4 when there is
+// nothing to open (a short ciphertext, offsets that do not fit).  A report whose status is
+// non-zero on entry keeps it and gets zeros.  Lanes have their own lengths; the only barrier is
+// the one after the S-box is built, before any lane diverges.
 __global__ void __launch_bounds__(256) k_hpke_open(
     uint32_t n, HpkeBatchConsts bc, const uint32_t* dh, const uint8_t* encs, const uint8_t* aads,
     const uint64_t* aad_off, uint64_t aad_total, const uint8_t* cts, const uint64_t* ct_off,
@@ -550,65 +634,14 @@ __global__ void __launch_bounds__(256) k_hpke_open(
   const uint64_t pt_cap = pt_fits ? p1 - p0 : 0;
   uint8_t* pt = pts + p0;
   const bool skip = status[r] != 0;
-  bool ok = !skip && pt_fits && a0 <= a1 && a1 <= aad_total && c0 <= c1 && c1 <= ct_total &&
-            c1 - c0 >= 16 && c1 - c0 - 16 <= pt_cap;
+  const bool ok = !skip && pt_fits && a0 <= a1 && a1 <= aad_total && c0 <= c1 && c1 <= ct_total &&
+                  c1 - c0 >= 16 && c1 - c0 - 16 <= pt_cap;
   if (!ok) {  // nothing to read: skip the work, not just the result
-    for (uint64_t j = 0; j < pt_cap; ++j) pt[j] = 0;
-    if (!skip) status[r] = ST_HPKE_DECRYPT;
+    hpke_open_reject(pt, pt_cap, status + r, skip);
     return;
   }
-  const uint64_t alen = a1 - a0, body = c1 - c0 - 16;
-  const uint8_t* aad = aads + a0;
-  const uint8_t* ct = cts + c0;
-  uint32_t dhw[8], encw[8], nz = 0;
-#pragma unroll
-  for (int i = 0; i < 8; ++i) {
-    const uint32_t d = dh[(size_t)r * 8 + i];
-    nz |= d;
-    dhw[i] = bswap32(d);
-    const uint8_t* e = encs + (size_t)r * 32 + 4 * i;
-    encw[i] = ((uint32_t)e[0] << 24) | ((uint32_t)e[1] << 16) | ((uint32_t)e[2] << 8) | e[3];
-  }
-  uint32_t key[4], nonce[3];
-  hpke_key_nonce(bc, dhw, encw, key, nonce);
-  uint32_t rk[44];
-  aes128_expand(sbox, key, rk);
-  const uint32_t zero[4] = {0, 0, 0, 0};
-  uint32_t hle[4], h[4], ctr[4], ek[4];
-  aes128_encrypt(sbox, rk, zero, hle);  // H = E(K, 0)
-#pragma unroll
-  for (int i = 0; i < 4; ++i) h[i] = bswap32(hle[i]);
-  uint32_t y[4] = {0, 0, 0, 0};
-  ghash_bytes(y, h, aad, alen);
-  ghash_bytes(y, h, ct, body);
-  const uint64_t abits = alen * 8, cbits = body * 8;
-  const uint32_t lens[4] = {(uint32_t)(abits >> 32), (uint32_t)abits, (uint32_t)(cbits >> 32),
-                            (uint32_t)cbits};
-  ghash_step(y, lens, h);
-#pragma unroll
-  for (int i = 0; i < 3; ++i) ctr[i] = bswap32(nonce[i]);
-  ctr[3] = bswap32(1u);  // J0 = nonce || 1 (seq 0: the nonce is base_nonce)
-  aes128_encrypt(sbox, rk, ctr, ek);
-  uint32_t tag[4], diff = 0;
-  load_block(ct + body, 16, tag);
-#pragma unroll
-  for (int i = 0; i < 4; ++i) diff |= (bswap32(y[i]) ^ ek[i]) ^ tag[i];  // no early exit
-  ok = diff == 0u && nz != 0u;
-  if (!ok) {
-    for (uint64_t j = 0; j < pt_cap; ++j) pt[j] = 0;
-    status[r] = ST_HPKE_DECRYPT;
-    return;
-  }
-  for (uint64_t o = 0; o < body; o += 16) {  // CTR from counter 2
-    uint32_t d[4];
-    load_block(ct + o, body - o, d);
-    ctr[3] = bswap32((uint32_t)(o >> 4) + 2u);
-    aes128_encrypt(sbox, rk, ctr, ek);
-#pragma unroll
-    for (int j = 0; j < 16; ++j)
-      if (o + j < body) pt[o + j] = (uint8_t)((d[j >> 2] ^ ek[j >> 2]) >> (8 * (j & 3)));
-  }
-  for (uint64_t j = body; j < pt_cap; ++j) pt[j] = 0;
+  hpke_open_lane(sbox, bc, dh + (size_t)r * 8, encs + (size_t)r * 32, PackedBytes{aads + a0, a1 - a0},
+                 cts + c0, c1 - c0 - 16, pt, pt_cap, status + r);
 }
 
 }  // namespace p3g

@@ -18,6 +18,13 @@ Per aggregation job (one AggregationJobInitializeReq):
                                                                                    accumulator.rs:76-122)
   5. encode the AggregationJobResp                                                (aggregator.rs:1811-1848)
 
+hpke="fused": `open` does only step 1's decode and request-level checks, the report times / batch
+slots and one copy of the request into a pooled pinned buffer; `prepare` then makes ONE engine call
+on the driver's own context (prio3gpu_helper_init_request, helper_request.h) that gathers the
+rows, opens and decodes the input shares and runs step 4 from the request in device memory --
+steps 2-3 never touch host memory for the reports the GPU opens -- followed by
+prio3gpu_agg_update_reports and step 5 as in the other modes.
+
 `handle_jobs` pipelines a stream of jobs: while the GPU runs job k (step 4, the ctypes call
 releases the GIL and blocks on the engine's stream), a host worker thread runs steps 1-3 of job
 k + 1 -- the north star's "HPKE open stays on pipelined CPU threads".  Per-report errors keep the
@@ -52,13 +59,29 @@ class _Opened:
     buf: int = -1  # index of the pinned staging buffer holding leader_prep (-1: none)
 
 
-class _PinnedPool:
-    """Pinned host buffers for the leader prep shares of jobs in flight.  A buffer is owned by one
-    opened job from `acquire` until `release` (after its GPU stage), so any number of jobs may be
-    opened ahead of preparation without one overwriting another's rows."""
+@dataclass
+class _OpenedRequest:
+    """hpke="fused": the decoded request, its bytes in a pooled pinned buffer (or where they
+    were, without one) -- everything else happens in `prepare`."""
+    n: int
+    req: object
+    msg: Optional[np.ndarray]
+    status: np.ndarray
+    slots: Optional[np.ndarray]
+    times: np.ndarray
+    buf: int = -1
 
-    def __init__(self, row_bytes: int):
+
+class _PinnedPool:
+    """Pinned host buffers of `row_bytes`-byte rows for jobs in flight: the leader prep shares
+    (one row per report), or in hpke="fused" mode the request itself (row_bytes = 1, one row per
+    byte).  A buffer is owned by one opened job from `acquire` until `release` (after its GPU
+    stage), so any number of jobs may be opened ahead of preparation without one overwriting
+    another's rows.  `min_rows`: the smallest buffer allocated."""
+
+    def __init__(self, row_bytes: int, min_rows: int = 1024):
         self.row_bytes = row_bytes
+        self.min_rows = min_rows
         self._bufs: List[np.ndarray] = []
         self._keep: List[object] = []
         self._busy: List[bool] = []
@@ -73,7 +96,8 @@ class _PinnedPool:
                 if not self._busy[k] and b.shape[0] >= n:
                     self._busy[k] = True
                     return k, b
-            t = torch.empty((max(n, 1024), self.row_bytes), dtype=torch.uint8, pin_memory=True)
+            t = torch.empty((max(n, self.min_rows), self.row_bytes), dtype=torch.uint8,
+                            pin_memory=True)
             self._keep.append(t)
             self._bufs.append(t.numpy())
             self._busy.append(True)
@@ -105,9 +129,12 @@ class HelperAggregateInit:
         (hpke.open_report_shares(gpu=...)), the rest on the host threads.  `open` still runs on
         the pipeline's host worker while the driver thread prepares the previous job, and a
         context serves one thread at a time, so the driver owns a second context on the same
-        device for HPKE."""
-        if hpke not in ("host", "gpu"):
-            raise ValueError('hpke must be "host" or "gpu"')
+        device for HPKE.  "fused": gather, open, decode and preparation are one engine call on
+        `vdaf`'s own context in `prepare` (Prio3Gpu.helper_init_request); `open` only decodes
+        and checks the request and copies it to pinned memory, and there is no second context.
+        Statuses and responses are those of "host" in every mode."""
+        if hpke not in ("host", "gpu", "fused"):
+            raise ValueError('hpke must be "host", "gpu" or "fused"')
         self.hpke_mode = hpke
         self._hpke_ctx = None
         if hpke == "gpu":
@@ -127,6 +154,8 @@ class HelperAggregateInit:
         # SumVec): job k+1 is gathered into one buffer while job k's is copied to the GPU from
         # another; pageable memory would make that copy the slowest step.
         self._pinned = _PinnedPool(vdaf.sizes.prep_share)
+        if hpke == "fused":  # the request's bytes instead
+            self._pinned = _PinnedPool(1, min_rows=1 << 20)
 
     def open(self, req_bytes: bytes) -> _Opened:
         """Steps 1-3 (host only).  Raises InvalidMessage / EmptyAggregation for the request."""
@@ -135,6 +164,8 @@ class HelperAggregateInit:
         C.check_agg_init_req(req)
         if req.n == 0:
             raise EmptyAggregation("aggregation job contains no reports")
+        if self.hpke_mode == "fused":
+            return self._open_request(req)
         k, buf = self._pinned.acquire(req.n)
         try:
             nonces, pub, lps, faults = C.gather_prepare_inits(s, req, lps_out=buf)
@@ -152,19 +183,38 @@ class HelperAggregateInit:
             raise
         return _Opened(req.n, nonces, pub, lps, hin, st, slots, times, k)
 
-    def prepare(self, o: _Opened, agg: AggregateShares) -> bytes:
-        """Steps 4-5 (GPU + encode)."""
+    def _open_request(self, req) -> _OpenedRequest:
+        """hpke="fused": the times / slots and the pinned copy of a decoded, checked request."""
+        times = req.times()
+        slots = None
+        if self.batch_slot_of is not None:
+            slots = np.ascontiguousarray(self.batch_slot_of(times), np.uint32)
+        k, buf = self._pinned.acquire(req.raw.size)
+        msg = None
+        if buf is not None:
+            msg = buf.reshape(-1)[:req.raw.size]
+            np.copyto(msg, req.raw)
+        return _OpenedRequest(req.n, req, msg, np.zeros(req.n, np.uint8), slots, times, k)
+
+    def prepare(self, o, agg: AggregateShares) -> bytes:
+        """Steps 4-5 (GPU + encode); in "fused" mode steps 2-4 in one engine call."""
         try:
             if o.n > self._cap:
                 if self._state is not None:
                     self._state.close()
                 self._cap = max(o.n, 2 * self._cap)
                 self._state = self.vdaf.new_state(1, self._cap)
+            if isinstance(o, _OpenedRequest):
+                msgs, st, nonces = self.vdaf.helper_init_request(
+                    self._state, self.task_id, o.req, self.task_keys, self.global_keys, agg=agg,
+                    batch_slots=o.slots, status=o.status, threads=self.hpke_threads, msg=o.msg)
+                agg.update_reports(nonces, o.times, st, o.slots)
+                return C.encode_agg_job_resp(nonces, msgs, self.vdaf.sizes.prep_msg, st)
             msgs, st = self.vdaf.helper_init(self._state, o.nonces, o.public, o.helper_in,
                                              o.leader_prep, agg=agg, batch_slots=o.slots,
                                              status=o.status)
         finally:
-            self._pinned.release(o.buf)  # helper_init returns after its stream has synchronised
+            self._pinned.release(o.buf)  # the engine call returns after its stream has synchronised
             o.buf = -1
         # Accumulator::update bookkeeping: report-ID checksum + client-timestamp interval
         agg.update_reports(o.nonces, o.times, st, o.slots)
@@ -204,7 +254,7 @@ class HelperAggregateInit:
                             ahead = nxt.result()
                         except BaseException:
                             ahead = None
-                        if isinstance(ahead, _Opened):
+                        if isinstance(ahead, (_Opened, _OpenedRequest)):
                             self._pinned.release(ahead.buf)
                     raise
         return out

@@ -451,6 +451,43 @@ class Prio3Gpu:
                                          agg._h if agg else None), "helper_init")
         return msgs, st
 
+    def helper_init_request(self, state: PrepareState, task_id: bytes, req, task_keys,
+                            global_keys=(), agg: Optional[AggregateShares] = None,
+                            batch_slots=None, status=None, threads: int = 0, msg=None):
+        """Helper aggregate-init straight from a decoded AggregationJobInitializeReq
+        (`janus_amd.codec.AggInitReq`): gather, HPKE open, PlaintextInputShare decode and
+        prio3gpu_helper_init in one call on this context (prio3gpu_helper_init_request), with the
+        statuses and outputs of the staged calls.  `msg`: where the request's bytes are, if not
+        `req.raw` -- a pinned copy (numpy) or an integer device pointer.
+        -> (prep_msgs, status, nonces)."""
+        from . import hpke as H
+        s = self.sizes
+        n = req.n
+        st = np.zeros(n, dtype=np.uint8) if status is None else status
+        assert st.dtype == np.uint8 and st.size == n and st.flags["C_CONTIGUOUS"]
+        msgs = np.zeros((n, s.prep_msg), dtype=np.uint8) if s.prep_msg else None
+        nonces = np.zeros((n, 16), dtype=np.uint8)
+        if n == 0:
+            return msgs, st, nonces
+        tid = np.frombuffer(bytes(task_id), np.uint8).copy()
+        if tid.size != 32:
+            raise ValueError("TaskId is 32 bytes")
+        tk, keep_t = H._keypairs(task_keys)
+        gk, keep_g = H._keypairs(global_keys)
+        slots = None
+        if batch_slots is not None:
+            slots = np.ascontiguousarray(batch_slots, dtype=np.uint32)
+        raw = req.raw if msg is None else msg
+        p_msg = raw if isinstance(raw, int) else _ptr(raw)
+        state.set_input_pitch(0)
+        check(lib().prio3gpu_helper_init_request(
+            self._ctx, state._h, tid.ctypes.data, tk, len(task_keys), gk, len(global_keys),
+            H.ROLE_CLIENT, H.ROLE_HELPER, p_msg, req.raw.size, req.views, n, _ptr(slots),
+            _ptr(nonces), _ptr(msgs), _ptr(st),
+            agg._h if agg else None, threads), "helper_init_request")
+        del keep_t, keep_g
+        return msgs, st, nonces
+
     # -- Client ------------------------------------------------------------------------------------
     def random_size(self) -> int:
         return lib().prio3gpu_random_size(self._ctx)

@@ -310,6 +310,19 @@ extern "C" {
                                                 offsets: *mut u64, status: *mut u8,
                                                 threads: c_int) -> c_int;
 
+    // -- helper aggregate-init from the request's bytes (one call per job, one context) ---------
+    pub fn prio3gpu_helper_init_request(ctx: *mut prio3gpu_ctx, st: *mut prio3gpu_state,
+                                        task_id: *const u8,
+                                        task_keys: *const prio3gpu_hpke_keypair,
+                                        n_task_keys: usize,
+                                        global_keys: *const prio3gpu_hpke_keypair,
+                                        n_global_keys: usize, sender_role: u8,
+                                        recipient_role: u8, msg: *const u8, msg_len: usize,
+                                        views: *const prio3gpu_prepare_init_view, n: usize,
+                                        batch_slots: *const u32, out_nonces: *mut u8,
+                                        out_prep_msgs: *mut u8, status: *mut u8,
+                                        agg: *mut prio3gpu_agg, threads: c_int) -> c_int;
+
     // -- errors and build identity ------------------------------------------------------------
     pub fn prio3gpu_last_error() -> *const c_char;
     pub fn prio3gpu_build_hash() -> *const c_char;
