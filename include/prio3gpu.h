@@ -164,6 +164,13 @@ int prio3gpu_ctx_set_async(prio3gpu_ctx* ctx, int on);
  *   "expand_lds", "jr_lds"  dynamic LDS bytes per k_expand / k_jr block (0 = none): caps those
  *                   kernels' occupancy so another context's kernels fit beside them
  *   "exact_squeeze" test switch: every XOF squeeze takes the exact per-element rejection path
+ *   "hpke_gpu_suites"  the HPKE suites the GPU opens (prio3gpu_hpke_open_batch,
+ *                   prio3gpu_hpke_open_report_shares_gpu, prio3gpu_helper_init_request): 0
+ *                   (default) only DHKEM(X25519, HKDF-SHA256) / HKDF-SHA256 / AES-128-GCM
+ *                   (0x0020 / 1 / 1); 1 every X25519 suite Janus accepts, KDF HKDF-SHA256 /
+ *                   -SHA384 / -SHA512 (1-3) x AEAD AES-128-GCM / AES-256-GCM / ChaCha20-Poly1305
+ *                   (1-3).  P-256 keys are opened on the host either way.  Any other value is
+ *                   PRIO3GPU_E_ARG
  * The engine reads no environment variables.  PRIO3GPU_E_ARG for an unknown name. */
 int prio3gpu_ctx_set_option(prio3gpu_ctx* ctx, const char* name, int64_t value);
 /* Work queued on `ctx` from now on starts only after all work queued on `other` so far. */
@@ -516,9 +523,12 @@ int prio3gpu_hpke_open_report_shares(const uint8_t* task_id, const prio3gpu_hpke
                                      int threads);
 
 /* ---- HPKE open on the GPU (janus_amd/csrc/hpke_gpu.h) ------------------------------------------
- * n opens under ONE keypair, one GPU lane per report, for the suite Janus generates by default:
- * DHKEM(X25519, HKDF-SHA256) / HKDF-SHA256 / AES-128-GCM (0x0020 / 1 / 1); any other suite is
- * PRIO3GPU_E_UNSUPPORTED with nothing launched (use the host functions above).  sk, pk and info
+ * n opens under ONE keypair, one GPU lane per report, for the suites the context opens on the GPU:
+ * by default the one Janus generates, DHKEM(X25519, HKDF-SHA256) / HKDF-SHA256 / AES-128-GCM
+ * (0x0020 / 1 / 1); with the context option "hpke_gpu_suites" = 1 every X25519 suite (0x0020 /
+ * KDF 1-3 / AEAD 1-3: HKDF-SHA256, -SHA384, -SHA512 x AES-128-GCM, AES-256-GCM,
+ * ChaCha20-Poly1305).  Any other suite (P-256 always; the eight wider ones while the option is 0)
+ * is PRIO3GPU_E_UNSUPPORTED with nothing launched (use the host functions above).  sk, pk and info
  * are host memory; every other pointer may be host or device (detected).  Report i has
  * enc = encs[32 i .. 32 i + 32), aad = aads[aad_offsets[i] .. aad_offsets[i+1]), ciphertext ||
  * tag = cts[ct_offsets[i] .. ct_offsets[i+1]) and its plaintext goes to pts[pt_offsets[i] ..
@@ -535,10 +545,11 @@ int prio3gpu_hpke_open_batch(prio3gpu_ctx* ctx, uint16_t kem_id, uint16_t kdf_id
                              const uint64_t* ct_offsets, uint8_t* pts, const uint64_t* pt_offsets,
                              uint8_t* status);
 /* prio3gpu_hpke_open_report_shares with the GPU opening every report whose first-choice key (task
- * key by config id, else global key) is of the suite above, one batch per key: same arguments,
- * offsets, statuses and key-selection order.  Reports whose first choice is another suite (P-256,
- * SHA-384/512, AES-256, ChaCha20), and the global-key second trial after a failed task-key open,
- * run on the host path on `threads` threads.  The plaintext slot of a report that ends with a
+ * key by config id, else global key) is of a suite above (as the context's "hpke_gpu_suites" option
+ * selects), one batch per key: same arguments, offsets, statuses and key-selection order.  Reports
+ * whose first choice is another suite (P-256; with the option at 0 also SHA-384/512, AES-256,
+ * ChaCha20), and the global-key second trial after a failed task-key open, run on the host path
+ * on `threads` threads.  The plaintext slot of a report that ends with a
  * non-zero status is unspecified in both functions.  All pointers are host memory. */
 int prio3gpu_hpke_open_report_shares_gpu(prio3gpu_ctx* ctx, const uint8_t* task_id,
                                          const prio3gpu_hpke_keypair* task_keys, size_t n_task_keys,
@@ -570,7 +581,8 @@ int prio3gpu_hpke_open_report_shares_gpu(prio3gpu_ctx* ctx, const uint8_t* task_
  *   out_nonces     n x 16 report IDs (may be NULL); out_prep_msgs n x prep_msg (may be NULL); host
  *                  or device memory.  batch_slots / agg as in prio3gpu_helper_init.
  * Reports whose first-choice key (task key by config id, else global key) is X25519 / HKDF-SHA256
- * / AES-128-GCM are opened and decoded on the GPU, one kernel pair per key.  The host path
+ * / AES-128-GCM -- or, with the context option "hpke_gpu_suites" = 1, any X25519 suite (KDF 1-3 x
+ * AEAD 1-3) -- are opened and decoded on the GPU, one kernel pair per key.  The host path
  * (prio3gpu_hpke_open_report_shares + prio3gpu_decode_plaintext_input_shares on `threads`
  * threads) takes, inside the call, the reports whose first choice is another suite or a malformed
  * key, the global-key second trial after a failed task-key open, and the plaintexts whose

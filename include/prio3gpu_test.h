@@ -47,6 +47,15 @@ int prio3gpu_test_hpke_set_ifma(int on);
 int prio3gpu_test_x25519_gpu(prio3gpu_ctx* ctx, const uint8_t* sk, const uint8_t* points, size_t n,
                              uint8_t* out);
 
+/* TEST ONLY.  The device Poly1305 (janus_amd/csrc/hpke_prims.h: poly1305_mac, RFC 8439 §2.5) alone,
+ * one lane per message: tags[16 i .. 16 i + 16) is the MAC of msgs[msg_offsets[i] ..
+ * msg_offsets[i + 1]) under keys[32 i .. 32 i + 32) (r || s; r is clamped inside).  The HPKE-level
+ * calls derive r from the key schedule, so only this hook can feed the final reduction the
+ * accumulators p - 1, p and 2^130 - 2.  keys n x 32, msg_offsets n + 1 (ascending), tags n x 16;
+ * all host memory.  n == 0 returns 0 and launches nothing. */
+int prio3gpu_test_poly1305_gpu(prio3gpu_ctx* ctx, const uint8_t* keys, const uint8_t* msgs,
+                               const uint64_t* msg_offsets, size_t n, uint8_t* tags);
+
 /* TEST ONLY.  One field primitive over caller-supplied operands, one lane per tuple: the device
  * functions the product kernels call (Field128Ops / Field64Ops, the generated carry chains and
  * fused Montgomery programs, the lazy dot product, the inverses), run alone so that tests can

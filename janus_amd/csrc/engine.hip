@@ -219,6 +219,9 @@ struct prio3gpu_ctx {
   bool query_overlap = true;
   bool wires_mfma = true;    // "wires_mfma": SumVec chunk > 64 wire pass on the matrix cores
   bool wires_cols = true;    // "wires_cols": chunk <= 64 lane-per-column wire pass
+  // "hpke_gpu_suites": which HPKE suites the GPU opens (hpke_gpu_suite): 0 only X25519 /
+  // HKDF-SHA256 / AES-128-GCM, 1 every X25519 suite (KDF 1-3 x AEAD 1-3)
+  bool hpke_gpu_suites = false;
   size_t expand_lds = 0;     // "expand_lds": dynamic LDS per k_expand block (occupancy cap)
   size_t jr_lds = 0;         // "jr_lds": dynamic LDS per k_jr block (occupancy cap)
   uint32_t cus = 0;          // compute units of the device
@@ -1640,6 +1643,12 @@ int prio3gpu_ctx_set_option(prio3gpu_ctx* c, const char* name, int64_t value) {
     c->wires_mfma = on;
   } else if (k == "wires_cols") {
     c->wires_cols = on;
+  } else if (k == "hpke_gpu_suites") {
+    if (value < 0 || value > 1) {
+      set_err("option hpke_gpu_suites: %lld is not 0 or 1", (long long)value);
+      return PRIO3GPU_E_ARG;
+    }
+    c->hpke_gpu_suites = on;
 
   } else if (k == "expand_lds" || k == "jr_lds") {
     if (value < 0 || value > 160 * 1024) {
@@ -2484,13 +2493,34 @@ int launch_req_gather(prio3gpu_ctx* c, size_t n, const uint8_t* d_msg, size_t ms
   return 0;
 }
 
-int hpke_open_batch_impl(prio3gpu_ctx* c, const uint8_t* sk, const uint8_t* pk, const uint8_t* info,
-                         size_t info_len, size_t n, const uint8_t* encs, const uint8_t* aads,
-                         const uint64_t* aad_offsets, const uint8_t* cts,
-                         const uint64_t* ct_offsets, uint8_t* pts, const uint64_t* pt_offsets,
-                         uint8_t* status) {
+// The suites the GPU opens on this context: DHKEM(X25519, HKDF-SHA256) / HKDF-SHA256 /
+// AES-128-GCM always; with the "hpke_gpu_suites" option every X25519 suite Janus accepts.
+bool hpke_gpu_suite(const prio3gpu_ctx* c, uint16_t kem, uint16_t kdf, uint16_t aead) {
+  if (kem != 0x0020) return false;
+  if (kdf == 1 && aead == 1) return true;
+  return c->hpke_gpu_suites && kdf >= 1 && kdf <= 3 && aead >= 1 && aead <= 3;
+}
+
+// f(KDF, AEAD) with the suite of bc as compile-time constants (one kernel instantiation each).
+template <class F>
+void hpke_suite_dispatch(const HpkeBatchConsts& bc, F&& f) {
+  auto with_aead = [&](auto kdf) {
+    if (bc.aead_id == 1) f(kdf, std::integral_constant<int, 1>{});
+    else if (bc.aead_id == 2) f(kdf, std::integral_constant<int, 2>{});
+    else f(kdf, std::integral_constant<int, 3>{});
+  };
+  if (bc.kdf_id == 1) with_aead(std::integral_constant<int, 1>{});
+  else if (bc.kdf_id == 2) with_aead(std::integral_constant<int, 2>{});
+  else with_aead(std::integral_constant<int, 3>{});
+}
+
+int hpke_open_batch_impl(prio3gpu_ctx* c, uint16_t kdf_id, uint16_t aead_id, const uint8_t* sk,
+                         const uint8_t* pk, const uint8_t* info, size_t info_len, size_t n,
+                         const uint8_t* encs, const uint8_t* aads, const uint64_t* aad_offsets,
+                         const uint8_t* cts, const uint64_t* ct_offsets, uint8_t* pts,
+                         const uint64_t* pt_offsets, uint8_t* status) {
   HpkeBatchConsts bc;
-  if (!hpke_batch_consts(pk, info, info_len, &bc)) {
+  if (!hpke_batch_consts(kdf_id, aead_id, pk, info, info_len, &bc)) {
     set_err("HPKE primitives unavailable");
     return PRIO3GPU_E_UNSUPPORTED;
   }
@@ -2526,11 +2556,13 @@ int hpke_open_batch_impl(prio3gpu_ctx* c, const uint8_t* sk, const uint8_t* pk, 
     CHK(launch_x25519(c, sk, n, d_enc, d_dh));
     {
       PROF(KID_HPKE_OPEN);
-      hipLaunchKernelGGL(k_hpke_open, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, c->stream,
-                         (uint32_t)n, bc, d_dh, d_enc, d_aad,
-                         reinterpret_cast<const uint64_t*>(d_aoff), aad_total, d_ct,
-                         reinterpret_cast<const uint64_t*>(d_coff), ct_total, d_pt,
-                         reinterpret_cast<const uint64_t*>(d_poff), pt_total, d_st);
+      hpke_suite_dispatch(bc, [&](auto kdf, auto aead) {
+        hipLaunchKernelGGL((k_hpke_open<decltype(kdf)::value, decltype(aead)::value>), dim3((unsigned)((n + 255) / 256)),
+                           dim3(256), 0, c->stream, (uint32_t)n, bc, d_dh, d_enc, d_aad,
+                           reinterpret_cast<const uint64_t*>(d_aoff), aad_total, d_ct,
+                           reinterpret_cast<const uint64_t*>(d_coff), ct_total, d_pt,
+                           reinterpret_cast<const uint64_t*>(d_poff), pt_total, d_st);
+      });
     }
     HIPCHK(hipGetLastError());
     return 0;
@@ -2552,10 +2584,6 @@ int hpke_open_batch_impl(prio3gpu_ctx* c, const uint8_t* sk, const uint8_t* pk, 
   return finish_call(c, {encs, aads, aad_offsets, cts, ct_offsets, pts, pt_offsets, status});
 }
 
-bool hpke_gpu_suite(uint16_t kem, uint16_t kdf, uint16_t aead) {
-  return kem == 0x0020 && kdf == 1 && aead == 1;
-}
-
 }  // namespace
 
 extern "C" {
@@ -2570,7 +2598,7 @@ int prio3gpu_hpke_open_batch(prio3gpu_ctx* c, uint16_t kem_id, uint16_t kdf_id, 
     set_err("null context");
     return PRIO3GPU_E_ARG;
   }
-  if (!hpke_gpu_suite(kem_id, kdf_id, aead_id)) {
+  if (!hpke_gpu_suite(c, kem_id, kdf_id, aead_id)) {
     set_err("HPKE suite 0x%04x/%u/%u is not opened on the GPU", kem_id, kdf_id, aead_id);
     return PRIO3GPU_E_UNSUPPORTED;
   }
@@ -2583,8 +2611,8 @@ int prio3gpu_hpke_open_batch(prio3gpu_ctx* c, uint16_t kem_id, uint16_t kdf_id, 
     set_err("HPKE open: null argument");
     return PRIO3GPU_E_ARG;
   }
-  return hpke_open_batch_impl(c, sk, pk, info, info_len, n, encs, aads, aad_offsets, cts,
-                              ct_offsets, pts, pt_offsets, status);
+  return hpke_open_batch_impl(c, kdf_id, aead_id, sk, pk, info, info_len, n, encs, aads,
+                              aad_offsets, cts, ct_offsets, pts, pt_offsets, status);
 }
 
 int prio3gpu_hpke_open_report_shares_gpu(
@@ -2611,9 +2639,9 @@ int prio3gpu_hpke_open_report_shares_gpu(
     return static_cast<const prio3gpu_hpke_keypair*>(nullptr);
   };
   // The first-choice key of every report (task key, else global key, by config id).  Reports
-  // whose first choice is an X25519 / HKDF-SHA256 / AES-128-GCM key go to the GPU, one batch per
-  // key; everything else (other suites, malformed keys or encapsulated keys, unknown ids) is the
-  // host path's, untouched.
+  // whose first choice is a key of a suite the GPU opens on this context (hpke_gpu_suite) go to
+  // the GPU, one batch per key; everything else (other suites, malformed keys or encapsulated
+  // keys, unknown ids) is the host path's, untouched.
   std::vector<const prio3gpu_hpke_keypair*> first(n, nullptr), groups;
   std::vector<uint8_t> st_host(status, status + n), st_retry(n, 1);
   for (size_t i = 0; i < n; ++i) {
@@ -2621,7 +2649,7 @@ int prio3gpu_hpke_open_report_shares_gpu(
     const prio3gpu_hpke_keypair* tk = find(task_keys, n_task_keys, views[i].hpke_config_id);
     const prio3gpu_hpke_keypair* kp =
         tk ? tk : find(global_keys, n_global_keys, views[i].hpke_config_id);
-    if (!kp || !hpke_gpu_suite(kp->kem_id, kp->kdf_id, kp->aead_id) || !kp->private_key ||
+    if (!kp || !hpke_gpu_suite(c, kp->kem_id, kp->kdf_id, kp->aead_id) || !kp->private_key ||
         kp->private_key_len != 32 || !kp->public_key || kp->public_key_len != 32 ||
         views[i].enc_len != 32 || views[i].payload_len < 16)
       continue;
@@ -2663,9 +2691,9 @@ int prio3gpu_hpke_open_report_shares_gpu(
     });
     pts.assign(std::max<size_t>(poff.back(), 1), 0);
     st.assign(m, 0);
-    CHK(hpke_open_batch_impl(c, kp->private_key, kp->public_key, info, sizeof info, m, encs.data(),
-                             aads.data(), aoff.data(), cts.data(), coff.data(), pts.data(),
-                             poff.data(), st.data()));
+    CHK(hpke_open_batch_impl(c, kp->kdf_id, kp->aead_id, kp->private_key, kp->public_key, info,
+                             sizeof info, m, encs.data(), aads.data(), aoff.data(), cts.data(),
+                             coff.data(), pts.data(), poff.data(), st.data()));
     for (size_t j = 0; j < m; ++j) {
       const size_t i = idx[j];
       if (st[j] == 0) {
@@ -2739,9 +2767,9 @@ int prio3gpu_helper_init_request(
     return static_cast<const prio3gpu_hpke_keypair*>(nullptr);
   };
   // Key selection as in prio3gpu_hpke_open_report_shares_gpu: the first-choice key of every report
-  // (task key, else global key, by config id).  Reports whose first choice is an X25519 /
-  // HKDF-SHA256 / AES-128-GCM key form one group per key for the GPU; an unknown id is status 3
-  // here; every other key is the host path's (REQ_HOST in the device status image).
+  // (task key, else global key, by config id).  Reports whose first choice is a key of a suite the
+  // GPU opens on this context (hpke_gpu_suite) form one group per key for the GPU; an unknown id is
+  // status 3 here; every other key is the host path's (REQ_HOST in the device status image).
   std::vector<const prio3gpu_hpke_keypair*> groups;
   std::vector<int32_t> grp(n, -1);
   std::vector<uint8_t> dst(status, status + n);
@@ -2756,7 +2784,7 @@ int prio3gpu_helper_init_request(
       dst[i] = PRIO3GPU_HPKE_UNKNOWN_CONFIG_ID;
       continue;
     }
-    if (!hpke_gpu_suite(kp->kem_id, kp->kdf_id, kp->aead_id) || !kp->private_key ||
+    if (!hpke_gpu_suite(c, kp->kem_id, kp->kdf_id, kp->aead_id) || !kp->private_key ||
         kp->private_key_len != 32 || !kp->public_key || kp->public_key_len != 32) {
       dst[i] = REQ_HOST;
       continue;
@@ -2776,7 +2804,8 @@ int prio3gpu_helper_init_request(
                             'h', 'a', 'r', 'e', sender_role, recipient_role};  // hpke.rs:52-77
   std::vector<HpkeBatchConsts> bcs(groups.size());
   for (size_t k = 0; k < groups.size(); ++k)
-    if (!hpke_batch_consts(groups[k]->public_key, info, sizeof info, &bcs[k])) {
+    if (!hpke_batch_consts(groups[k]->kdf_id, groups[k]->aead_id, groups[k]->public_key, info,
+                           sizeof info, &bcs[k])) {
       set_err("HPKE primitives unavailable");
       return PRIO3GPU_E_UNSUPPORTED;
     }
@@ -2827,9 +2856,11 @@ int prio3gpu_helper_init_request(
       CHK(launch_x25519_idx(c, groups[k]->private_key, m, d_idx + gbeg[k], d_msg, d_views, d_dh));
       {
         PROF(KID_HPKE_OPEN_REQ);
-        hipLaunchKernelGGL(k_hpke_open_req, dim3((unsigned)((m + 255) / 256)), dim3(256), 0,
-                           c->stream, (uint32_t)m, bcs[k], tid, d_idx + gbeg[k], d_dh, d_msg,
-                           d_views, d_pts, d_poff, d_status);
+        hpke_suite_dispatch(bcs[k], [&](auto kdf, auto aead) {
+          hipLaunchKernelGGL((k_hpke_open_req<decltype(kdf)::value, decltype(aead)::value>), dim3((unsigned)((m + 255) / 256)),
+                             dim3(256), 0, c->stream, (uint32_t)m, bcs[k], tid, d_idx + gbeg[k],
+                             d_dh, d_msg, d_views, d_pts, d_poff, d_status);
+        });
       }
       HIPCHK(hipGetLastError());
     }
@@ -2993,6 +3024,38 @@ int prio3gpu_test_x25519_gpu(prio3gpu_ctx* c, const uint8_t* sk, const uint8_t* 
     HIPCHK(hipMemcpyAsync(out, d_out, n * 32, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(hipMemsetAsync(d_out, 0, n * 32, c->stream));
   }
+  HIPCHK(hipStreamSynchronize(c->stream));
+  return 0;
+}
+
+int prio3gpu_test_poly1305_gpu(prio3gpu_ctx* c, const uint8_t* keys, const uint8_t* msgs,
+                               const uint64_t* msg_offsets, size_t n, uint8_t* tags) {
+  if (!c || (n && (!keys || !msg_offsets || !tags)) || n > 0x7FFFFFFFu) {
+    set_err("null argument");
+    return PRIO3GPU_E_ARG;
+  }
+  if (n == 0) return 0;
+  const uint64_t total = msg_offsets[n];
+  for (size_t i = 0; i < n; ++i)
+    if (msg_offsets[i] > msg_offsets[i + 1]) {
+      set_err("message offsets out of order");
+      return PRIO3GPU_E_ARG;
+    }
+  if (total && !msgs) {
+    set_err("null argument");
+    return PRIO3GPU_E_ARG;
+  }
+  HIPCHK(hipSetDevice(c->device));
+  const uint8_t *d_keys, *d_msgs, *d_off;
+  CHK(stage_in(c, c->hpke[0], keys, n * 32, &d_keys, kHpkeMinStage));
+  CHK(stage_in(c, c->hpke[1], msgs, total, &d_msgs, kHpkeMinStage));
+  CHK(stage_in(c, c->hpke[2], msg_offsets, (n + 1) * 8, &d_off, kHpkeMinStage));
+  CHK(c->hpke[5].ensure(n * 16));
+  hipLaunchKernelGGL(k_test_poly1305, dim3((unsigned)((n + 63) / 64)), dim3(64), 0, c->stream,
+                     (uint32_t)n, d_keys, d_msgs, reinterpret_cast<const uint64_t*>(d_off),
+                     c->hpke[5].u8());
+  HIPCHK(hipGetLastError());
+  HIPCHK(hipMemcpyAsync(tags, c->hpke[5].u8(), n * 16, hipMemcpyDeviceToHost, c->stream));
   HIPCHK(hipStreamSynchronize(c->stream));
   return 0;
 }

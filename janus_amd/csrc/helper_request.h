@@ -5,8 +5,9 @@
 // the host has checked against the message length.
 //   k_req_gather        nonces, public shares, leader prep shares -> rows; faults[i]
 //   k_x25519_idx        k_x25519 over a key group (a list of report indices), enc read in place
-//   k_hpke_open_req     hpke_open_lane over a key group: enc and ciphertext in place, the
-//                       InputShareAad assembled from its five pieces, never materialised
+//   k_hpke_open_req     hpke_open_lane (of the group's suite) over a key group: enc and ciphertext
+//                       in place, the InputShareAad assembled from its five pieces, never
+//                       materialised
 //   k_decode_plaintext_input_shares   PlaintextInputShare -> helper input share row, then faults
 //   k_req_scatter       host-fallback reports' rows and statuses into place
 // Included by engine.hip after hpke_gpu.h and include/prio3gpu.h.
@@ -97,7 +98,8 @@ struct ReqTaskId {  // the 32-byte TaskId as block words (byte j at bits 8 (j & 
   uint32_t w[8];
 };
 
-// InputShareAad (messages/src/lib.rs:1790-1827; hpke.cpp's open_i) as a GHASH byte source:
+// InputShareAad (messages/src/lib.rs:1790-1827; hpke.cpp's open_i) as a GHASH / Poly1305 byte
+// source:
 //   task_id[32] | report_id[16] | time u64 BE | public_share_len u32 BE | public share
 // Blocks 0, 1: the task id; block 2: the report ID; block 3: time, length and the first four
 // public-share bytes; block k >= 4: public-share bytes 16 k - 60 ..., none on a block boundary.
@@ -129,13 +131,19 @@ struct ReqAad {
 // One lane per report of a key group: hpke_open_lane with enc, ciphertext and AAD read where the
 // request has them; report r's plaintext goes to pts[pt_off[r] .. pt_off[r + 1]).  An enc_len
 // other than 32, a payload shorter than the tag or longer than its slot: status 4, nothing read.
+// (KDF, AEAD) is the group's suite, as for k_hpke_open.
+template <int KDF, int AEAD>
 __global__ void __launch_bounds__(256) k_hpke_open_req(
     uint32_t m, HpkeBatchConsts bc, ReqTaskId tid, const uint32_t* idx, const uint32_t* dh,
     const uint8_t* msg, const ReqView* views, uint8_t* pts, const uint64_t* pt_off,
     uint8_t* status) {
-  __shared__ uint8_t sbox[256];
-  aes_sbox_init(sbox);
-  __syncthreads();
+  const uint8_t* sbox = nullptr;
+  if constexpr (AEAD != 3) {
+    __shared__ uint8_t sbox_lds[256];
+    aes_sbox_init(sbox_lds);
+    __syncthreads();
+    sbox = sbox_lds;
+  }
   const uint32_t j = blockIdx.x * blockDim.x + threadIdx.x;
   if (j >= m) return;
   const uint32_t r = idx[j];
@@ -150,8 +158,8 @@ __global__ void __launch_bounds__(256) k_hpke_open_req(
   }
   const ReqAad aad{tid, msg + v.report_id_off, v.time, v.public_share_len,
                    msg + v.public_share_off};
-  hpke_open_lane(sbox, bc, dh + (size_t)r * 8, msg + v.enc_off, aad, msg + v.payload_off,
-                 (uint64_t)clen - 16, pt, pt_cap, status + r);
+  hpke_open_lane<KDF, AEAD>(sbox, bc, dh + (size_t)r * 8, msg + v.enc_off, aad,
+                            msg + v.payload_off, (uint64_t)clen - 16, pt, pt_cap, status + r);
 }
 
 // ---- decode ------------------------------------------------------------------------------------

@@ -784,27 +784,29 @@ void parallel_for(size_t n, int threads, F&& f) {
 
 }  // namespace
 
-// The batch-shared inputs of the GPU open (hpke_gpu.h): psk_id_hash and info_hash of the key
-// schedule, and the HMAC pad states of the empty salt, as big-endian words.
-bool p3g::hpke_batch_consts(const uint8_t* pk, const uint8_t* info, size_t info_len,
-                            HpkeBatchConsts* out) {
+// The batch-shared inputs of the GPU open (hpke_gpu.h): psk_id_hash and info_hash of the suite's
+// key schedule, and the HMAC-SHA256 pad states of the empty salt (the KEM's), as big-endian words.
+bool p3g::hpke_batch_consts(uint16_t kdf_id, uint16_t aead_id, const uint8_t* pk,
+                            const uint8_t* info, size_t info_len, HpkeBatchConsts* out) {
   Suite s;
-  if (!suite_of(KEM_X25519, KDF_SHA256, AEAD_AES128GCM, &s)) return false;
-  const EVP_MD* md = algs().md[KDF_SHA256];
+  if (!suite_of(KEM_X25519, kdf_id, aead_id, &s)) return false;
+  const EVP_MD* md = algs().md[s.kdf];
   Bytes sid;
   sid.add("HPKE").u16(s.kem).u16(s.kdf).u16(s.aead);
-  uint8_t psk_id_hash[kMaxHash], info_hash[kMaxHash];
+  uint8_t psk_id_hash[kMaxHash] = {0}, info_hash[kMaxHash] = {0};
   if (!labeled_extract(md, sid, nullptr, 0, "psk_id_hash", nullptr, 0, psk_id_hash) ||
       !labeled_extract(md, sid, nullptr, 0, "info_hash", info, info_len, info_hash))
     return false;
-  auto be = [](uint32_t* w, const uint8_t* b) {
-    for (int i = 0; i < 8; ++i)
+  auto be = [](uint32_t* w, const uint8_t* b, int nwords) {
+    for (int i = 0; i < nwords; ++i)
       w[i] = uint32_t(b[4 * i]) << 24 | uint32_t(b[4 * i + 1]) << 16 | uint32_t(b[4 * i + 2]) << 8 |
              b[4 * i + 3];
   };
-  be(out->pk, pk);
-  be(out->psk_id_hash, psk_id_hash);
-  be(out->info_hash, info_hash);
+  memset(out, 0, sizeof *out);
+  out->kdf_id = s.kdf, out->aead_id = s.aead;
+  be(out->pk, pk, 8);
+  be(out->psk_id_hash, psk_id_hash, int(s.nh / 4));
+  be(out->info_hash, info_hash, int(s.nh / 4));
   uint8_t pad[64];
   SHA256_CTX c;
   memset(pad, 0x36, sizeof pad);  // the empty salt is a zero key

@@ -1,13 +1,18 @@
-// Batched HPKE open on the GPU for DHKEM(X25519, HKDF-SHA256) / HKDF-SHA256 / AES-128-GCM
-// (0x0020 / 1 / 1), RFC 9180 base mode, single shot: the suite Janus generates by default
-// (core/src/hpke.rs:204-231) and the helper opens once per report (aggregator.rs:1634-1700).
-// One lane per report, every report of a launch under ONE private key:
-//   k_x25519     dh = X25519(skR, enc)                       RFC 7748 §5
-//   k_hpke_open  shared_secret, key schedule, AES-128-GCM    RFC 9180 §4.1, §5.1; NIST SP 800-38D
+// Batched HPKE open on the GPU for DHKEM(X25519, HKDF-SHA256) with every KDF and AEAD Janus
+// accepts, RFC 9180 base mode, single shot: 0x0020 / 1 / 1 is the suite Janus generates by default
+// (core/src/hpke.rs:204-231) and the helper opens once per report (aggregator.rs:1634-1700); the
+// other eight (KDF HKDF-SHA256 / -SHA384 / -SHA512 x AEAD AES-128-GCM / AES-256-GCM /
+// ChaCha20-Poly1305) are opened when the context's "hpke_gpu_suites" option is on.
+// One lane per report, every report of a launch under ONE private key, hence one suite:
+//   k_x25519                dh = X25519(skR, enc)                     RFC 7748 §5
+//   k_hpke_open<KDF, AEAD>  shared_secret, key schedule, the AEAD     RFC 9180 §4.1, §5.1;
+//                                                     NIST SP 800-38D (GCM); RFC 8439 (ChaCha20)
 // Each kernel is a thin shell around a per-lane device function (x25519_lane, hpke_open_lane over
-// a GHASH byte source) that helper_request.h's kernels call too, with the request read in place.
+// a byte source for the AAD) that helper_request.h's kernels call too, with the request read in
+// place.  SHA-512, ChaCha20 and Poly1305 are hpke_prims.h's (free of HIP, tested on the CPU).
 // Included by engine.hip after prio3_kernels.h (SHA-256 is sha256_compress from there).
 #pragma once
+#include "hpke_prims.h"
 #include "hpke_shared.h"
 
 namespace p3g {
@@ -345,19 +350,23 @@ DEVI void msg_kem_prefix(uint32_t* w, int off) {
   msg_str(w, off + 7, "KEM");
   msg_byte(w, off + 11, 0x20u);
 }
-// "HPKE-v1" || suite_id("HPKE" || 0x0020 || 0x0001 || 0x0001) at off (17 bytes)
+// "HPKE-v1" || suite_id("HPKE" || 0x0020 || 0x0001 || aead) at off (17 bytes)
+template <int AEAD>
 DEVI void msg_hpke_prefix(uint32_t* w, int off) {
   msg_str(w, off, "HPKE-v1");
   msg_str(w, off + 7, "HPKE");
   msg_byte(w, off + 12, 0x20u);
   msg_byte(w, off + 14, 0x01u);
-  msg_byte(w, off + 16, 0x01u);
+  msg_byte(w, off + 16, (uint32_t)AEAD);
 }
 
-// (dh, enc) -> AES-128 key (4 BE words) and base nonce (3 BE words): ExtractAndExpand of the
-// DHKEM (RFC 9180 §4.1) and KeySchedule(mode_base) (§5.1).  19 SHA-256 compressions.
+// (dh, enc) -> the AEAD key (Nk / 4 BE words) and base nonce (3 BE words): ExtractAndExpand of
+// the DHKEM (RFC 9180 §4.1; HKDF-SHA256 for every suite) and KeySchedule(mode_base) (§5.1) under
+// the suite's KDF.  19 SHA-256 compressions for KDF 1; 9 and 12 SHA-512 compressions otherwise.
+template <int KDF, int AEAD>
 DEVI void hpke_key_nonce(const HpkeBatchConsts& bc, const uint32_t dh[8], const uint32_t enc[8],
-                         uint32_t key[4], uint32_t nonce[3]) {
+                         uint32_t* key, uint32_t nonce[3]) {
+  constexpr int NK = hpke_aead_nk(AEAD);
   uint32_t w[32], ist[8], ost[8], prk[8], ss[8], secret[8], t[8];
   // eae_prk = LabeledExtract("", "eae_prk", dh)
 #pragma unroll
@@ -379,21 +388,26 @@ DEVI void hpke_key_nonce(const HpkeBatchConsts& bc, const uint32_t dh[8], const 
   msg_byte(w, 91, 1u);
   msg_pad(w, 92, 2);
   hmac_finish<2>(ist, ost, w, ss);
+  if constexpr (KDF != 1) {
+    uint64_t secret64[8];
+    hpke_kdf512_key_nonce<KDF, AEAD>(ss, bc.psk_id_hash, bc.info_hash, secret64, key, nonce);
+    return;
+  }
   // secret = LabeledExtract(shared_secret, "secret", psk = "")
   hmac_pads(ss, ist, ost);
 #pragma unroll
   for (int i = 0; i < 16; ++i) w[i] = 0;
-  msg_hpke_prefix(w, 0);
+  msg_hpke_prefix<AEAD>(w, 0);
   msg_str(w, 17, "secret");
   msg_pad(w, 23, 1);
   hmac_finish<1>(ist, ost, w, secret);
-  // key = LabeledExpand(secret, "key", key_schedule_context, 16);  context = mode 0 ||
+  // key = LabeledExpand(secret, "key", key_schedule_context, Nk);  context = mode 0 ||
   // psk_id_hash || info_hash
   hmac_pads(secret, ist, ost);
 #pragma unroll
   for (int i = 0; i < 32; ++i) w[i] = 0;
-  msg_byte(w, 1, 16u);
-  msg_hpke_prefix(w, 2);
+  msg_byte(w, 1, (uint32_t)NK);
+  msg_hpke_prefix<AEAD>(w, 2);
   msg_str(w, 19, "key");
   msg_words8(w, 23, bc.psk_id_hash);
   msg_words8(w, 55, bc.info_hash);
@@ -401,12 +415,12 @@ DEVI void hpke_key_nonce(const HpkeBatchConsts& bc, const uint32_t dh[8], const 
   msg_pad(w, 88, 2);
   hmac_finish<2>(ist, ost, w, t);
 #pragma unroll
-  for (int i = 0; i < 4; ++i) key[i] = t[i];
+  for (int i = 0; i < NK / 4; ++i) key[i] = t[i];
   // base_nonce = LabeledExpand(secret, "base_nonce", key_schedule_context, 12)
 #pragma unroll
   for (int i = 0; i < 32; ++i) w[i] = 0;
   msg_byte(w, 1, 12u);
-  msg_hpke_prefix(w, 2);
+  msg_hpke_prefix<AEAD>(w, 2);
   msg_str(w, 19, "base_nonce");
   msg_words8(w, 30, bc.psk_id_hash);
   msg_words8(w, 62, bc.info_hash);
@@ -418,8 +432,9 @@ DEVI void hpke_key_nonce(const HpkeBatchConsts& bc, const uint32_t dh[8], const 
 }
 
 // ------------------------------------------------------------------------------------------------
-// AES-128 (FIPS 197) with the S-box in LDS (computed by the block: inverse in GF(2^8) + affine
-// map), and GHASH bit-serial (SP 800-38D §6.3): X25519 dominates the open, so the simplest forms.
+// AES-128 / AES-256 (FIPS 197; NK = 4 / 8 key words, NK + 6 rounds) with the S-box in LDS (computed
+// by the block: inverse in GF(2^8) + affine map), and GHASH bit-serial (SP 800-38D §6.3): X25519
+// dominates the open, so the simplest forms.
 // A 16-byte block is four words, byte j at bits 8 (j & 3) of word j >> 2.
 // ------------------------------------------------------------------------------------------------
 DEVI uint32_t gf8_mul(uint32_t a, uint32_t b) {
@@ -454,28 +469,33 @@ DEVI uint32_t aes_sub_word(const uint8_t* sbox, uint32_t x) {
          ((uint32_t)sbox[(x >> 16) & 0xffu] << 16) | ((uint32_t)sbox[x >> 24] << 24);
 }
 
-DEVI void aes128_expand(const uint8_t* sbox, const uint32_t key_be[4], uint32_t rk[44]) {
+template <int NK>
+DEVI void aes_expand(const uint8_t* sbox, const uint32_t* key_be, uint32_t* rk) {  // 4 (NK + 7)
 #pragma unroll
-  for (int i = 0; i < 4; ++i) rk[i] = bswap32(key_be[i]);
+  for (int i = 0; i < NK; ++i) rk[i] = bswap32(key_be[i]);
   uint32_t rcon = 1u;
 #pragma unroll
-  for (int i = 4; i < 44; ++i) {
+  for (int i = NK; i < 4 * (NK + 7); ++i) {
     uint32_t t = rk[i - 1];
-    if ((i & 3) == 0) {
+    if (i % NK == 0) {
       t = aes_sub_word(sbox, rotr32(t, 8)) ^ rcon;
       rcon = ((rcon << 1) ^ ((0u - (rcon >> 7)) & 0x11bu)) & 0xffu;
+    } else if (NK > 6 && i % NK == 4) {
+      t = aes_sub_word(sbox, t);
     }
-    rk[i] = rk[i - 4] ^ t;
+    rk[i] = rk[i - NK] ^ t;
   }
 }
 
-DEVI void aes128_encrypt(const uint8_t* sbox, const uint32_t rk[44], const uint32_t in[4],
-                         uint32_t out[4]) {
+template <int NK>
+DEVI void aes_encrypt(const uint8_t* sbox, const uint32_t* rk, const uint32_t in[4],
+                      uint32_t out[4]) {
+  constexpr int NR = NK + 6;
   uint32_t s[4];
 #pragma unroll
   for (int c = 0; c < 4; ++c) s[c] = in[c] ^ rk[c];
 #pragma unroll
-  for (int rnd = 1; rnd <= 10; ++rnd) {
+  for (int rnd = 1; rnd <= NR; ++rnd) {
     uint32_t t[4];
 #pragma unroll
     for (int c = 0; c < 4; ++c) {  // SubBytes + ShiftRows
@@ -486,7 +506,7 @@ DEVI void aes128_encrypt(const uint8_t* sbox, const uint32_t rk[44], const uint3
 #pragma unroll
     for (int c = 0; c < 4; ++c) {
       uint32_t x = t[c];
-      if (rnd < 10) {  // MixColumns: 2 b_r + 3 b_(r+1) + b_(r+2) + b_(r+3), bytewise in the word
+      if (rnd < NR) {  // MixColumns: 2 b_r + 3 b_(r+1) + b_(r+2) + b_(r+3), bytewise in the word
         const uint32_t x2 = ((x & 0x7f7f7f7fu) << 1) ^ (((x >> 7) & 0x01010101u) * 0x1bu);
         x = x2 ^ rotr32(x ^ x2, 8) ^ rotr32(x, 16) ^ rotr32(x, 24);
       }
@@ -519,27 +539,8 @@ DEVI void ghash_step(uint32_t y[4], const uint32_t x[4], const uint32_t h[4]) {
   y[0] = z0; y[1] = z1; y[2] = z2; y[3] = z3;
 }
 
-// up to 16 bytes at p (rem of them exist; the rest read as zero) -> block words
-DEVI void load_block(const uint8_t* p, uint64_t rem, uint32_t d[4]) {
-#pragma unroll
-  for (int i = 0; i < 4; ++i) d[i] = 0;
-#pragma unroll
-  for (int j = 0; j < 16; ++j) {
-    const uint32_t b = (uint64_t)j < rem ? (uint32_t)p[j] : 0u;
-    d[j >> 2] |= b << (8 * (j & 3));
-  }
-}
-
-// A byte source for GHASH: len() bytes, block(o, d) = the 16 bytes at offset o (a multiple of 16)
-// as block words, zero past the end.  PackedBytes is the contiguous one.
-struct PackedBytes {
-  const uint8_t* p;
-  uint64_t n;
-  DEVI uint64_t len() const { return n; }
-  DEVI void block(uint64_t o, uint32_t d[4]) const { load_block(p + o, n - o, d); }
-};
-
-// GHASH the source's bytes into y (zero-padded to whole blocks).
+// GHASH the bytes of a source (hpke_prims.h: len(), block(o, d)) into y, zero-padded to whole
+// blocks.
 template <class Src>
 DEVI void ghash_bytes(uint32_t y[4], const uint32_t h[4], const Src& src) {
   const uint64_t len = src.len();
@@ -559,10 +560,11 @@ DEVI void hpke_open_reject(uint8_t* pt, uint64_t pt_cap, uint8_t* status, bool s
 }
 
 // One report, one lane: derive (key, base_nonce) from the lane's dh (8 words as k_x25519 wrote
-// them) and enc (32 bytes), check the GCM tag over aad || ct[0 .. body), then write the plaintext
-// to pt[0 .. body) and zeros up to pt_cap -- or zeros and status 4 when the tag does not match or
-// dh is all zero (RFC 9180 §7.1.4): never unauthenticated plaintext.  ct holds body + 16 bytes.
-template <class Aad>
+// them) and enc (32 bytes), check the AEAD's tag over aad || ct[0 .. body), then write the
+// plaintext to pt[0 .. body) and zeros up to pt_cap -- or zeros and status 4 when the tag does not
+// match or dh is all zero (RFC 9180 §7.1.4): never unauthenticated plaintext.  ct holds body + 16
+// bytes.  sbox is unused (null) for ChaCha20-Poly1305.
+template <int KDF, int AEAD, class Aad>
 DEVI void hpke_open_lane(const uint8_t* sbox, const HpkeBatchConsts& bc, const uint32_t* dh,
                          const uint8_t* enc, const Aad& aad, const uint8_t* ct, uint64_t body,
                          uint8_t* pt, uint64_t pt_cap, uint8_t* status) {
@@ -575,13 +577,28 @@ DEVI void hpke_open_lane(const uint8_t* sbox, const HpkeBatchConsts& bc, const u
     const uint8_t* e = enc + 4 * i;
     encw[i] = ((uint32_t)e[0] << 24) | ((uint32_t)e[1] << 16) | ((uint32_t)e[2] << 8) | e[3];
   }
-  uint32_t key[4], nonce[3];
-  hpke_key_nonce(bc, dhw, encw, key, nonce);
-  uint32_t rk[44];
-  aes128_expand(sbox, key, rk);
+  constexpr int NKW = hpke_aead_nk(AEAD) / 4;
+  uint32_t key[NKW], nonce[3];
+  hpke_key_nonce<KDF, AEAD>(bc, dhw, encw, key, nonce);
+  if constexpr (AEAD == 3) {
+    uint32_t tag[4];
+#pragma unroll
+    for (int i = 0; i < NKW; ++i) key[i] = bswap32(key[i]);
+#pragma unroll
+    for (int i = 0; i < 3; ++i) nonce[i] = bswap32(nonce[i]);
+    load_block(ct + body, 16, tag);
+    if (nz == 0u || !chacha20poly1305_open(key, nonce, aad, PackedBytes{ct, body}, tag, pt)) {
+      hpke_open_reject(pt, pt_cap, status, false);
+      return;
+    }
+    for (uint64_t j = body; j < pt_cap; ++j) pt[j] = 0;
+    return;
+  }
+  uint32_t rk[4 * (NKW + 7)];
+  aes_expand<NKW>(sbox, key, rk);
   const uint32_t zero[4] = {0, 0, 0, 0};
   uint32_t hle[4], h[4], ctr[4], ek[4];
-  aes128_encrypt(sbox, rk, zero, hle);  // H = E(K, 0)
+  aes_encrypt<NKW>(sbox, rk, zero, hle);  // H = E(K, 0)
 #pragma unroll
   for (int i = 0; i < 4; ++i) h[i] = bswap32(hle[i]);
   uint32_t y[4] = {0, 0, 0, 0};
@@ -594,7 +611,7 @@ DEVI void hpke_open_lane(const uint8_t* sbox, const HpkeBatchConsts& bc, const u
 #pragma unroll
   for (int i = 0; i < 3; ++i) ctr[i] = bswap32(nonce[i]);
   ctr[3] = bswap32(1u);  // J0 = nonce || 1 (seq 0: the nonce is base_nonce)
-  aes128_encrypt(sbox, rk, ctr, ek);
+  aes_encrypt<NKW>(sbox, rk, ctr, ek);
   uint32_t tag[4], diff = 0;
   load_block(ct + body, 16, tag);
 #pragma unroll
@@ -607,7 +624,7 @@ DEVI void hpke_open_lane(const uint8_t* sbox, const HpkeBatchConsts& bc, const u
     uint32_t d[4];
     load_block(ct + o, body - o, d);
     ctr[3] = bswap32((uint32_t)(o >> 4) + 2u);
-    aes128_encrypt(sbox, rk, ctr, ek);
+    aes_encrypt<NKW>(sbox, rk, ctr, ek);
 #pragma unroll
     for (int j = 0; j < 16; ++j)
       if (o + j < body) pt[o + j] = (uint8_t)((d[j >> 2] ^ ek[j >> 2]) >> (8 * (j & 3)));
@@ -618,14 +635,19 @@ DEVI void hpke_open_lane(const uint8_t* sbox, const HpkeBatchConsts& bc, const u
 // One lane per report: hpke_open_lane over packed inputs, or zeros and status 4 when there is
 // nothing to open (a short ciphertext, offsets that do not fit).  A report whose status is
 // non-zero on entry keeps it and gets zeros.  Lanes have their own lengths; the only barrier is
-// the one after the S-box is built, before any lane diverges.
+// the one after the S-box is built, before any lane diverges (no S-box for ChaCha20-Poly1305).
+template <int KDF, int AEAD>
 __global__ void __launch_bounds__(256) k_hpke_open(
     uint32_t n, HpkeBatchConsts bc, const uint32_t* dh, const uint8_t* encs, const uint8_t* aads,
     const uint64_t* aad_off, uint64_t aad_total, const uint8_t* cts, const uint64_t* ct_off,
     uint64_t ct_total, uint8_t* pts, const uint64_t* pt_off, uint64_t pt_total, uint8_t* status) {
-  __shared__ uint8_t sbox[256];
-  aes_sbox_init(sbox);
-  __syncthreads();
+  const uint8_t* sbox = nullptr;
+  if constexpr (AEAD != 3) {
+    __shared__ uint8_t sbox_lds[256];
+    aes_sbox_init(sbox_lds);
+    __syncthreads();
+    sbox = sbox_lds;
+  }
   const uint32_t r = blockIdx.x * blockDim.x + threadIdx.x;
   if (r >= n) return;
   const uint64_t a0 = aad_off[r], a1 = aad_off[r + 1], c0 = ct_off[r], c1 = ct_off[r + 1];
@@ -640,8 +662,23 @@ __global__ void __launch_bounds__(256) k_hpke_open(
     hpke_open_reject(pt, pt_cap, status + r, skip);
     return;
   }
-  hpke_open_lane(sbox, bc, dh + (size_t)r * 8, encs + (size_t)r * 32, PackedBytes{aads + a0, a1 - a0},
-                 cts + c0, c1 - c0 - 16, pt, pt_cap, status + r);
+  hpke_open_lane<KDF, AEAD>(sbox, bc, dh + (size_t)r * 8, encs + (size_t)r * 32,
+                            PackedBytes{aads + a0, a1 - a0}, cts + c0, c1 - c0 - 16, pt, pt_cap,
+                            status + r);
+}
+
+// TEST ONLY (prio3gpu_test_poly1305_gpu): tags[i] = Poly1305(keys[i], msgs[off[i] .. off[i + 1])),
+// one lane per message, through hpke_prims.h's poly1305_mac.
+__global__ void __launch_bounds__(64) k_test_poly1305(uint32_t n, const uint8_t* keys,
+                                                      const uint8_t* msgs, const uint64_t* off,
+                                                      uint8_t* tags) {
+  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  uint32_t k[8], tag[4];
+  load_le_words8(keys + (size_t)i * 32, k);
+  poly1305_mac(k, msgs + off[i], off[i + 1] - off[i], tag);
+#pragma unroll
+  for (int j = 0; j < 16; ++j) tags[(size_t)i * 16 + j] = (uint8_t)(tag[j >> 2] >> (8 * (j & 3)));
 }
 
 }  // namespace p3g

@@ -8,7 +8,8 @@ Per aggregation job (one AggregationJobInitializeReq):
      fails it too (`EmptyAggregation`, aggregator.rs:1851-1863); gather the engine inputs and
      each report's structural faults                                 codec.cpp   (aggregator.rs:1561-1612)
   2. HPKE-open every encrypted input share on host threads            hpke.cpp    (aggregator.rs:1634-1700)
-     (hpke="gpu": X25519 / HKDF-SHA256 / AES-128-GCM shares on the GPU, hpke_gpu.h)
+     (hpke="gpu": X25519 / HKDF-SHA256 / AES-128-GCM shares on the GPU, hpke_gpu.h; with
+     hpke_gpu_suites=1 the shares of every X25519 suite)
   3. decode the PlaintextInputShares into the input-share array, then apply the structural
      faults to the reports still OK (Janus's precedence: HPKE 3/4, plaintext/input share 8,
      public share 8, ping-pong 5)                                                 (aggregator.rs:1702-1797)
@@ -120,7 +121,7 @@ class HelperAggregateInit:
                  global_keys: Sequence[hpke.HpkeKeypair] = (), query_type: int = C.TIME_INTERVAL,
                  hpke_threads: int = 0,
                  batch_slot_of: Optional[Callable[[np.ndarray], np.ndarray]] = None,
-                 hpke: str = "host"):
+                 hpke: str = "host", hpke_gpu_suites: int = 0):
         """`batch_slot_of(times) -> slots` maps report times to aggregate slots (Janus's
         Q::to_batch_identifier, aggregator.rs:1614-1619); None = one slot.
 
@@ -132,15 +133,28 @@ class HelperAggregateInit:
         device for HPKE.  "fused": gather, open, decode and preparation are one engine call on
         `vdaf`'s own context in `prepare` (Prio3Gpu.helper_init_request); `open` only decodes
         and checks the request and copies it to pinned memory, and there is no second context.
-        Statuses and responses are those of "host" in every mode."""
+        Statuses and responses are those of "host" in every mode.
+
+        `hpke_gpu_suites` is the engine option of that name (prio3gpu_ctx_set_option): 0
+        (default) the GPU opens only X25519 / HKDF-SHA256 / AES-128-GCM keys; 1 every X25519
+        suite Janus accepts (KDF HKDF-SHA256 / -SHA384 / -SHA512 x AEAD AES-128-GCM / AES-256-GCM
+        / ChaCha20-Poly1305), so a task whose key names one of those keeps its reports off the
+        host threads.  In "gpu" mode it is set on the driver's own HPKE context; in "fused" mode
+        on `vdaf`'s context, which keeps it after the driver is closed.  A non-zero value with
+        hpke="host" is a `ValueError`: nothing would open on the GPU."""
         if hpke not in ("host", "gpu", "fused"):
             raise ValueError('hpke must be "host", "gpu" or "fused"')
+        if hpke_gpu_suites and hpke == "host":
+            raise ValueError('hpke_gpu_suites needs hpke="gpu" or "fused"')
         self.hpke_mode = hpke
         self._hpke_ctx = None
         if hpke == "gpu":
             self._hpke_ctx = Prio3Gpu(vdaf.kind, vdaf.verify_key, bits=vdaf.bits,
                                       length=vdaf.length, chunk_length=vdaf.chunk_length,
                                       device=vdaf.device, xof=vdaf.xof)
+            self._hpke_ctx.set_option("hpke_gpu_suites", hpke_gpu_suites)
+        elif hpke == "fused":
+            vdaf.set_option("hpke_gpu_suites", hpke_gpu_suites)
         self.vdaf = vdaf
         self.task_id = bytes(task_id)
         self.task_keys = list(task_keys)

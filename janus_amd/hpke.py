@@ -167,8 +167,10 @@ def _ptr(x, dtype):
 
 def open_batch_gpu(gpu, keypair: HpkeKeypair, info: bytes, encs, aads, aad_offsets, cts,
                    ct_offsets, pts=None, pt_offsets=None, status=None, n: Optional[int] = None):
-    """n HPKE opens under ONE keypair on the GPU (prio3gpu_hpke_open_batch; X25519 /
-    HKDF-SHA256 / AES-128-GCM only -- `ValueError` for any other suite, nothing launched).
+    """n HPKE opens under ONE keypair on the GPU (prio3gpu_hpke_open_batch).  By default only
+    X25519 / HKDF-SHA256 / AES-128-GCM; after `gpu.set_option("hpke_gpu_suites", 1)` every X25519
+    suite (KDF HKDF-SHA256 / -SHA384 / -SHA512 x AEAD AES-128-GCM / AES-256-GCM /
+    ChaCha20-Poly1305).  `ValueError` for any other suite (P-256 always), nothing launched.
 
     `gpu` is a `Prio3Gpu` or a context handle.  Report i: enc = encs[32 i : 32 i + 32], aad =
     aads[aad_offsets[i] : aad_offsets[i+1]], ciphertext || tag = cts[ct_offsets[i] :
@@ -211,8 +213,10 @@ def open_report_shares(task_id: bytes, req, task_keys: Sequence[HpkeKeypair],
     """Open every encrypted input share of a decoded AggregationJobInitializeReq
     (`janus_amd.codec.AggInitReq`) on `threads` host threads (0: all cores).  With `gpu` (a
     `Prio3Gpu` or a context handle) the reports whose first-choice key is X25519 / HKDF-SHA256 /
-    AES-128-GCM are opened on that context's GPU instead (prio3gpu_hpke_open_report_shares_gpu);
-    statuses, offsets and plaintexts are the host path's.
+    AES-128-GCM -- or, with that context's "hpke_gpu_suites" option at 1, any X25519 suite -- are
+    opened on that context's GPU instead (prio3gpu_hpke_open_report_shares_gpu); the rest (P-256,
+    the second trial with a global key) stay on the host threads.  Statuses, offsets and
+    plaintexts are the host path's.
 
     -> (plaintexts uint8 array, offsets (n + 1), status); report i's PlaintextInputShare is
     plaintexts[offsets[i]:offsets[i+1]] -- the input of codec.decode_plaintext_input_shares_raw.

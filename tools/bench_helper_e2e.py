@@ -51,7 +51,11 @@ def main():
                     help="where the helper input shares are opened (HelperAggregateInit hpke=): "
                          "host, gpu, fused, or a comma-separated list run alternately")
     ap.add_argument("--config", choices=("sumvec", "sum", "histogram", "count"), default="sumvec")
+    ap.add_argument("--suite", default="0x20/1/1",
+                    help="KEM/KDF/AEAD of the task key; a suite other than 0x20/1/1 runs the gpu "
+                         "and fused modes with hpke_gpu_suites=1")
     args = ap.parse_args()
+    suite = tuple(int(x, 0) for x in args.suite.split("/"))
     modes = args.hpke.split(",")
     if not modes or any(m not in ("host", "gpu", "fused") for m in modes):
         ap.error("--hpke: host, gpu, fused or a comma-separated list of them")
@@ -63,7 +67,7 @@ def main():
     s = v.sizes
     M, J = args.job_size, args.jobs
     rng = np.random.default_rng(2024)
-    tk = H.generate_hpke_config_and_private_key(7)
+    tk = H.generate_hpke_config_and_private_key(7, *suite)
     info = H.application_info(H.Label.INPUT_SHARE, H.ROLE_CLIENT, H.ROLE_HELPER)
     task_id = hashlib.sha256(b"e2e task").digest()
     t0 = time.time()
@@ -104,7 +108,9 @@ def main():
     gen_s = time.time() - t0
     drvs, aggs, rep_s, resps = {}, {}, {m: [] for m in modes}, {}
     for m in modes:
-        drvs[m] = HelperAggregateInit(v, task_id, [tk], hpke_threads=args.threads, hpke=m)
+        wide = 1 if m != "host" and suite != (0x20, 1, 1) else 0
+        drvs[m] = HelperAggregateInit(v, task_id, [tk], hpke_threads=args.threads, hpke=m,
+                                      hpke_gpu_suites=wide)
         drvs[m].handle_jobs(reqs[:1], v.new_aggregate(1))  # warm (allocates the state)
         aggs[m] = v.new_aggregate(1)
     torch.cuda.synchronize()
@@ -182,7 +188,7 @@ def report(args, v, s, drv, mode, reqs, task_id, tk, rep_s, gen_s, label):
                 "threads) -> GPU prepare+decide+prepare_next+accumulate -> response bytes, "
                 "pipelined over jobs",
         "value": round(n / dt, 1), "unit": "reports/s", "jobs": J, "job_size": M,
-        "reps": args.reps, "hpke": mode, "hpke_threads": args.threads, "seconds": round(dt, 3),
+        "reps": args.reps, "hpke": mode, "suite": args.suite, "hpke_threads": args.threads, "seconds": round(dt, 3),
         "reports_per_s_by_rep": [round(J * M / x) for x in rep_s],
         "median_reports_per_s": round(statistics.median(rates)),
         "min_reports_per_s": round(rates[0]), "max_reports_per_s": round(rates[-1]),
