@@ -19,6 +19,7 @@
 #include "errors.h"
 #include "plan_cfg.h"
 #include "plan_accum.h"
+#include "plan_hpke.h"
 #include "prio3_kernels.h"
 #include "fpvec_kernels.h"
 #include "wires_mfma.h"
@@ -2406,74 +2407,46 @@ void host_parallel(size_t n, int threads, F&& f) {
   for (auto& th : pool) th.join();
 }
 
-// d_out[r] = X25519(sk, d_points[r]); the clamped scalar travels as a kernel argument, so no
-// device buffer ever holds the private key.
-void clamp_scalar(const uint8_t* sk, X25519Scalar* ks) {
-  uint8_t k[32];
-  memcpy(k, sk, 32);
-  k[0] &= 248;  // decodeScalar25519
-  k[31] &= 127;
-  k[31] |= 64;
-  memcpy(ks->w, k, 32);  // little-endian host
-  wipe(k, sizeof k);
-}
-
-int launch_x25519(prio3gpu_ctx* c, const uint8_t* sk, size_t n, const uint8_t* d_points,
-                  uint32_t* d_out) {
+// launch(ks) with sk clamped (decodeScalar25519): the scalar travels as a kernel argument, so no
+// device buffer ever holds the private key, and its host copy is wiped after the launch.
+template <class F>
+int with_clamped_scalar(const uint8_t* sk, F&& launch) {
   X25519Scalar ks;
-  clamp_scalar(sk, &ks);
-  {
-    PROF(KID_X25519);
-    hipLaunchKernelGGL(k_x25519, dim3((unsigned)((n + 63) / 64)), dim3(64), 0, c->stream,
-                       (uint32_t)n, ks, d_points, d_out);
-  }
+  memcpy(ks.w, sk, 32);  // little-endian host
+  ks.w[0] &= ~7u;
+  ks.w[7] = (ks.w[7] & 0x7FFFFFFFu) | 0x40000000u;
+  launch(ks);
   wipe(&ks, sizeof ks);
   HIPCHK(hipGetLastError());
   return 0;
+}
+
+// d_out[r] = X25519(sk, d_points[r]) for r < n.
+int launch_x25519(prio3gpu_ctx* c, const uint8_t* sk, size_t n, const uint8_t* d_points,
+                  uint32_t* d_out) {
+  return with_clamped_scalar(sk, [&](const X25519Scalar& ks) {
+    PROF(KID_X25519);
+    hipLaunchKernelGGL(k_x25519, dim3((unsigned)((n + 63) / 64)), dim3(64), 0, c->stream,
+                       (uint32_t)n, ks, d_points, d_out);
+  });
 }
 
 // The same over a key group of the request in device memory: d_dh[idx[j]] for j < m.
 int launch_x25519_idx(prio3gpu_ctx* c, const uint8_t* sk, size_t m, const uint32_t* d_idx,
                       const uint8_t* d_msg, const ReqView* d_views, uint32_t* d_dh) {
-  X25519Scalar ks;
-  clamp_scalar(sk, &ks);
-  {
+  return with_clamped_scalar(sk, [&](const X25519Scalar& ks) {
     PROF(KID_X25519_IDX);
     hipLaunchKernelGGL(k_x25519_idx, dim3((unsigned)((m + 63) / 64)), dim3(64), 0, c->stream,
                        (uint32_t)m, ks, d_idx, d_msg, d_views, d_dh);
-  }
-  wipe(&ks, sizeof ks);
-  HIPCHK(hipGetLastError());
-  return 0;
+  });
 }
 
-bool span_fits(uint64_t off, uint64_t len, uint64_t total) {
-  return off <= total && len <= total - off;
-}
-
-// Every offset a kernel (or the host fallback) reads through, against the message length; and
-// the gather's grid, which must fit one launch.
-int check_request_views(const Cfg& g, const prio3gpu_prepare_init_view* views, size_t n,
-                        size_t msg_len) {
-  for (size_t i = 0; i < n; ++i) {
-    const prio3gpu_prepare_init_view& v = views[i];
-    if (!span_fits(v.report_id_off, 16, msg_len) ||
-        !span_fits(v.public_share_off, v.public_share_len, msg_len) ||
-        !span_fits(v.enc_off, v.enc_len, msg_len) ||
-        !span_fits(v.payload_off, v.payload_len, msg_len) ||
-        !span_fits(v.prep_share_off, v.prep_share_len, msg_len) ||
-        !span_fits(v.prep_msg_off, v.prep_msg_len, msg_len)) {
-      set_err("view %zu does not fit the %zu-byte message", i, msg_len);
-      return PRIO3GPU_E_ARG;
-    }
-  }
-  const uint64_t max_ppr =
-      std::max<uint64_t>(1, (std::max(g.public_share_len, g.prep_share_len) + 15u) / 16u);
-  if ((n * max_ppr + 255) / 256 > 0x7FFFFFFFull) {
-    set_err("job too large for one gather launch");
-    return PRIO3GPU_E_CAPACITY;
-  }
-  return 0;
+// check_request_views (plan_hpke.h) with its message in the thread's error string.
+int check_views(const Cfg& g, const prio3gpu_prepare_init_view* views, size_t n, size_t msg_len) {
+  std::string err;
+  const int rc = check_request_views(g, views, n, msg_len, &err);
+  if (rc) set_err("%s", err.c_str());
+  return rc;
 }
 
 // k_req_gather over n checked views: rows of 16 / public_share_len / prep_share_len bytes.
@@ -2481,11 +2454,9 @@ int launch_req_gather(prio3gpu_ctx* c, size_t n, const uint8_t* d_msg, size_t ms
                       const ReqView* d_views, uint8_t* d_nonces, uint8_t* d_pub, uint8_t* d_lps,
                       uint8_t* d_faults) {
   const Cfg& g = c->cfg;
-  const uint64_t max_ppr =
-      std::max<uint64_t>(1, (std::max(g.public_share_len, g.prep_share_len) + 15u) / 16u);
   {
     PROF(KID_REQ_GATHER);
-    hipLaunchKernelGGL(k_req_gather, dim3((unsigned)((n * max_ppr + 255) / 256), 3), dim3(256), 0,
+    hipLaunchKernelGGL(k_req_gather, dim3((unsigned)req_gather_blocks(g, n), 3), dim3(256), 0,
                        c->stream, (uint32_t)n, d_msg, (uint64_t)msg_len, d_views,
                        g.public_share_len, g.prep_share_len, d_nonces, d_pub, d_lps, d_faults);
   }
@@ -2493,12 +2464,9 @@ int launch_req_gather(prio3gpu_ctx* c, size_t n, const uint8_t* d_msg, size_t ms
   return 0;
 }
 
-// The suites the GPU opens on this context: DHKEM(X25519, HKDF-SHA256) / HKDF-SHA256 /
-// AES-128-GCM always; with the "hpke_gpu_suites" option every X25519 suite Janus accepts.
+// The suites the GPU opens on this context (plan_hpke.h).
 bool hpke_gpu_suite(const prio3gpu_ctx* c, uint16_t kem, uint16_t kdf, uint16_t aead) {
-  if (kem != 0x0020) return false;
-  if (kdf == 1 && aead == 1) return true;
-  return c->hpke_gpu_suites && kdf >= 1 && kdf <= 3 && aead >= 1 && aead <= 3;
+  return p3g::hpke_gpu_suite(c->hpke_gpu_suites, kem, kdf, aead);
 }
 
 // f(KDF, AEAD) with the suite of bc as compile-time constants (one kernel instantiation each).
@@ -2512,6 +2480,41 @@ void hpke_suite_dispatch(const HpkeBatchConsts& bc, F&& f) {
   if (bc.kdf_id == 1) with_aead(std::integral_constant<int, 1>{});
   else if (bc.kdf_id == 2) with_aead(std::integral_constant<int, 2>{});
   else with_aead(std::integral_constant<int, 3>{});
+}
+
+// k_hpke_open / k_hpke_open_req, instantiated for the suite of bc.
+int launch_hpke_open(prio3gpu_ctx* c, const HpkeBatchConsts& bc, size_t n, const uint32_t* d_dh,
+                     const uint8_t* d_enc, const uint8_t* d_aad, const uint64_t* d_aoff,
+                     uint64_t aad_total, const uint8_t* d_ct, const uint64_t* d_coff,
+                     uint64_t ct_total, uint8_t* d_pt, const uint64_t* d_poff, uint64_t pt_total,
+                     uint8_t* d_st) {
+  {
+    PROF(KID_HPKE_OPEN);
+    hpke_suite_dispatch(bc, [&](auto kdf, auto aead) {
+      hipLaunchKernelGGL((k_hpke_open<decltype(kdf)::value, decltype(aead)::value>),
+                         dim3((unsigned)((n + 255) / 256)), dim3(256), 0, c->stream, (uint32_t)n,
+                         bc, d_dh, d_enc, d_aad, d_aoff, aad_total, d_ct, d_coff, ct_total, d_pt,
+                         d_poff, pt_total, d_st);
+    });
+  }
+  HIPCHK(hipGetLastError());
+  return 0;
+}
+
+int launch_hpke_open_req(prio3gpu_ctx* c, const HpkeBatchConsts& bc, const ReqTaskId& tid,
+                         size_t m, const uint32_t* d_idx, const uint32_t* d_dh,
+                         const uint8_t* d_msg, const ReqView* d_views, uint8_t* d_pts,
+                         const uint64_t* d_poff, uint8_t* d_status) {
+  {
+    PROF(KID_HPKE_OPEN_REQ);
+    hpke_suite_dispatch(bc, [&](auto kdf, auto aead) {
+      hipLaunchKernelGGL((k_hpke_open_req<decltype(kdf)::value, decltype(aead)::value>),
+                         dim3((unsigned)((m + 255) / 256)), dim3(256), 0, c->stream, (uint32_t)m,
+                         bc, tid, d_idx, d_dh, d_msg, d_views, d_pts, d_poff, d_status);
+    });
+  }
+  HIPCHK(hipGetLastError());
+  return 0;
 }
 
 int hpke_open_batch_impl(prio3gpu_ctx* c, uint16_t kdf_id, uint16_t aead_id, const uint8_t* sk,
@@ -2552,22 +2555,11 @@ int hpke_open_batch_impl(prio3gpu_ctx* c, uint16_t kdf_id, uint16_t aead_id, con
   }
   CHK(c->hpke[8].ensure(n * 32));
   uint32_t* d_dh = static_cast<uint32_t*>(c->hpke[8].p);
-  auto run = [&]() -> int {
-    CHK(launch_x25519(c, sk, n, d_enc, d_dh));
-    {
-      PROF(KID_HPKE_OPEN);
-      hpke_suite_dispatch(bc, [&](auto kdf, auto aead) {
-        hipLaunchKernelGGL((k_hpke_open<decltype(kdf)::value, decltype(aead)::value>), dim3((unsigned)((n + 255) / 256)),
-                           dim3(256), 0, c->stream, (uint32_t)n, bc, d_dh, d_enc, d_aad,
-                           reinterpret_cast<const uint64_t*>(d_aoff), aad_total, d_ct,
-                           reinterpret_cast<const uint64_t*>(d_coff), ct_total, d_pt,
-                           reinterpret_cast<const uint64_t*>(d_poff), pt_total, d_st);
-      });
-    }
-    HIPCHK(hipGetLastError());
-    return 0;
-  };
-  int rc = run();
+  int rc = launch_x25519(c, sk, n, d_enc, d_dh);
+  if (!rc)
+    rc = launch_hpke_open(c, bc, n, d_dh, d_enc, d_aad, reinterpret_cast<const uint64_t*>(d_aoff),
+                          aad_total, d_ct, reinterpret_cast<const uint64_t*>(d_coff), ct_total,
+                          d_pt, reinterpret_cast<const uint64_t*>(d_poff), pt_total, d_st);
   // the per-report secrets: the DH values (keys and nonces never leave registers)
   if (hipMemsetAsync(d_dh, 0, n * 32, c->stream) != hipSuccess && !rc) {
     set_err("clearing the DH values failed");
@@ -2582,6 +2574,279 @@ int hpke_open_batch_impl(prio3gpu_ctx* c, uint16_t kdf_id, uint16_t aead_id, con
                           hipMemcpyDeviceToHost, c->stream));
   if (d_st != status) HIPCHK(hipMemcpyAsync(status, d_st, n, hipMemcpyDeviceToHost, c->stream));
   return finish_call(c, {encs, aads, aad_offsets, cts, ct_offsets, pts, pt_offsets, status});
+}
+
+// The packed inputs and outputs of one key group's batch, reused from group to group.
+struct HpkeGroupBufs {
+  std::vector<uint8_t> encs, aads, cts, pts, st;
+  std::vector<uint64_t> aoff, coff, poff;
+};
+
+// One key group of prio3gpu_hpke_open_report_shares_gpu: pack its reports' fields, open them on
+// the GPU, unpack.  An opened report gets its plaintext; a failed one the second trial on the host
+// (st_retry 0) or its status.  The packed plaintexts are wiped on every way out.
+int open_group_packed(prio3gpu_ctx* c, const HpkePlan& plan, size_t k, const uint8_t info[20],
+                      const uint8_t* task_id, const uint8_t* msg,
+                      const prio3gpu_prepare_init_view* views, int threads, HpkeGroupBufs& b,
+                      uint8_t* plaintexts, const uint64_t* offsets, uint8_t* status,
+                      uint8_t* st_retry, bool* any_retry) {
+  struct WipeAtExit {
+    std::vector<uint8_t>& v;
+    ~WipeAtExit() { wipe(v.data(), v.size()); }
+  } wipe_pts{b.pts};
+  const prio3gpu_hpke_keypair* kp = plan.groups[k];
+  const uint32_t* idx = plan.idx.data() + plan.gbeg[k];
+  const size_t m = plan.gbeg[k + 1] - plan.gbeg[k];
+  b.aoff.assign(m + 1, 0), b.coff.assign(m + 1, 0), b.poff.assign(m + 1, 0);
+  for (size_t j = 0; j < m; ++j) {
+    const prio3gpu_prepare_init_view& v = views[idx[j]];
+    b.aoff[j + 1] = b.aoff[j] + 60 + v.public_share_len;  // InputShareAad
+    b.coff[j + 1] = b.coff[j] + v.payload_len;
+    b.poff[j + 1] = b.poff[j] + (v.payload_len - 16);
+  }
+  b.encs.resize(m * 32), b.aads.resize(b.aoff[m]), b.cts.resize(b.coff[m]);
+  // the fields of one report lie kilobytes apart in the request (its prep share is between
+  // them): the gather is DRAM-latency-bound on one thread, so it runs on the host threads
+  host_parallel(m, threads, [&](size_t j) {
+    const prio3gpu_prepare_init_view& v = views[idx[j]];
+    memcpy(&b.encs[j * 32], msg + v.enc_off, 32);
+    uint8_t* a = &b.aads[b.aoff[j]];  // task id, report id, time, u32-prefixed public share
+    memcpy(a, task_id, 32);
+    memcpy(a + 32, msg + v.report_id_off, 16);
+    for (int s = 0; s < 8; ++s) a[48 + s] = uint8_t(v.time >> (56 - 8 * s));
+    for (int s = 0; s < 4; ++s) a[56 + s] = uint8_t(v.public_share_len >> (24 - 8 * s));
+    memcpy(a + 60, msg + v.public_share_off, v.public_share_len);
+    memcpy(&b.cts[b.coff[j]], msg + v.payload_off, v.payload_len);
+  });
+  b.pts.assign(std::max<size_t>(b.poff.back(), 1), 0);
+  b.st.assign(m, 0);
+  CHK(hpke_open_batch_impl(c, kp->kdf_id, kp->aead_id, kp->private_key, kp->public_key, info, 20,
+                           m, b.encs.data(), b.aads.data(), b.aoff.data(), b.cts.data(),
+                           b.coff.data(), b.pts.data(), b.poff.data(), b.st.data()));
+  for (size_t j = 0; j < m; ++j) {
+    const size_t i = idx[j];
+    if (b.st[j] == 0) {
+      memcpy(plaintexts + offsets[i], b.pts.data() + b.poff[j], b.poff[j + 1] - b.poff[j]);
+    } else if (wants_global_retry(plan, views, i)) {
+      st_retry[i] = 0;
+      *any_retry = true;
+    } else {
+      status[i] = PRIO3GPU_HPKE_DECRYPT_ERROR;
+    }
+  }
+  return 0;
+}
+
+// ---- prio3gpu_helper_init_request, step by step -------------------------------------------------
+// One call's arguments, plan and buffers.
+struct ReqCall {
+  prio3gpu_ctx* c;
+  prio3gpu_state* st;
+  const uint8_t* task_id;
+  uint8_t sender_role, recipient_role;
+  const uint8_t* msg;
+  size_t msg_len;
+  const prio3gpu_prepare_init_view* views;
+  size_t n;
+  int threads;
+  HpkePlan plan;                     // request mode (plan_hpke.h)
+  std::vector<uint64_t> poff;        // plaintext_offsets
+  std::vector<uint8_t> dst;          // the device status image on the host
+  std::vector<HpkeBatchConsts> bcs;  // per group
+  ReqTaskId tid;
+  size_t in_pitch;
+  const uint8_t* d_msg;
+  const ReqView* d_views;
+  const uint32_t* d_idx;
+  uint32_t* d_dh;
+  uint8_t* d_pts;
+  const uint64_t* d_poff;
+  uint8_t *d_faults, *d_status, *d_in;
+  std::vector<uint8_t> hp, hin, fb;  // host fallback: plaintexts, decoded rows, packed upload
+};
+
+// 1. Who opens which report, the status image the kernels start from, each group's constants.
+int req_plan(ReqCall& q, const prio3gpu_hpke_keypair* task_keys, size_t n_task_keys,
+             const prio3gpu_hpke_keypair* global_keys, size_t n_global_keys,
+             const uint8_t* status) {
+  q.poff.resize(q.n + 1);
+  plaintext_offsets(q.views, q.n, q.poff.data());
+  plan_hpke(task_keys, n_task_keys, global_keys, n_global_keys, q.views, status, q.n,
+            q.c->hpke_gpu_suites, /*strict=*/false, &q.plan);
+  q.dst.resize(q.n);
+  request_status_image(q.plan, status, q.n, q.dst.data());
+  uint8_t info[20];
+  input_share_info(q.sender_role, q.recipient_role, info);
+  q.bcs.resize(q.plan.groups.size());
+  for (size_t k = 0; k < q.bcs.size(); ++k) {
+    const prio3gpu_hpke_keypair* kp = q.plan.groups[k];
+    if (!hpke_batch_consts(kp->kdf_id, kp->aead_id, kp->public_key, info, sizeof info,
+                           &q.bcs[k])) {
+      set_err("HPKE primitives unavailable");
+      return PRIO3GPU_E_UNSUPPORTED;
+    }
+  }
+  memcpy(q.tid.w, q.task_id, 32);  // little-endian host: byte j at bits 8 (j & 3) of word j >> 2
+  return 0;
+}
+
+// 2. The staged buffers; the message goes to the device here (or is used where it is).
+int req_reserve(ReqCall& q) {
+  prio3gpu_ctx* c = q.c;
+  prio3gpu_state* st = q.st;
+  const Cfg& g = c->cfg;
+  const size_t n = q.n;
+  HIPCHK(hipSetDevice(c->device));
+  q.in_pitch = input_pitch(st);
+  CHK(c->req[1].ensure(n * sizeof(ReqView)));
+  CHK(c->req[2].ensure(std::max<size_t>(q.plan.idx.size(), 1) * 4));
+  CHK(c->req[3].ensure(n * 32));
+  CHK(c->req[4].ensure(std::max<uint64_t>(q.poff[n], 16)));
+  CHK(c->req[5].ensure((n + 1) * 8));
+  CHK(c->req[6].ensure(n));
+  CHK(st->status.ensure(n));
+  CHK(st->nonces.ensure(n * 16));
+  CHK(st->pub.ensure(std::max<size_t>(n * g.public_share_len, 16)));
+  CHK(st->input.ensure((n - 1) * q.in_pitch + g.helper_share_len));
+  CHK(c->io[0].ensure(std::max<size_t>(n * g.prep_share_len, 16)));
+  {
+    PROF(KID_REQ_COPY);
+    CHK(stage_in(c, c->req[0], q.msg, q.msg_len, &q.d_msg, 16));
+  }
+  q.d_views = static_cast<const ReqView*>(c->req[1].p);
+  q.d_idx = static_cast<const uint32_t*>(c->req[2].p);
+  q.d_dh = static_cast<uint32_t*>(c->req[3].p);
+  q.d_pts = c->req[4].u8();
+  q.d_poff = static_cast<const uint64_t*>(c->req[5].p);
+  q.d_faults = c->req[6].u8();
+  q.d_status = st->status.u8();
+  q.d_in = st->input.u8();
+  return 0;
+}
+
+// 3. Views, group members, plaintext offsets and the status image up; nonces, public shares and
+// leader prep shares gathered into the engine's rows.
+int req_upload_gather(ReqCall& q) {
+  prio3gpu_ctx* c = q.c;
+  const size_t n = q.n;
+  const std::vector<uint32_t>& idx = q.plan.idx;
+  HIPCHK(hipMemcpyAsync(c->req[1].p, q.views, n * sizeof(ReqView), hipMemcpyHostToDevice,
+                        c->stream));
+  if (!idx.empty())
+    HIPCHK(hipMemcpyAsync(c->req[2].p, idx.data(), idx.size() * 4, hipMemcpyHostToDevice,
+                          c->stream));
+  HIPCHK(hipMemcpyAsync(c->req[5].p, q.poff.data(), (n + 1) * 8, hipMemcpyHostToDevice,
+                        c->stream));
+  HIPCHK(hipMemcpyAsync(q.d_status, q.dst.data(), n, hipMemcpyHostToDevice, c->stream));
+  return launch_req_gather(c, n, q.d_msg, q.msg_len, q.d_views, q.st->nonces.u8(), q.st->pub.u8(),
+                           c->io[0].u8(), q.d_faults);
+}
+
+// 4. Per key group: the DH values, then the open into d_pts / d_status.
+int req_open_groups(ReqCall& q) {
+  for (size_t k = 0; k < q.plan.groups.size(); ++k) {
+    const size_t m = q.plan.gbeg[k + 1] - q.plan.gbeg[k];
+    const uint32_t* d_idx = q.d_idx + q.plan.gbeg[k];
+    CHK(launch_x25519_idx(q.c, q.plan.groups[k]->private_key, m, d_idx, q.d_msg, q.d_views,
+                          q.d_dh));
+    CHK(launch_hpke_open_req(q.c, q.bcs[k], q.tid, m, d_idx, q.d_dh, q.d_msg, q.d_views, q.d_pts,
+                             q.d_poff, q.d_status));
+  }
+  return 0;
+}
+
+// 5. Plaintexts to input-share rows; the status image comes back for the host's classification.
+int req_decode(ReqCall& q) {
+  prio3gpu_ctx* c = q.c;
+  {
+    PROF(KID_DECODE_PT);
+    hipLaunchKernelGGL(k_decode_plaintext_input_shares, grid1(q.n, 256), dim3(256), 0, c->stream,
+                       (uint32_t)q.n, q.d_pts, q.d_poff, c->cfg.helper_share_len, q.d_in,
+                       (uint64_t)q.in_pitch, q.d_faults, q.d_status);
+  }
+  HIPCHK(hipGetLastError());
+  HIPCHK(hipMemcpyAsync(q.dst.data(), q.d_status, q.n, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(hipStreamSynchronize(c->stream));
+  return 0;
+}
+
+// 6a. The fallback reports opened and decoded on the host: q.hp, q.hin and their statuses.
+int req_host_open(ReqCall& q, const HpkeFallback& f, std::vector<uint8_t>& st_fb) {
+  prio3gpu_ctx* c = q.c;
+  const HpkePlan& p = q.plan;
+  const size_t n = q.n;
+  std::vector<uint8_t> host_msg;
+  const uint8_t* h_msg = q.msg;
+  if (is_device_ptr(q.msg)) {
+    host_msg.resize(q.msg_len);
+    HIPCHK(hipMemcpyAsync(host_msg.data(), q.msg, q.msg_len, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    h_msg = host_msg.data();
+  }
+  q.hp.assign(std::max<uint64_t>(q.poff[n], 1), 0);
+  std::vector<uint64_t> offs(n + 1);
+  st_fb.assign(n, 1);
+  if (f.n_host) {
+    st_fb = f.st_host;
+    CHK(prio3gpu_hpke_open_report_shares(q.task_id, p.task_keys, p.n_task_keys, p.global_keys,
+                                         p.n_global_keys, q.sender_role, q.recipient_role, h_msg,
+                                         q.views, n, q.hp.data(), offs.data(), st_fb.data(),
+                                         q.threads));
+  }
+  if (f.n_retry) {
+    std::vector<uint8_t> s2(f.st_retry);
+    CHK(prio3gpu_hpke_open_report_shares(q.task_id, nullptr, 0, p.global_keys, p.n_global_keys,
+                                         q.sender_role, q.recipient_role, h_msg, q.views, n,
+                                         q.hp.data(), offs.data(), s2.data(), q.threads));
+    for (size_t i = 0; i < n; ++i)
+      if (!f.st_retry[i]) st_fb[i] = s2[i];
+  }
+  q.hin.assign(n * (size_t)c->cfg.helper_share_len, 0);
+  return prio3gpu_decode_plaintext_input_shares(&c->sz, q.hp.data(), offs.data(), n, 1,
+                                                q.hin.data(), st_fb.data());
+}
+
+// 6. The host's share (classify_fallback, plan_hpke.h): opened and decoded on the host, packed
+// into one upload, scattered into the rows and the status image.
+int req_host_fallback(ReqCall& q) {
+  prio3gpu_ctx* c = q.c;
+  const uint32_t want = c->cfg.helper_share_len;
+  HpkeFallback f;
+  classify_fallback(q.plan, q.views, q.dst.data(), q.n, &f);
+  if (f.n_host + f.n_retry == 0) return 0;
+  std::vector<uint8_t> st_fb;
+  CHK(req_host_open(q, f, st_fb));
+  const FallbackLayout l = pack_fallback(f, q.n, q.hin.data(), st_fb.data(), want, &q.fb);
+  CHK(c->req[7].ensure(l.bytes));
+  uint8_t* d_fb = c->req[7].u8();
+  HIPCHK(hipMemcpyAsync(d_fb, q.fb.data(), l.bytes, hipMemcpyHostToDevice, c->stream));
+  {
+    PROF(KID_REQ_SCATTER);
+    hipLaunchKernelGGL(k_req_scatter, grid1(l.kf, 256), dim3(256), 0, c->stream, (uint32_t)l.kf,
+                       reinterpret_cast<const uint32_t*>(d_fb), d_fb + l.o_rows, d_fb + l.o_st,
+                       want, q.d_in, (uint64_t)q.in_pitch, q.d_faults, q.d_status);
+  }
+  HIPCHK(hipGetLastError());
+  HIPCHK(hipMemsetAsync(d_fb, 0, l.bytes, c->stream));  // input shares are secrets too
+  return 0;
+}
+
+// 7. The per-report secrets outside the engine's rows, after steps 3 to 6 ended with rc: the DH
+// values and the plaintexts on the device, the fallback's vectors on the host.
+int req_clear_secrets(ReqCall& q, int rc) {
+  prio3gpu_ctx* c = q.c;
+  bool cleared = hipMemsetAsync(q.d_dh, 0, q.n * 32, c->stream) == hipSuccess;
+  if (q.poff[q.n])
+    cleared &= hipMemsetAsync(q.d_pts, 0, q.poff[q.n], c->stream) == hipSuccess;
+  if (!cleared && !rc) {
+    set_err("clearing the request's secrets failed");
+    rc = PRIO3GPU_E_HIP;
+  }
+  if (rc || !q.fb.empty()) (void)hipStreamSynchronize(c->stream);  // fb, hp, hin are read by copies
+  wipe(q.hp.data(), q.hp.size());
+  wipe(q.hin.data(), q.hin.size());
+  wipe(q.fb.data(), q.fb.size());
+  return rc;
 }
 
 }  // namespace
@@ -2630,97 +2895,33 @@ int prio3gpu_hpke_open_report_shares_gpu(
                                             n_global_keys, sender_role, recipient_role, msg, views,
                                             n, plaintexts, offsets, status, threads);
   if (!msg || !views || !offsets || !task_id || !status) return PRIO3GPU_E_ARG;
-  offsets[0] = 0;
-  for (size_t i = 0; i < n; ++i)
-    offsets[i + 1] = offsets[i] + (views[i].payload_len >= 16 ? views[i].payload_len - 16 : 0);
-  auto find = [](const prio3gpu_hpke_keypair* ks, size_t nk, uint8_t id) {
-    for (size_t k = 0; k < nk; ++k)
-      if (ks[k].config_id == id) return &ks[k];
-    return static_cast<const prio3gpu_hpke_keypair*>(nullptr);
-  };
-  // The first-choice key of every report (task key, else global key, by config id).  Reports
-  // whose first choice is a key of a suite the GPU opens on this context (hpke_gpu_suite) go to
-  // the GPU, one batch per key; everything else (other suites, malformed keys or encapsulated
-  // keys, unknown ids) is the host path's, untouched.
-  std::vector<const prio3gpu_hpke_keypair*> first(n, nullptr), groups;
+  plaintext_offsets(views, n, offsets);
+  // The plan's groups go to the GPU, one batch per key; everything else (other suites, malformed
+  // keys or encapsulated keys, unknown ids) is the host path's, untouched.
+  HpkePlan plan;
+  plan_hpke(task_keys, n_task_keys, global_keys, n_global_keys, views, status, n,
+            c->hpke_gpu_suites, /*strict=*/true, &plan);
+  uint8_t info[20];
+  input_share_info(sender_role, recipient_role, info);
+  // the status arrays of the two host passes: 0 selects a report
   std::vector<uint8_t> st_host(status, status + n), st_retry(n, 1);
+  bool any_host = false, any_retry = false;
   for (size_t i = 0; i < n; ++i) {
-    if (status[i]) continue;
-    const prio3gpu_hpke_keypair* tk = find(task_keys, n_task_keys, views[i].hpke_config_id);
-    const prio3gpu_hpke_keypair* kp =
-        tk ? tk : find(global_keys, n_global_keys, views[i].hpke_config_id);
-    if (!kp || !hpke_gpu_suite(c, kp->kem_id, kp->kdf_id, kp->aead_id) || !kp->private_key ||
-        kp->private_key_len != 32 || !kp->public_key || kp->public_key_len != 32 ||
-        views[i].enc_len != 32 || views[i].payload_len < 16)
-      continue;
-    first[i] = kp;
-    st_host[i] = 1;  // not the host pass's
-    if (std::find(groups.begin(), groups.end(), kp) == groups.end()) groups.push_back(kp);
+    if (plan.route[i] >= 0) st_host[i] = 1;
+    any_host |= plan.route[i] == ROUTE_HOST;
   }
-  const uint8_t info[20] = {'d', 'a', 'p', '-', '0', '7', ' ', 'i', 'n', 'p', 'u', 't', ' ', 's',
-                            'h', 'a', 'r', 'e', sender_role, recipient_role};  // hpke.rs:52-77
-  bool any_retry = false;
-  std::vector<uint8_t> encs, aads, cts, pts, st;
-  std::vector<uint64_t> aoff, coff, poff;
-  std::vector<size_t> idx;
-  for (const prio3gpu_hpke_keypair* kp : groups) {
-    idx.clear();
-    for (size_t i = 0; i < n; ++i)
-      if (first[i] == kp) idx.push_back(i);
-    const size_t m = idx.size();
-    aoff.assign(m + 1, 0), coff.assign(m + 1, 0), poff.assign(m + 1, 0);
-    for (size_t j = 0; j < m; ++j) {
-      const prio3gpu_prepare_init_view& v = views[idx[j]];
-      aoff[j + 1] = aoff[j] + 60 + v.public_share_len;  // InputShareAad
-      coff[j + 1] = coff[j] + v.payload_len;
-      poff[j + 1] = poff[j] + (v.payload_len - 16);
-    }
-    encs.resize(m * 32), aads.resize(aoff[m]), cts.resize(coff[m]);
-    // the fields of one report lie kilobytes apart in the request (its prep share is between
-    // them): the gather is DRAM-latency-bound on one thread, so it runs on the host threads
-    host_parallel(m, threads, [&](size_t j) {
-      const prio3gpu_prepare_init_view& v = views[idx[j]];
-      memcpy(&encs[j * 32], msg + v.enc_off, 32);
-      uint8_t* a = &aads[aoff[j]];  // task id, report id, time, u32-prefixed public share
-      memcpy(a, task_id, 32);
-      memcpy(a + 32, msg + v.report_id_off, 16);
-      for (int b = 0; b < 8; ++b) a[48 + b] = uint8_t(v.time >> (56 - 8 * b));
-      for (int b = 0; b < 4; ++b) a[56 + b] = uint8_t(v.public_share_len >> (24 - 8 * b));
-      memcpy(a + 60, msg + v.public_share_off, v.public_share_len);
-      memcpy(&cts[coff[j]], msg + v.payload_off, v.payload_len);
-    });
-    pts.assign(std::max<size_t>(poff.back(), 1), 0);
-    st.assign(m, 0);
-    CHK(hpke_open_batch_impl(c, kp->kdf_id, kp->aead_id, kp->private_key, kp->public_key, info,
-                             sizeof info, m, encs.data(), aads.data(), aoff.data(), cts.data(),
-                             coff.data(), pts.data(), poff.data(), st.data()));
-    for (size_t j = 0; j < m; ++j) {
-      const size_t i = idx[j];
-      if (st[j] == 0) {
-        memcpy(plaintexts + offsets[i], pts.data() + poff[j], poff[j + 1] - poff[j]);
-        continue;
-      }
-      // a failed open: the global key of the same id gets the second trial, on the host
-      const bool is_task_key = kp >= task_keys && kp < task_keys + n_task_keys;
-      if (is_task_key && find(global_keys, n_global_keys, views[i].hpke_config_id)) {
-        st_retry[i] = 0;
-        any_retry = true;
-      } else {
-        status[i] = PRIO3GPU_HPKE_DECRYPT_ERROR;
-      }
-    }
-  }
-  wipe(pts.data(), pts.size());
-  bool any_host = false;
-  for (size_t i = 0; i < n; ++i) any_host |= !first[i] && !status[i];
+  HpkeGroupBufs bufs;
+  for (size_t k = 0; k < plan.groups.size(); ++k)
+    CHK(open_group_packed(c, plan, k, info, task_id, msg, views, threads, bufs, plaintexts,
+                          offsets, status, st_retry.data(), &any_retry));
   if (any_host) {
     CHK(prio3gpu_hpke_open_report_shares(task_id, task_keys, n_task_keys, global_keys,
                                          n_global_keys, sender_role, recipient_role, msg, views, n,
                                          plaintexts, offsets, st_host.data(), threads));
     for (size_t i = 0; i < n; ++i)
-      if (!first[i]) status[i] = st_host[i];
+      if (plan.route[i] < 0) status[i] = st_host[i];
   }
-  if (any_retry) {
+  if (any_retry) {  // the global key of the same id gets the second trial, on the host
     std::vector<uint8_t> was_retry(st_retry);
     CHK(prio3gpu_hpke_open_report_shares(task_id, nullptr, 0, global_keys, n_global_keys,
                                          sender_role, recipient_role, msg, views, n, plaintexts,
@@ -2757,216 +2958,26 @@ int prio3gpu_helper_init_request(
     set_err("helper_init_request: views and status are host memory");
     return PRIO3GPU_E_ARG;
   }
-  const Cfg& g = c->cfg;
-  const uint32_t pub_len = g.public_share_len, prep_len = g.prep_share_len;
-  const uint32_t want = g.helper_share_len;
-  CHK(check_request_views(g, views, n, msg_len));
-  auto find = [](const prio3gpu_hpke_keypair* ks, size_t nk, uint8_t id) {
-    for (size_t k = 0; k < nk; ++k)
-      if (ks[k].config_id == id) return &ks[k];
-    return static_cast<const prio3gpu_hpke_keypair*>(nullptr);
-  };
-  // Key selection as in prio3gpu_hpke_open_report_shares_gpu: the first-choice key of every report
-  // (task key, else global key, by config id).  Reports whose first choice is a key of a suite the
-  // GPU opens on this context (hpke_gpu_suite) form one group per key for the GPU; an unknown id is
-  // status 3 here; every other key is the host path's (REQ_HOST in the device status image).
-  std::vector<const prio3gpu_hpke_keypair*> groups;
-  std::vector<int32_t> grp(n, -1);
-  std::vector<uint8_t> dst(status, status + n);
-  std::vector<uint64_t> poff(n + 1, 0);
-  for (size_t i = 0; i < n; ++i) {
-    const prio3gpu_prepare_init_view& v = views[i];
-    poff[i + 1] = poff[i] + (v.payload_len >= 16 ? v.payload_len - 16 : 0);
-    if (status[i]) continue;
-    const prio3gpu_hpke_keypair* tk = find(task_keys, n_task_keys, v.hpke_config_id);
-    const prio3gpu_hpke_keypair* kp = tk ? tk : find(global_keys, n_global_keys, v.hpke_config_id);
-    if (!kp) {
-      dst[i] = PRIO3GPU_HPKE_UNKNOWN_CONFIG_ID;
-      continue;
-    }
-    if (!hpke_gpu_suite(c, kp->kem_id, kp->kdf_id, kp->aead_id) || !kp->private_key ||
-        kp->private_key_len != 32 || !kp->public_key || kp->public_key_len != 32) {
-      dst[i] = REQ_HOST;
-      continue;
-    }
-    size_t k = std::find(groups.begin(), groups.end(), kp) - groups.begin();
-    if (k == groups.size()) groups.push_back(kp);
-    grp[i] = (int32_t)k;
-  }
-  std::vector<uint32_t> idx;
-  std::vector<size_t> gbeg(groups.size() + 1, 0);
-  for (size_t k = 0; k < groups.size(); ++k) {
-    for (size_t i = 0; i < n; ++i)
-      if (grp[i] == (int32_t)k) idx.push_back((uint32_t)i);
-    gbeg[k + 1] = idx.size();
-  }
-  const uint8_t info[20] = {'d', 'a', 'p', '-', '0', '7', ' ', 'i', 'n', 'p', 'u', 't', ' ', 's',
-                            'h', 'a', 'r', 'e', sender_role, recipient_role};  // hpke.rs:52-77
-  std::vector<HpkeBatchConsts> bcs(groups.size());
-  for (size_t k = 0; k < groups.size(); ++k)
-    if (!hpke_batch_consts(groups[k]->kdf_id, groups[k]->aead_id, groups[k]->public_key, info,
-                           sizeof info, &bcs[k])) {
-      set_err("HPKE primitives unavailable");
-      return PRIO3GPU_E_UNSUPPORTED;
-    }
-  ReqTaskId tid;
-  memcpy(tid.w, task_id, 32);  // little-endian host: byte j at bits 8 (j & 3) of word j >> 2
-
-  HIPCHK(hipSetDevice(c->device));
-  const size_t in_pitch = input_pitch(st);
-  const uint64_t pt_total = poff[n];
-  CHK(c->req[1].ensure(n * sizeof(ReqView)));
-  CHK(c->req[2].ensure(std::max<size_t>(idx.size(), 1) * 4));
-  CHK(c->req[3].ensure(n * 32));
-  CHK(c->req[4].ensure(std::max<uint64_t>(pt_total, 16)));
-  CHK(c->req[5].ensure((n + 1) * 8));
-  CHK(c->req[6].ensure(n));
-  CHK(st->status.ensure(n));
-  CHK(st->nonces.ensure(n * 16));
-  CHK(st->pub.ensure(std::max<size_t>(n * pub_len, 16)));
-  CHK(st->input.ensure((n - 1) * in_pitch + want));
-  CHK(c->io[0].ensure(std::max<size_t>(n * prep_len, 16)));
-  const uint8_t* d_msg;
-  {
-    PROF(KID_REQ_COPY);
-    CHK(stage_in(c, c->req[0], msg, msg_len, &d_msg, 16));
-  }
-  const ReqView* d_views = static_cast<const ReqView*>(c->req[1].p);
-  const uint32_t* d_idx = static_cast<const uint32_t*>(c->req[2].p);
-  uint32_t* d_dh = static_cast<uint32_t*>(c->req[3].p);
-  uint8_t* d_pts = c->req[4].u8();
-  const uint64_t* d_poff = static_cast<const uint64_t*>(c->req[5].p);
-  uint8_t* d_faults = c->req[6].u8();
-  uint8_t* d_status = st->status.u8();
-  uint8_t* d_in = st->input.u8();
-  std::vector<uint8_t> host_msg, hp, hin, fb;  // host fallback: message copy, plaintexts, rows
-  auto run = [&]() -> int {
-    HIPCHK(hipMemcpyAsync(c->req[1].p, views, n * sizeof(ReqView), hipMemcpyHostToDevice,
-                          c->stream));
-    if (!idx.empty())
-      HIPCHK(hipMemcpyAsync(c->req[2].p, idx.data(), idx.size() * 4, hipMemcpyHostToDevice,
-                            c->stream));
-    HIPCHK(hipMemcpyAsync(c->req[5].p, poff.data(), (n + 1) * 8, hipMemcpyHostToDevice,
-                          c->stream));
-    HIPCHK(hipMemcpyAsync(d_status, dst.data(), n, hipMemcpyHostToDevice, c->stream));
-    CHK(launch_req_gather(c, n, d_msg, msg_len, d_views, st->nonces.u8(), st->pub.u8(),
-                          c->io[0].u8(), d_faults));
-    for (size_t k = 0; k < groups.size(); ++k) {
-      const size_t m = gbeg[k + 1] - gbeg[k];
-      CHK(launch_x25519_idx(c, groups[k]->private_key, m, d_idx + gbeg[k], d_msg, d_views, d_dh));
-      {
-        PROF(KID_HPKE_OPEN_REQ);
-        hpke_suite_dispatch(bcs[k], [&](auto kdf, auto aead) {
-          hipLaunchKernelGGL((k_hpke_open_req<decltype(kdf)::value, decltype(aead)::value>), dim3((unsigned)((m + 255) / 256)),
-                             dim3(256), 0, c->stream, (uint32_t)m, bcs[k], tid, d_idx + gbeg[k],
-                             d_dh, d_msg, d_views, d_pts, d_poff, d_status);
-        });
-      }
-      HIPCHK(hipGetLastError());
-    }
-    {
-      PROF(KID_DECODE_PT);
-      hipLaunchKernelGGL(k_decode_plaintext_input_shares, grid1(n, 256), dim3(256), 0, c->stream,
-                         (uint32_t)n, d_pts, d_poff, want, d_in, (uint64_t)in_pitch, d_faults,
-                         d_status);
-    }
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipMemcpyAsync(dst.data(), d_status, n, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(hipStreamSynchronize(c->stream));
-    // The host's share: other suites and malformed keys (REQ_HOST), long extension lists
-    // (REQ_DEFER), both with the full key order; and the global-key second trial after a failed
-    // task-key open, with the global keys alone.
-    std::vector<uint8_t> st_host(n, 1), st_retry(n, 1);
-    size_t n_host = 0, n_retry = 0;
-    for (size_t i = 0; i < n; ++i) {
-      if (dst[i] == REQ_HOST || dst[i] == REQ_DEFER) {
-        st_host[i] = 0;
-        ++n_host;
-      } else if (grp[i] >= 0 && dst[i] == PRIO3GPU_HPKE_DECRYPT_ERROR) {
-        const prio3gpu_hpke_keypair* kp = groups[grp[i]];
-        const bool is_task_key = kp >= task_keys && kp < task_keys + n_task_keys;
-        if (is_task_key && find(global_keys, n_global_keys, views[i].hpke_config_id)) {
-          st_retry[i] = 0;
-          ++n_retry;
-        }
-      }
-    }
-    if (n_host + n_retry == 0) return 0;
-    const uint8_t* h_msg = msg;
-    if (is_device_ptr(msg)) {
-      host_msg.resize(msg_len);
-      HIPCHK(hipMemcpyAsync(host_msg.data(), msg, msg_len, hipMemcpyDeviceToHost, c->stream));
-      HIPCHK(hipStreamSynchronize(c->stream));
-      h_msg = host_msg.data();
-    }
-    hp.assign(std::max<uint64_t>(pt_total, 1), 0);
-    std::vector<uint64_t> offs(n + 1);
-    std::vector<uint8_t> st_fb(n, 1);
-    if (n_host) {
-      st_fb = st_host;
-      CHK(prio3gpu_hpke_open_report_shares(task_id, task_keys, n_task_keys, global_keys,
-                                           n_global_keys, sender_role, recipient_role, h_msg,
-                                           views, n, hp.data(), offs.data(), st_fb.data(),
-                                           threads));
-    }
-    if (n_retry) {
-      std::vector<uint8_t> s2(st_retry);
-      CHK(prio3gpu_hpke_open_report_shares(task_id, nullptr, 0, global_keys, n_global_keys,
-                                           sender_role, recipient_role, h_msg, views, n, hp.data(),
-                                           offs.data(), s2.data(), threads));
-      for (size_t i = 0; i < n; ++i)
-        if (!st_retry[i]) st_fb[i] = s2[i];
-    }
-    hin.assign(n * (size_t)want, 0);
-    CHK(prio3gpu_decode_plaintext_input_shares(&c->sz, hp.data(), offs.data(), n, 1, hin.data(),
-                                               st_fb.data()));
-    // compact: indices | rows | statuses of the fallback reports, one upload
-    const size_t kf = n_host + n_retry;
-    const size_t o_rows = (kf * 4 + 15) / 16 * 16, o_st = o_rows + kf * want;
-    fb.assign(o_st + kf, 0);
-    size_t j = 0;
-    for (size_t i = 0; i < n; ++i) {
-      if (st_host[i] && st_retry[i]) continue;
-      const uint32_t r = (uint32_t)i;
-      memcpy(&fb[4 * j], &r, 4);
-      memcpy(&fb[o_rows + j * want], &hin[i * (size_t)want], want);
-      fb[o_st + j] = st_fb[i];
-      ++j;
-    }
-    CHK(c->req[7].ensure(fb.size()));
-    uint8_t* d_fb = c->req[7].u8();
-    HIPCHK(hipMemcpyAsync(d_fb, fb.data(), fb.size(), hipMemcpyHostToDevice, c->stream));
-    {
-      PROF(KID_REQ_SCATTER);
-      hipLaunchKernelGGL(k_req_scatter, grid1(kf, 256), dim3(256), 0, c->stream, (uint32_t)kf,
-                         reinterpret_cast<const uint32_t*>(d_fb), d_fb + o_rows, d_fb + o_st, want,
-                         d_in, (uint64_t)in_pitch, d_faults, d_status);
-    }
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipMemsetAsync(d_fb, 0, fb.size(), c->stream));  // input shares are secrets too
-    return 0;
-  };
-  int rc = run();
-  // the per-report secrets outside the engine's rows: the DH values and the plaintexts
-  bool cleared = hipMemsetAsync(d_dh, 0, n * 32, c->stream) == hipSuccess;
-  if (pt_total) cleared &= hipMemsetAsync(d_pts, 0, pt_total, c->stream) == hipSuccess;
-  if (!cleared && !rc) {
-    set_err("clearing the request's secrets failed");
-    rc = PRIO3GPU_E_HIP;
-  }
-  if (rc || !fb.empty()) (void)hipStreamSynchronize(c->stream);  // fb, hp, hin are read by copies
-  wipe(hp.data(), hp.size());
-  wipe(hin.data(), hin.size());
-  wipe(fb.data(), fb.size());
-  if (rc) return rc;
+  CHK(check_views(c->cfg, views, n, msg_len));
+  ReqCall q{};
+  q.c = c, q.st = st, q.task_id = task_id;
+  q.sender_role = sender_role, q.recipient_role = recipient_role;
+  q.msg = msg, q.msg_len = msg_len, q.views = views, q.n = n, q.threads = threads;
+  CHK(req_plan(q, task_keys, n_task_keys, global_keys, n_global_keys, status));
+  CHK(req_reserve(q));
+  int rc = req_upload_gather(q);
+  if (!rc) rc = req_open_groups(q);
+  if (!rc) rc = req_decode(q);
+  if (!rc) rc = req_host_fallback(q);
+  CHK(req_clear_secrets(q, rc));
   CHK(copy_out(c, out_nonces, st->nonces.u8(), n * 16));
-  rc = prio3gpu_helper_init(c, st, n, st->nonces.u8(), st->pub.u8(), d_in, c->io[0].u8(),
-                            batch_slots, out_prep_msgs, d_status, agg);
+  rc = prio3gpu_helper_init(c, st, n, st->nonces.u8(), st->pub.u8(), q.d_in, c->io[0].u8(),
+                            batch_slots, out_prep_msgs, q.d_status, agg);
   if (rc) {
     (void)hipStreamSynchronize(c->stream);
     return rc;
   }
-  HIPCHK(hipMemcpyAsync(status, d_status, n, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(hipMemcpyAsync(status, q.d_status, n, hipMemcpyDeviceToHost, c->stream));
   HIPCHK(hipStreamSynchronize(c->stream));
   return 0;
 }
@@ -2982,7 +2993,7 @@ int prio3gpu_test_req_gather(prio3gpu_ctx* c, const uint8_t* msg, size_t msg_len
   }
   if (n == 0) return 0;
   const Cfg& g = c->cfg;
-  CHK(check_request_views(g, views, n, msg_len));
+  CHK(check_views(g, views, n, msg_len));
   HIPCHK(hipSetDevice(c->device));
   const size_t nb_pub = n * (size_t)g.public_share_len, nb_lps = n * (size_t)g.prep_share_len;
   const uint8_t* d_msg;

@@ -41,6 +41,7 @@
 #include "../../include/prio3gpu.h"
 #include "../../include/prio3gpu_test.h"
 #include "hpke_shared.h"
+#include "plan_hpke.h"
 
 namespace {
 
@@ -910,27 +911,24 @@ int prio3gpu_hpke_open_report_shares(const uint8_t* task_id, const prio3gpu_hpke
     return 0;
   }
   if (!msg || !views || !offsets) return PRIO3GPU_E_ARG;
-  offsets[0] = 0;
-  for (size_t i = 0; i < n; ++i)
-    offsets[i + 1] = offsets[i] + (views[i].payload_len >= kTag ? views[i].payload_len - kTag : 0);
+  p3g::plaintext_offsets(views, n, offsets);
   if (!plaintexts) return 0;  // sizing call
   if (!task_id || !status) return PRIO3GPU_E_ARG;
   if (!algs().ok) return PRIO3GPU_E_UNSUPPORTED;
-  static const char kLabel[] = "dap-07 input share";  // Label::InputShare, hpke.rs:52-57
-  Bytes info;
-  info.add(kLabel).add(&sender_role, 1).add(&recipient_role, 1);
-  auto find = [](const prio3gpu_hpke_keypair* ks, size_t nk, uint8_t id) {
-    for (size_t k = 0; k < nk; ++k)
-      if (ks[k].config_id == id) return &ks[k];
-    return static_cast<const prio3gpu_hpke_keypair*>(nullptr);
+  uint8_t info[20];
+  p3g::input_share_info(sender_role, recipient_role, info);
+  auto task_key = [&](size_t i) {
+    return p3g::find_keypair(task_keys, n_task_keys, views[i].hpke_config_id);
+  };
+  auto global_key = [&](size_t i) {
+    return p3g::find_keypair(global_keys, n_global_keys, views[i].hpke_config_id);
   };
   // One report: InputShareAad, the first-choice key (with its DH precomputed by the 8-way
   // ladder when dh_pre is set), then the global key after a decryption failure.
   auto open_i = [&](size_t i, const uint8_t* dh_pre) {
     if (status[i]) return;
     const prio3gpu_prepare_init_view& v = views[i];
-    const prio3gpu_hpke_keypair* tk = find(task_keys, n_task_keys, v.hpke_config_id);
-    const prio3gpu_hpke_keypair* gk = find(global_keys, n_global_keys, v.hpke_config_id);
+    const prio3gpu_hpke_keypair *tk = task_key(i), *gk = global_key(i);
     if (!tk && !gk) {
       status[i] = 3;  // PrepareError::HpkeUnknownConfigId
       return;
@@ -947,18 +945,13 @@ int prio3gpu_hpke_open_report_shares(const uint8_t* task_id, const prio3gpu_hpke
       Suite s;
       if (!suite_of(kp->kem_id, kp->kdf_id, kp->aead_id, &s)) return PRIO3GPU_E_UNSUPPORTED;
       return open_one(s, kp->private_key, kp->private_key_len, kp->public_key,
-                      kp->public_key_len, msg + v.enc_off, v.enc_len, info.v.data(),
-                      info.v.size(), aad.v.data(), aad.v.size(), msg + v.payload_off,
+                      kp->public_key_len, msg + v.enc_off, v.enc_len, info,
+                      sizeof info, aad.v.data(), aad.v.size(), msg + v.payload_off,
                       v.payload_len, out, pre);
     };
     int rc = try_open(tk ? tk : gk, dh_pre);
     if (rc == PRIO3GPU_E_HPKE && tk && gk) rc = try_open(gk, nullptr);  // second trial
     if (rc != 0) status[i] = 4;  // PrepareError::HpkeDecryptError
-  };
-  auto primary = [&](size_t i) {
-    const uint8_t id = views[i].hpke_config_id;
-    const prio3gpu_hpke_keypair* tk = find(task_keys, n_task_keys, id);
-    return tk ? tk : find(global_keys, n_global_keys, id);
   };
   const bool simd = have_ifma();
   // Chunks of 8 reports: the X25519 DH of every report whose first-choice key is the chunk's
@@ -974,7 +967,7 @@ int prio3gpu_hpke_open_report_shares(const uint8_t* task_id, const prio3gpu_hpke
       int lanes = 0;
       for (size_t i = b; i < e; ++i) {
         if (status[i]) continue;
-        const prio3gpu_hpke_keypair* kp = primary(i);
+        const prio3gpu_hpke_keypair* kp = task_key(i) ? task_key(i) : global_key(i);
         if (!kp || kp->kem_id != KEM_X25519 || kp->private_key_len != 32 || views[i].enc_len != 32)
           continue;
         if (!kp0) kp0 = kp;

@@ -13,7 +13,8 @@ from janus_amd import hpke as H
 from janus_amd._lib import lib
 from janus_amd.helper import HelperAggregateInit
 from tests.reports import expected_aggregate
-from tests.test_gpu_helper_request import TASK_ID, _batch, _vdaf, encode_request, items_of
+from tests.test_gpu_helper_request import (TASK_ID, _batch, _vdaf, both, encode_request, items_of,
+                                           same)
 
 pytestmark = pytest.mark.gpu
 
@@ -76,6 +77,61 @@ def test_fused_driver_wider_suite_matches_host(name, n, jobs, kdf, aead):
     exp, ecnt = expected_aggregate(b, "helper", mask=st == 0)
     got, cnt = on[2]
     assert got == exp and cnt == ecnt == b.n - 2
+
+
+def _staged_on_host(v, req_bytes, tks, gks):
+    """test_gpu_helper_request.staged with the open on the host threads."""
+    req = C.decode_agg_init_req(req_bytes)
+    nonces, pub, lps, faults = C.gather_prepare_inits(v.sizes, req)
+    pts, offs, st = H.open_report_shares(TASK_ID, req, tks, gks, np.zeros(req.n, np.uint8),
+                                         threads=2)
+    hin, st = C.decode_plaintext_input_shares_raw(v.sizes, pts, offs, 1, st)
+    C.apply_faults(st, faults)
+    state, agg = v.new_state(1, req.n), v.new_aggregate(1)
+    msgs, st = v.helper_init(state, nonces, pub, hin, lps, agg=agg, status=st)
+    out = (msgs, st.copy(), nonces, [agg.read(0)])
+    state.close()
+    agg.close()
+    return out
+
+
+def test_key_groups_of_several_suites_in_one_call():
+    """Two GPU key groups of different suites, a P-256 key for the host and the second trial with
+    a global key of another suite, in one call: prio3gpu_hpke_open_report_shares_gpu and the fused
+    call both answer as the host path does."""
+    name, n = "count", 12
+    b = _batch(name, n)
+    v = _vdaf(name, b)
+    x25519 = H.KEM_X25519_HKDF_SHA256
+    tk1 = H.generate_hpke_config_and_private_key(1, x25519, 1, 1)
+    tk2 = H.generate_hpke_config_and_private_key(2, x25519, 2, 3)
+    gk_same_id = H.generate_hpke_config_and_private_key(1, x25519, 3, 2)   # tk1's id
+    gk_p256 = H.generate_hpke_config_and_private_key(4, H.KEM_P256_HKDF_SHA256, 1, 2)
+    kps = [tk1, tk2, gk_same_id, gk_p256] * 3        # 2, 6, 10: opened by the second trial
+    items = items_of(b, list(range(1000, 1000 + n)), lambda r: kps[r])
+    items[4]["cid"] = 77                                                 # unknown config id
+    p = bytearray(items[5]["payload"])
+    p[3] ^= 0x40                                                         # corrupted payload
+    items[5]["payload"] = bytes(p)
+    req = encode_request(items)
+    tks, gks = [tk1, tk2], [gk_same_id, gk_p256]
+    L, ctx = lib(), v._ctx
+    try:
+        host = _staged_on_host(v, req, tks, gks)
+        v.set_option("hpke_gpu_suites", 1)
+        assert L.prio3gpu_prof_enable(ctx, 1) == 0
+        try:
+            _launches(ctx)  # drain
+            msgs, st, nonces, aggs = both(v, req, tks, gks)
+            got = _launches(ctx)
+        finally:
+            L.prio3gpu_prof_enable(ctx, 0)
+        same(host, (msgs, st, nonces, aggs))
+    finally:
+        v.close()
+    assert got["k_hpke_open"] == 2 and got["k_hpke_open_req"] == 2       # tk1 (+ its id), tk2
+    assert st[4] == 3 and st[5] == 4 and (np.delete(st, [4, 5]) == 0).all()
+    assert aggs[0] == expected_aggregate(b, "helper", mask=st == 0)
 
 
 def test_suites_option_needs_a_gpu_mode():

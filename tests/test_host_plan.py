@@ -2,7 +2,8 @@
 built with g++ and checked on the CPU: the lengths of every VDAF instance against the oracle, the
 Montgomery-form FLP tables against direct powers of the generator, the accumulation chunk plan
 against a Python restatement and its structural properties, and the column-summed element range.
-tests/native/host_plan_host.cpp is the driver (a text protocol on stdin / stdout)."""
+tests/native/host_plan_host.cpp is the driver (a text protocol on stdin / stdout).  The HPKE and
+request routing header, plan_hpke.h, has its own driver and tests in tests/test_hpke_plan.py."""
 import os
 import subprocess
 
