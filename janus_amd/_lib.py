@@ -37,7 +37,7 @@ class EmptyAggregation(Prio3GpuError):
 
 E_INVALID_MESSAGE = -7
 
-SOURCES = ("engine.hip", "codec.cpp", "hpke.cpp")
+SOURCES = ("engine.hip", "engine_hpke.hip", "codec.cpp", "hpke.cpp")
 FLAGS = ("--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-shared")
 LIBS = ("-lrccl", "-lcrypto")
 HASH_MARKER = b"PRIO3GPU_BUILD_HASH="
@@ -81,13 +81,27 @@ def build(force: bool = False, verbose: bool = False) -> Path:
     want = source_hash()
     if not force and not needs_rebuild(LIB_PATH, want):
         return LIB_PATH
+    import tempfile
+    from concurrent.futures import ThreadPoolExecutor
     LIB_DIR.mkdir(exist_ok=True)
-    tmp = LIB_PATH.with_suffix(".so.tmp")
-    cmd = (["hipcc"] + list(FLAGS) + [f'-DPRIO3GPU_BUILD_HASH="{want}"', "-o", str(tmp)]
-           + [str(CSRC / s) for s in SOURCES] + list(LIBS))
-    if verbose:
-        print(" ".join(cmd))
-    subprocess.run(cmd, check=True)
+    compile_flags = [f for f in FLAGS if f != "-shared"] + [f'-DPRIO3GPU_BUILD_HASH="{want}"']
+
+    def run(cmd):
+        if verbose:
+            print(" ".join(cmd))
+        subprocess.run(cmd, check=True)
+
+    def compile_one(src, obj):
+        run(["hipcc"] + compile_flags + ["-c", str(CSRC / src), "-o", obj])
+
+    # one object per source, compiled side by side (a device compile runs on one core), then one
+    # link; a failed step raises before the library in place is touched
+    with tempfile.TemporaryDirectory(dir=LIB_DIR, prefix="obj.") as objdir:
+        objs = [str(Path(objdir) / (Path(s).stem + ".o")) for s in SOURCES]
+        with ThreadPoolExecutor(max_workers=len(SOURCES)) as pool:
+            list(pool.map(compile_one, SOURCES, objs))
+        tmp = LIB_PATH.with_suffix(".so.tmp")
+        run(["hipcc"] + list(FLAGS) + ["-o", str(tmp)] + objs + list(LIBS))
     os.replace(tmp, LIB_PATH)
     return LIB_PATH
 

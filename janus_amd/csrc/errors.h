@@ -1,5 +1,5 @@
 // Thread-local last-error message shared by every translation unit of libprio3gpu.so
-// (engine.hip, codec.cpp, hpke.cpp); read through prio3gpu_last_error().
+// (engine.hip, engine_hpke.hip, codec.cpp, hpke.cpp); read through prio3gpu_last_error().
 #pragma once
 
 namespace p3g {

@@ -10,7 +10,7 @@
 //                       materialised
 //   k_decode_plaintext_input_shares   PlaintextInputShare -> helper input share row, then faults
 //   k_req_scatter       host-fallback reports' rows and statuses into place
-// Included by engine.hip after hpke_gpu.h and include/prio3gpu.h.
+// Included by engine_hpke.hip after include/prio3gpu.h.
 #pragma once
 #include "hpke_gpu.h"
 #include "request_parse.h"

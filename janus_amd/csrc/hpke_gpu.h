@@ -10,10 +10,11 @@
 // Each kernel is a thin shell around a per-lane device function (x25519_lane, hpke_open_lane over
 // a byte source for the AAD) that helper_request.h's kernels call too, with the request read in
 // place.  SHA-512, ChaCha20 and Poly1305 are hpke_prims.h's (free of HIP, tested on the CPU).
-// Included by engine.hip after prio3_kernels.h (SHA-256 is sha256_compress from there).
+// SHA-256 is sha256.h's.  Included by engine_hpke.hip.
 #pragma once
 #include "hpke_prims.h"
 #include "hpke_shared.h"
+#include "sha256.h"
 
 namespace p3g {
 

@@ -1,5 +1,6 @@
-// What the host half (hpke.cpp) and the GPU half (hpke_gpu.h, engine.hip) of the batched HPKE open
-// share: the values one batch of opens under ONE keypair has in common, computed once on the host.
+// What the host half (hpke.cpp) and the GPU half (hpke_gpu.h, engine_hpke.hip) of the batched HPKE
+// open share: the values one batch of opens under ONE keypair has in common, computed once on the
+// host.
 #pragma once
 #include <stddef.h>
 #include <stdint.h>

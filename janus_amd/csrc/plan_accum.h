@@ -1,7 +1,7 @@
 // Host planning of the segmented accumulation (k_accum_partial / k_accum_spec / k_accum_merge),
 // no HIP: which measurement elements k_jr column-sums, the chunk plan of one batch, and where
-// each host array lies in the two packed device buffers.  Included by engine.hip; built alone
-// with g++ by tests/test_host_plan.py.
+// each host array lies in the two packed device buffers.  Included by engine_internal.h (the
+// context keeps its last plan) and engine.hip; built alone with g++ by tests/test_host_plan.py.
 #pragma once
 #include <stddef.h>
 #include <stdint.h>

@@ -44,7 +44,9 @@ fn main() {
         .arg(format!("-DPRIO3GPU_BUILD_HASH=\"{hash}\""))
         .arg("-o")
         .arg(out.join("libprio3gpu.so"))
-        .args(["engine.hip", "codec.cpp", "hpke.cpp"].iter().map(|f| csrc.join(f)))
+        .args(
+            ["engine.hip", "engine_hpke.hip", "codec.cpp", "hpke.cpp"].iter().map(|f| csrc.join(f)),
+        )
         .args(["-lrccl", "-lcrypto"])
         .status()
         .expect("hipcc");

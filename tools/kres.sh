@@ -1,7 +1,10 @@
 #!/bin/bash
 # Print VGPR / occupancy of the main kernels (compile-only, no GPU):  tools/kres.sh [pattern]
-cd /tmp && hipcc --offload-arch=gfx950 -O3 -std=c++17 -fPIC -c --cuda-device-only -Rpass-analysis=kernel-resource-usage \
-  -o /tmp/kres.o /root/repo/janus_amd/csrc/engine.hip 2>&1 | python3 -c '
+C=$(cd "$(dirname "$0")/.." && pwd)/janus_amd/csrc
+for unit in engine.hip engine_hpke.hip; do
+  hipcc --offload-arch=gfx950 -O3 -std=c++17 -fPIC -c --cuda-device-only -Rpass-analysis=kernel-resource-usage \
+    -o /tmp/kres.o "$C/$unit" 2>&1
+done | python3 -c '
 import re,sys
 pat=sys.argv[1] if len(sys.argv)>1 else "Field128"
 cur=None
