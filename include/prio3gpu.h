@@ -169,8 +169,12 @@ int prio3gpu_ctx_set_async(prio3gpu_ctx* ctx, int on);
  *                   (default) only DHKEM(X25519, HKDF-SHA256) / HKDF-SHA256 / AES-128-GCM
  *                   (0x0020 / 1 / 1); 1 every X25519 suite Janus accepts, KDF HKDF-SHA256 /
  *                   -SHA384 / -SHA512 (1-3) x AEAD AES-128-GCM / AES-256-GCM / ChaCha20-Poly1305
- *                   (1-3).  P-256 keys are opened on the host either way.  Any other value is
- *                   PRIO3GPU_E_ARG
+ *                   (1-3).  It does not add a KEM: P-256 keys are the host's unless
+ *                   "hpke_gpu_p256" is on.  Any other value is PRIO3GPU_E_ARG
+ *   "hpke_gpu_p256"  0 (default): DHKEM(P-256, HKDF-SHA256) (KEM 0x0010) keys are opened on the
+ *                   host.  1: the GPU opens them too (k_p256_dh): 0x0010 / 1 / 1 with this option
+ *                   alone, all nine 0x0010 / KDF 1-3 / AEAD 1-3 with "hpke_gpu_suites" = 1 as
+ *                   well.  Independent of "hpke_gpu_suites".  Any other value is PRIO3GPU_E_ARG
  * The engine reads no environment variables.  PRIO3GPU_E_ARG for an unknown name. */
 int prio3gpu_ctx_set_option(prio3gpu_ctx* ctx, const char* name, int64_t value);
 /* Work queued on `ctx` from now on starts only after all work queued on `other` so far. */
@@ -527,14 +531,20 @@ int prio3gpu_hpke_open_report_shares(const uint8_t* task_id, const prio3gpu_hpke
  * by default the one Janus generates, DHKEM(X25519, HKDF-SHA256) / HKDF-SHA256 / AES-128-GCM
  * (0x0020 / 1 / 1); with the context option "hpke_gpu_suites" = 1 every X25519 suite (0x0020 /
  * KDF 1-3 / AEAD 1-3: HKDF-SHA256, -SHA384, -SHA512 x AES-128-GCM, AES-256-GCM,
- * ChaCha20-Poly1305).  Any other suite (P-256 always; the eight wider ones while the option is 0)
- * is PRIO3GPU_E_UNSUPPORTED with nothing launched (use the host functions above).  sk, pk and info
+ * ChaCha20-Poly1305); with "hpke_gpu_p256" = 1 the same choice under DHKEM(P-256, HKDF-SHA256)
+ * (KEM 0x0010).  Any other suite (P-256 while that option is 0; the wider KDFs and AEADs while
+ * "hpke_gpu_suites" is 0) is PRIO3GPU_E_UNSUPPORTED with nothing launched (use the host functions
+ * above).  sk is 32 bytes; pk and every enc are Nenc bytes, 32 for X25519 and 65 for KEM 0x0010
+ * (uncompressed points).  A P-256 keypair whose scalar is not in [1, n) or whose public key is no
+ * point on the curve is PRIO3GPU_E_HPKE with nothing launched, as the host's prio3gpu_hpke_open
+ * fails under it.  sk, pk and info
  * are host memory; every other pointer may be host or device (detected).  Report i has
- * enc = encs[32 i .. 32 i + 32), aad = aads[aad_offsets[i] .. aad_offsets[i+1]), ciphertext ||
+ * enc = encs[Nenc i .. Nenc i + Nenc), aad = aads[aad_offsets[i] .. aad_offsets[i+1]), ciphertext ||
  * tag = cts[ct_offsets[i] .. ct_offsets[i+1]) and its plaintext goes to pts[pt_offsets[i] ..
  * pt_offsets[i+1]) (room for the ciphertext length - 16; a longer slot is zero-filled).
  * status in/out: non-zero on entry = skipped (the slot is zeroed); a failed open -- bad tag,
- * ciphertext shorter than the tag, an all-zero DH value, offsets that do not fit -- sets 4
+ * ciphertext shorter than the tag, an all-zero X25519 DH value, a P-256 enc that is no valid
+ * point (prefix, coordinate range, curve equation), offsets that do not fit -- sets 4
  * (HpkeDecryptError) and writes zeros, never unauthenticated plaintext.  The private key reaches
  * the GPU only as a kernel argument; the device buffer that held the per-report DH values is
  * zeroed before the call returns.  Scratch belongs to the context (see prio3gpu_state_create). */
@@ -545,10 +555,11 @@ int prio3gpu_hpke_open_batch(prio3gpu_ctx* ctx, uint16_t kem_id, uint16_t kdf_id
                              const uint64_t* ct_offsets, uint8_t* pts, const uint64_t* pt_offsets,
                              uint8_t* status);
 /* prio3gpu_hpke_open_report_shares with the GPU opening every report whose first-choice key (task
- * key by config id, else global key) is of a suite above (as the context's "hpke_gpu_suites" option
- * selects), one batch per key: same arguments, offsets, statuses and key-selection order.  Reports
- * whose first choice is another suite (P-256; with the option at 0 also SHA-384/512, AES-256,
- * ChaCha20), and the global-key second trial after a failed task-key open, run on the host path
+ * key by config id, else global key) is of a suite above (as the context's "hpke_gpu_suites" and
+ * "hpke_gpu_p256" options select), one batch per key: same arguments, offsets, statuses and
+ * key-selection order.  Reports whose first choice is another suite (P-256 with "hpke_gpu_p256" at
+ * 0; with "hpke_gpu_suites" at 0 also SHA-384/512, AES-256, ChaCha20) or a malformed keypair, and
+ * the global-key second trial after a failed task-key open, run on the host path
  * on `threads` threads.  The plaintext slot of a report that ends with a
  * non-zero status is unspecified in both functions.  All pointers are host memory. */
 int prio3gpu_hpke_open_report_shares_gpu(prio3gpu_ctx* ctx, const uint8_t* task_id,
@@ -582,7 +593,8 @@ int prio3gpu_hpke_open_report_shares_gpu(prio3gpu_ctx* ctx, const uint8_t* task_
  *                  or device memory.  batch_slots / agg as in prio3gpu_helper_init.
  * Reports whose first-choice key (task key by config id, else global key) is X25519 / HKDF-SHA256
  * / AES-128-GCM -- or, with the context option "hpke_gpu_suites" = 1, any X25519 suite (KDF 1-3 x
- * AEAD 1-3) -- are opened and decoded on the GPU, one kernel pair per key.  The host path
+ * AEAD 1-3), and with "hpke_gpu_p256" = 1 the same under DHKEM(P-256, HKDF-SHA256) -- are opened
+ * and decoded on the GPU, one kernel pair per key.  The host path
  * (prio3gpu_hpke_open_report_shares + prio3gpu_decode_plaintext_input_shares on `threads`
  * threads) takes, inside the call, the reports whose first choice is another suite or a malformed
  * key, the global-key second trial after a failed task-key open, and the plaintexts whose

@@ -47,6 +47,17 @@ int prio3gpu_test_hpke_set_ifma(int on);
 int prio3gpu_test_x25519_gpu(prio3gpu_ctx* ctx, const uint8_t* sk, const uint8_t* points, size_t n,
                              uint8_t* out);
 
+/* TEST ONLY.  The GPU open's P-256 scalar multiplication alone (k_p256_dh without its KEM half,
+ * one lane per point), the counterpart of prio3gpu_test_x25519_gpu: for n 65-byte uncompressed
+ * encodings under one 32-byte big-endian scalar sk, out_x[32 i .. 32 i + 32) is the big-endian x
+ * coordinate of [sk] P_i and ok[i] = 1 -- or 32 zero bytes and ok[i] = 0 for an encoding
+ * DeserializePublicKey refuses (first byte not 0x04, a coordinate >= p, a point off the curve).
+ * An all-zero x with ok[i] = 1 is a result, not a failure.  sk = 0 or sk >= n returns
+ * PRIO3GPU_E_HPKE and launches nothing.  All host memory; n == 0 returns 0 and launches
+ * nothing. */
+int prio3gpu_test_p256_gpu(prio3gpu_ctx* ctx, const uint8_t* sk, const uint8_t* points, size_t n,
+                           uint8_t* out_x, uint8_t* ok);
+
 /* TEST ONLY.  The device Poly1305 (janus_amd/csrc/hpke_prims.h: poly1305_mac, RFC 8439 §2.5) alone,
  * one lane per message: tags[16 i .. 16 i + 16) is the MAC of msgs[msg_offsets[i] ..
  * msg_offsets[i + 1]) under keys[32 i .. 32 i + 32) (r || s; r is clamped inside).  The HPKE-level

@@ -67,7 +67,7 @@ const char* const kKernelNames[KID_COUNT] = {
     "k_flp_wires_mfma", "k_fpv_regen", "k_x25519", "k_hpke_open", "k_req_gather", "k_x25519_idx",
     "k_hpke_open_req", "k_decode_plaintext_input_shares", "k_req_scatter",
     // not a kernel: the request's one host-to-device copy in prio3gpu_helper_init_request
-    "copy_request"};
+    "copy_request", "k_p256_dh", "k_p256_dh_idx"};
 
 }  // namespace
 
@@ -1414,7 +1414,12 @@ int prio3gpu_ctx_set_option(prio3gpu_ctx* c, const char* name, int64_t value) {
       return PRIO3GPU_E_ARG;
     }
     c->hpke_gpu_suites = on;
-
+  } else if (k == "hpke_gpu_p256") {
+    if (value < 0 || value > 1) {
+      set_err("option hpke_gpu_p256: %lld is not 0 or 1", (long long)value);
+      return PRIO3GPU_E_ARG;
+    }
+    c->hpke_gpu_p256 = on;
   } else if (k == "expand_lds" || k == "jr_lds") {
     if (value < 0 || value > 160 * 1024) {
       set_err("option %s: %lld bytes is outside [0, 163840]", name, (long long)value);

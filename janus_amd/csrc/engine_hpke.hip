@@ -97,6 +97,49 @@ int launch_x25519_idx(prio3gpu_ctx* c, const uint8_t* sk, size_t m, const uint32
   });
 }
 
+// launch(ks, dc) with sk as a P-256 scalar (little-endian words from the 32 big-endian bytes) and
+// the batch's constants: pkRm's coordinates and the empty salt's pad states of bc.  The keypair
+// has passed p256_keypair_valid.  The scalar's host copy is wiped after the launch.
+template <class F>
+int with_p256_scalar(const uint8_t* sk, const uint8_t* pk, const HpkeBatchConsts& bc, F&& launch) {
+  P256Scalar ks;
+  for (int i = 0; i < 8; ++i)
+    ks.w[i] = (uint32_t)sk[31 - 4 * i] | ((uint32_t)sk[30 - 4 * i] << 8) |
+              ((uint32_t)sk[29 - 4 * i] << 16) | ((uint32_t)sk[28 - 4 * i] << 24);
+  P256DhConsts dc;
+  p256_load_be_words8(pk + 1, dc.pk.x);
+  p256_load_be_words8(pk + 33, dc.pk.y);
+  memcpy(dc.salt0_i, bc.salt0_i, sizeof dc.salt0_i);
+  memcpy(dc.salt0_o, bc.salt0_o, sizeof dc.salt0_o);
+  launch(ks, dc);
+  wipe(&ks, sizeof ks);
+  HIPCHK(hipGetLastError());
+  return 0;
+}
+
+// d_out[r] = the shared_secret (raw: x([sk] point)) and d_ok[r] for the n packed 65-byte points.
+int launch_p256_dh(prio3gpu_ctx* c, const uint8_t* sk, const uint8_t* pk,
+                   const HpkeBatchConsts& bc, bool raw, size_t n, const uint8_t* d_points,
+                   uint32_t* d_out, uint8_t* d_ok) {
+  return with_p256_scalar(sk, pk, bc, [&](const P256Scalar& ks, const P256DhConsts& dc) {
+    PROF(KID_P256_DH);
+    hipLaunchKernelGGL(k_p256_dh, dim3((unsigned)((n + 63) / 64)), dim3(64), 0, c->stream,
+                       (uint32_t)n, ks, dc, raw ? 1u : 0u, d_points, d_out, d_ok);
+  });
+}
+
+// The same over a key group of the request in device memory.
+int launch_p256_dh_idx(prio3gpu_ctx* c, const uint8_t* sk, const uint8_t* pk,
+                       const HpkeBatchConsts& bc, size_t m, const uint32_t* d_idx,
+                       const uint8_t* d_msg, const ReqView* d_views, uint32_t* d_ss,
+                       uint8_t* d_ok) {
+  return with_p256_scalar(sk, pk, bc, [&](const P256Scalar& ks, const P256DhConsts& dc) {
+    PROF(KID_P256_DH_IDX);
+    hipLaunchKernelGGL(k_p256_dh_idx, dim3((unsigned)((m + 63) / 64)), dim3(64), 0, c->stream,
+                       (uint32_t)m, ks, dc, d_idx, d_msg, d_views, d_ss, d_ok);
+  });
+}
+
 // check_request_views (plan_hpke.h) with its message in the thread's error string.
 int check_views(const Cfg& g, const prio3gpu_prepare_init_view* views, size_t n, size_t msg_len) {
   std::string err;
@@ -121,8 +164,11 @@ int launch_req_gather(prio3gpu_ctx* c, size_t n, const uint8_t* d_msg, size_t ms
 }
 
 // The suites the GPU opens on this context (plan_hpke.h).
+unsigned hpke_gpu_opts(const prio3gpu_ctx* c) {
+  return (c->hpke_gpu_suites ? HPKE_OPT_SUITES : 0u) | (c->hpke_gpu_p256 ? HPKE_OPT_P256 : 0u);
+}
 bool hpke_gpu_suite(const prio3gpu_ctx* c, uint16_t kem, uint16_t kdf, uint16_t aead) {
-  return p3g::hpke_gpu_suite(c->hpke_gpu_suites, kem, kdf, aead);
+  return p3g::hpke_gpu_suite(hpke_gpu_opts(c), kem, kdf, aead);
 }
 
 // f(KDF, AEAD) with the suite of bc as compile-time constants (one kernel instantiation each).
@@ -173,16 +219,18 @@ int launch_hpke_open_req(prio3gpu_ctx* c, const HpkeBatchConsts& bc, const ReqTa
   return 0;
 }
 
-int hpke_open_batch_impl(prio3gpu_ctx* c, uint16_t kdf_id, uint16_t aead_id, const uint8_t* sk,
+int hpke_open_batch_impl(prio3gpu_ctx* c, uint16_t kem_id, uint16_t kdf_id, uint16_t aead_id,
+                         const uint8_t* sk,
                          const uint8_t* pk, const uint8_t* info, size_t info_len, size_t n,
                          const uint8_t* encs, const uint8_t* aads, const uint64_t* aad_offsets,
                          const uint8_t* cts, const uint64_t* ct_offsets, uint8_t* pts,
                          const uint64_t* pt_offsets, uint8_t* status) {
   HpkeBatchConsts bc;
-  if (!hpke_batch_consts(kdf_id, aead_id, pk, info, info_len, &bc)) {
+  if (!hpke_batch_consts(kem_id, kdf_id, aead_id, pk, info, info_len, &bc)) {
     set_err("HPKE primitives unavailable");
     return PRIO3GPU_E_UNSUPPORTED;
   }
+  const bool p256 = kem_id == 0x0010;
   HIPCHK(hipSetDevice(c->device));
   uint64_t aad_total = 0, ct_total = 0, pt_total = 0, pt_first = 0;
   CHK(hpke_fetch_u64(c, aad_offsets + n, &aad_total));
@@ -194,7 +242,7 @@ int hpke_open_batch_impl(prio3gpu_ctx* c, uint16_t kdf_id, uint16_t aead_id, con
     return PRIO3GPU_E_ARG;
   }
   const uint8_t *d_enc, *d_aad, *d_aoff, *d_ct, *d_coff, *d_poff, *d_st_in;
-  CHK(stage_in(c, c->hpke[0], encs, n * 32, &d_enc, kHpkeMinStage));
+  CHK(stage_in(c, c->hpke[0], encs, n * bc.nenc, &d_enc, kHpkeMinStage));
   CHK(stage_in(c, c->hpke[1], aads, aad_total, &d_aad, kHpkeMinStage));
   CHK(stage_in(c, c->hpke[2], aad_offsets, (n + 1) * 8, &d_aoff, kHpkeMinStage));
   CHK(stage_in(c, c->hpke[3], cts, ct_total, &d_ct, kHpkeMinStage));
@@ -209,15 +257,24 @@ int hpke_open_batch_impl(prio3gpu_ctx* c, uint16_t kdf_id, uint16_t aead_id, con
     d_pt = c->hpke[5].u8();
     if (pt_total) HIPCHK(hipMemsetAsync(d_pt, 0, pt_total, c->stream));
   }
-  CHK(c->hpke[8].ensure(n * 32));
+  // per report 32 bytes of DH value (P-256: shared secret) and, for P-256, one validity byte
+  const size_t dh_bytes = n * (p256 ? 33 : 32);
+  CHK(c->hpke[8].ensure(dh_bytes));
   uint32_t* d_dh = static_cast<uint32_t*>(c->hpke[8].p);
-  int rc = launch_x25519(c, sk, n, d_enc, d_dh);
+  int rc;
+  if (p256) {
+    uint8_t* d_ok = c->hpke[8].u8() + n * 32;
+    bc.dh_ok = d_ok;
+    rc = launch_p256_dh(c, sk, pk, bc, /*raw=*/false, n, d_enc, d_dh, d_ok);
+  } else {
+    rc = launch_x25519(c, sk, n, d_enc, d_dh);
+  }
   if (!rc)
     rc = launch_hpke_open(c, bc, n, d_dh, d_enc, d_aad, reinterpret_cast<const uint64_t*>(d_aoff),
                           aad_total, d_ct, reinterpret_cast<const uint64_t*>(d_coff), ct_total,
                           d_pt, reinterpret_cast<const uint64_t*>(d_poff), pt_total, d_st);
   // the per-report secrets: the DH values (keys and nonces never leave registers)
-  if (hipMemsetAsync(d_dh, 0, n * 32, c->stream) != hipSuccess && !rc) {
+  if (hipMemsetAsync(d_dh, 0, dh_bytes, c->stream) != hipSuccess && !rc) {
     set_err("clearing the DH values failed");
     rc = PRIO3GPU_E_HIP;
   }
@@ -260,12 +317,13 @@ int open_group_packed(prio3gpu_ctx* c, const HpkePlan& plan, size_t k, const uin
     b.coff[j + 1] = b.coff[j] + v.payload_len;
     b.poff[j + 1] = b.poff[j] + (v.payload_len - 16);
   }
-  b.encs.resize(m * 32), b.aads.resize(b.aoff[m]), b.cts.resize(b.coff[m]);
+  const size_t nenc = hpke_kem_nenc(kp->kem_id);  // every member's enc_len (strict plan)
+  b.encs.resize(m * nenc), b.aads.resize(b.aoff[m]), b.cts.resize(b.coff[m]);
   // the fields of one report lie kilobytes apart in the request (its prep share is between
   // them): the gather is DRAM-latency-bound on one thread, so it runs on the host threads
   host_parallel(m, threads, [&](size_t j) {
     const prio3gpu_prepare_init_view& v = views[idx[j]];
-    memcpy(&b.encs[j * 32], msg + v.enc_off, 32);
+    memcpy(&b.encs[j * nenc], msg + v.enc_off, nenc);
     uint8_t* a = &b.aads[b.aoff[j]];  // task id, report id, time, u32-prefixed public share
     memcpy(a, task_id, 32);
     memcpy(a + 32, msg + v.report_id_off, 16);
@@ -276,7 +334,8 @@ int open_group_packed(prio3gpu_ctx* c, const HpkePlan& plan, size_t k, const uin
   });
   b.pts.assign(std::max<size_t>(b.poff.back(), 1), 0);
   b.st.assign(m, 0);
-  CHK(hpke_open_batch_impl(c, kp->kdf_id, kp->aead_id, kp->private_key, kp->public_key, info, 20,
+  CHK(hpke_open_batch_impl(c, kp->kem_id, kp->kdf_id, kp->aead_id, kp->private_key,
+                           kp->public_key, info, 20,
                            m, b.encs.data(), b.aads.data(), b.aoff.data(), b.cts.data(),
                            b.coff.data(), b.pts.data(), b.poff.data(), b.st.data()));
   for (size_t j = 0; j < m; ++j) {
@@ -328,7 +387,7 @@ int req_plan(ReqCall& q, const prio3gpu_hpke_keypair* task_keys, size_t n_task_k
   q.poff.resize(q.n + 1);
   plaintext_offsets(q.views, q.n, q.poff.data());
   plan_hpke(task_keys, n_task_keys, global_keys, n_global_keys, q.views, status, q.n,
-            q.c->hpke_gpu_suites, /*strict=*/false, &q.plan);
+            hpke_gpu_opts(q.c), /*strict=*/false, &q.plan);
   q.dst.resize(q.n);
   request_status_image(q.plan, status, q.n, q.dst.data());
   uint8_t info[20];
@@ -336,8 +395,8 @@ int req_plan(ReqCall& q, const prio3gpu_hpke_keypair* task_keys, size_t n_task_k
   q.bcs.resize(q.plan.groups.size());
   for (size_t k = 0; k < q.bcs.size(); ++k) {
     const prio3gpu_hpke_keypair* kp = q.plan.groups[k];
-    if (!hpke_batch_consts(kp->kdf_id, kp->aead_id, kp->public_key, info, sizeof info,
-                           &q.bcs[k])) {
+    if (!hpke_batch_consts(kp->kem_id, kp->kdf_id, kp->aead_id, kp->public_key, info,
+                           sizeof info, &q.bcs[k])) {
       set_err("HPKE primitives unavailable");
       return PRIO3GPU_E_UNSUPPORTED;
     }
@@ -356,7 +415,7 @@ int req_reserve(ReqCall& q) {
   q.in_pitch = input_pitch(st);
   CHK(c->req[1].ensure(n * sizeof(ReqView)));
   CHK(c->req[2].ensure(std::max<size_t>(q.plan.idx.size(), 1) * 4));
-  CHK(c->req[3].ensure(n * 32));
+  CHK(c->req[3].ensure(n * 33));  // DH values / shared secrets, then P-256's validity bytes
   CHK(c->req[4].ensure(std::max<uint64_t>(q.poff[n], 16)));
   CHK(c->req[5].ensure((n + 1) * 8));
   CHK(c->req[6].ensure(n));
@@ -403,8 +462,15 @@ int req_open_groups(ReqCall& q) {
   for (size_t k = 0; k < q.plan.groups.size(); ++k) {
     const size_t m = q.plan.gbeg[k + 1] - q.plan.gbeg[k];
     const uint32_t* d_idx = q.d_idx + q.plan.gbeg[k];
-    CHK(launch_x25519_idx(q.c, q.plan.groups[k]->private_key, m, d_idx, q.d_msg, q.d_views,
-                          q.d_dh));
+    const prio3gpu_hpke_keypair* kp = q.plan.groups[k];
+    if (kp->kem_id == 0x0010) {
+      uint8_t* d_ok = reinterpret_cast<uint8_t*>(q.d_dh) + q.n * 32;
+      q.bcs[k].dh_ok = d_ok;
+      CHK(launch_p256_dh_idx(q.c, kp->private_key, kp->public_key, q.bcs[k], m, d_idx, q.d_msg,
+                             q.d_views, q.d_dh, d_ok));
+    } else {
+      CHK(launch_x25519_idx(q.c, kp->private_key, m, d_idx, q.d_msg, q.d_views, q.d_dh));
+    }
     CHK(launch_hpke_open_req(q.c, q.bcs[k], q.tid, m, d_idx, q.d_dh, q.d_msg, q.d_views, q.d_pts,
                              q.d_poff, q.d_status));
   }
@@ -491,7 +557,7 @@ int req_host_fallback(ReqCall& q) {
 // values and the plaintexts on the device, the fallback's vectors on the host.
 int req_clear_secrets(ReqCall& q, int rc) {
   prio3gpu_ctx* c = q.c;
-  bool cleared = hipMemsetAsync(q.d_dh, 0, q.n * 32, c->stream) == hipSuccess;
+  bool cleared = hipMemsetAsync(q.d_dh, 0, q.n * 33, c->stream) == hipSuccess;
   if (q.poff[q.n])
     cleared &= hipMemsetAsync(q.d_pts, 0, q.poff[q.n], c->stream) == hipSuccess;
   if (!cleared && !rc) {
@@ -523,16 +589,23 @@ int prio3gpu_hpke_open_batch(prio3gpu_ctx* c, uint16_t kem_id, uint16_t kdf_id, 
     set_err("HPKE suite 0x%04x/%u/%u is not opened on the GPU", kem_id, kdf_id, aead_id);
     return PRIO3GPU_E_UNSUPPORTED;
   }
-  if (!sk || sk_len != 32 || !pk || pk_len != 32 || (info_len && !info)) {
-    set_err("HPKE open: X25519 keys are 32 bytes");
+  const size_t npk = hpke_kem_nenc(kem_id);
+  if (!sk || sk_len != 32 || !pk || pk_len != npk || (info_len && !info)) {
+    set_err("HPKE open: the private key is 32 bytes, the public key %zu", npk);
     return PRIO3GPU_E_ARG;
+  }
+  // a P-256 scalar outside [1, n) fails the host's open of every report with this code; a public
+  // key that is no point can have sealed nothing
+  if (kem_id == 0x0010 && !p256_keypair_valid(sk, sk_len, pk, pk_len)) {
+    set_err("HPKE open: not a P-256 keypair");
+    return PRIO3GPU_E_HPKE;
   }
   if (n == 0) return 0;
   if (!encs || !aad_offsets || !ct_offsets || !pt_offsets || !status || n > 0x7FFFFFFFu) {
     set_err("HPKE open: null argument");
     return PRIO3GPU_E_ARG;
   }
-  return hpke_open_batch_impl(c, kdf_id, aead_id, sk, pk, info, info_len, n, encs, aads,
+  return hpke_open_batch_impl(c, kem_id, kdf_id, aead_id, sk, pk, info, info_len, n, encs, aads,
                               aad_offsets, cts, ct_offsets, pts, pt_offsets, status);
 }
 
@@ -556,7 +629,7 @@ int prio3gpu_hpke_open_report_shares_gpu(
   // keys or encapsulated keys, unknown ids) is the host path's, untouched.
   HpkePlan plan;
   plan_hpke(task_keys, n_task_keys, global_keys, n_global_keys, views, status, n,
-            c->hpke_gpu_suites, /*strict=*/true, &plan);
+            hpke_gpu_opts(c), /*strict=*/true, &plan);
   uint8_t info[20];
   input_share_info(sender_role, recipient_role, info);
   // the status arrays of the two host passes: 0 selects a report
@@ -693,6 +766,41 @@ int prio3gpu_test_x25519_gpu(prio3gpu_ctx* c, const uint8_t* sk, const uint8_t* 
   }
   HIPCHK(hipStreamSynchronize(c->stream));
   return 0;
+}
+
+int prio3gpu_test_p256_gpu(prio3gpu_ctx* c, const uint8_t* sk, const uint8_t* points, size_t n,
+                           uint8_t* out_x, uint8_t* ok) {
+  if (!c || !sk || (n && (!points || !out_x || !ok)) || n > 0x7FFFFFFFu) {
+    set_err("null argument");
+    return PRIO3GPU_E_ARG;
+  }
+  if (!p256_scalar_valid(sk)) {
+    set_err("P-256 scalar outside [1, n)");
+    return PRIO3GPU_E_HPKE;
+  }
+  if (n == 0) return 0;
+  // the generator stands in for pkRm: a refused encoding's lane runs over it
+  static const uint8_t kG[65] = {
+      0x04, 0x6b, 0x17, 0xd1, 0xf2, 0xe1, 0x2c, 0x42, 0x47, 0xf8, 0xbc, 0xe6, 0xe5, 0x63, 0xa4,
+      0x40, 0xf2, 0x77, 0x03, 0x7d, 0x81, 0x2d, 0xeb, 0x33, 0xa0, 0xf4, 0xa1, 0x39, 0x45, 0xd8,
+      0x98, 0xc2, 0x96, 0x4f, 0xe3, 0x42, 0xe2, 0xfe, 0x1a, 0x7f, 0x9b, 0x8e, 0xe7, 0xeb, 0x4a,
+      0x7c, 0x0f, 0x9e, 0x16, 0x2b, 0xce, 0x33, 0x57, 0x6b, 0x31, 0x5e, 0xce, 0xcb, 0xb6, 0x40,
+      0x68, 0x37, 0xbf, 0x51, 0xf5};
+  HpkeBatchConsts bc{};  // raw mode hashes nothing: the pad states are not read
+  HIPCHK(hipSetDevice(c->device));
+  const uint8_t* d_pts;
+  CHK(stage_in(c, c->hpke[0], points, n * 65, &d_pts, kHpkeMinStage));
+  CHK(c->hpke[8].ensure(n * 33));
+  uint8_t* d_out = c->hpke[8].u8();
+  int rc = launch_p256_dh(c, sk, kG, bc, /*raw=*/true, n, d_pts,
+                          reinterpret_cast<uint32_t*>(d_out), d_out + n * 32);
+  if (!rc && hipMemcpyAsync(out_x, d_out, n * 32, hipMemcpyDeviceToHost, c->stream) != hipSuccess)
+    rc = PRIO3GPU_E_HIP;
+  if (!rc && hipMemcpyAsync(ok, d_out + n * 32, n, hipMemcpyDeviceToHost, c->stream) != hipSuccess)
+    rc = PRIO3GPU_E_HIP;
+  (void)hipMemsetAsync(d_out, 0, n * 33, c->stream);
+  HIPCHK(hipStreamSynchronize(c->stream));
+  return rc;
 }
 
 int prio3gpu_test_poly1305_gpu(prio3gpu_ctx* c, const uint8_t* keys, const uint8_t* msgs,

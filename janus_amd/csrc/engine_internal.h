@@ -86,7 +86,7 @@ enum KernelId {
   KID_SHARD_MEAS, KID_SHARD_JR, KID_PROVE, KID_SHARD_PROOF, KID_REPORT_META, KID_REPORT_META_FOLD,
   KID_SHARD_NORM, KID_JR_RING, KID_FLP_QUERY_LANE, KID_FLP_WIRES_COLS, KID_FLP_WIRES_MFMA,
   KID_FPV_REGEN, KID_X25519, KID_HPKE_OPEN, KID_REQ_GATHER, KID_X25519_IDX, KID_HPKE_OPEN_REQ,
-  KID_DECODE_PT, KID_REQ_SCATTER, KID_REQ_COPY, KID_COUNT
+  KID_DECODE_PT, KID_REQ_SCATTER, KID_REQ_COPY, KID_P256_DH, KID_P256_DH_IDX, KID_COUNT
 };
 
 // Per-kernel HIP-event timing on the context's stream (opt-in; used by bench.py).
@@ -132,7 +132,8 @@ struct prio3gpu_ctx {
   DevBuf io[6];
   DevBuf perm, chunks, partials, pcounts, spec_idx;
   // prio3gpu_hpke_open_batch: staging of host inputs / outputs (enc, aad, aad offsets, ct, ct
-  // offsets, pt, pt offsets, status) and the ladder's DH values; grown on demand
+  // offsets, pt, pt offsets, status) and the ladder's DH values (for P-256 the shared secrets
+  // and, behind them, one validity byte per report); grown on demand
   DevBuf hpke[9];
   // prio3gpu_helper_init_request: the request, its views, key-group index lists, DH values,
   // plaintexts, plaintext offsets, faults, and the host-fallback reports' compact rows; grown on
@@ -168,6 +169,9 @@ struct prio3gpu_ctx {
   // "hpke_gpu_suites": which HPKE suites the GPU opens (hpke_gpu_suite): 0 only X25519 /
   // HKDF-SHA256 / AES-128-GCM, 1 every X25519 suite (KDF 1-3 x AEAD 1-3)
   bool hpke_gpu_suites = false;
+  // "hpke_gpu_p256": 1 lets the GPU open DHKEM(P-256, HKDF-SHA256) too (k_p256_dh): with
+  // HKDF-SHA256 / AES-128-GCM, and with every KDF and AEAD when "hpke_gpu_suites" is on as well
+  bool hpke_gpu_p256 = false;
   size_t expand_lds = 0;     // "expand_lds": dynamic LDS per k_expand block (occupancy cap)
   size_t jr_lds = 0;         // "jr_lds": dynamic LDS per k_jr block (occupancy cap)
   uint32_t cus = 0;          // compute units of the device

@@ -5,6 +5,7 @@
 // the host has checked against the message length.
 //   k_req_gather        nonces, public shares, leader prep shares -> rows; faults[i]
 //   k_x25519_idx        k_x25519 over a key group (a list of report indices), enc read in place
+//   k_p256_dh_idx       k_p256_dh over a key group, enc read in place
 //   k_hpke_open_req     hpke_open_lane (of the group's suite) over a key group: enc and ciphertext
 //                       in place, the InputShareAad assembled from its five pieces, never
 //                       materialised
@@ -94,6 +95,26 @@ __global__ void __launch_bounds__(64) k_x25519_idx(uint32_t m, X25519Scalar k, c
   }
 }
 
+// ss[idx[j]] = the P-256 shared_secret of (k, enc of report idx[j]) and ok[idx[j]] = 1 for the m
+// reports of a key group; zeros and 0 for an enc DeserializePublicKey refuses or whose length is
+// not 65 (not read: k_hpke_open_req rejects that one by its length).
+__global__ void __launch_bounds__(64) k_p256_dh_idx(uint32_t m, P256Scalar k, P256DhConsts dc,
+                                                    const uint32_t* idx, const uint8_t* msg,
+                                                    const ReqView* views, uint32_t* ss,
+                                                    uint8_t* ok) {
+  const uint32_t j = blockIdx.x * blockDim.x + threadIdx.x;
+  const bool live = j < m;
+  const uint32_t r = idx[live ? j : m - 1];
+  const ReqView& v = views[r];
+  uint32_t w[8];
+  const bool good = p256_lane_out(k, dc, 0u, msg + v.enc_off, v.enc_len == 65, w);
+  if (live) {
+#pragma unroll
+    for (int i = 0; i < 8; ++i) ss[(size_t)r * 8 + i] = w[i];
+    ok[r] = good ? 1 : 0;
+  }
+}
+
 struct ReqTaskId {  // the 32-byte TaskId as block words (byte j at bits 8 (j & 3) of word j >> 2)
   uint32_t w[8];
 };
@@ -130,7 +151,7 @@ struct ReqAad {
 
 // One lane per report of a key group: hpke_open_lane with enc, ciphertext and AAD read where the
 // request has them; report r's plaintext goes to pts[pt_off[r] .. pt_off[r + 1]).  An enc_len
-// other than 32, a payload shorter than the tag or longer than its slot: status 4, nothing read.
+// other than the KEM's Nenc (32; 65 for P-256), a payload shorter than the tag or longer than its slot: status 4, nothing read.
 // (KDF, AEAD) is the group's suite, as for k_hpke_open.
 template <int KDF, int AEAD>
 __global__ void __launch_bounds__(256) k_hpke_open_req(
@@ -152,13 +173,14 @@ __global__ void __launch_bounds__(256) k_hpke_open_req(
   uint8_t* pt = pts + p0;
   const bool skip = status[r] != 0;
   const uint32_t clen = v.payload_len;
-  if (skip || v.enc_len != 32 || clen < 16 || clen - 16 > pt_cap) {
+  if (skip || v.enc_len != bc.nenc || clen < 16 || clen - 16 > pt_cap) {
     hpke_open_reject(pt, pt_cap, status + r, skip);
     return;
   }
   const ReqAad aad{tid, msg + v.report_id_off, v.time, v.public_share_len,
                    msg + v.public_share_off};
-  hpke_open_lane<KDF, AEAD>(sbox, bc, dh + (size_t)r * 8, msg + v.enc_off, aad,
+  hpke_open_lane<KDF, AEAD>(sbox, bc, dh + (size_t)r * 8, bc.dh_ok ? bc.dh_ok[r] : 1u,
+                            msg + v.enc_off, aad,
                             msg + v.payload_off, (uint64_t)clen - 16, pt, pt_cap, status + r);
 }
 

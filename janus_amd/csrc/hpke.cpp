@@ -787,10 +787,10 @@ void parallel_for(size_t n, int threads, F&& f) {
 
 // The batch-shared inputs of the GPU open (hpke_gpu.h): psk_id_hash and info_hash of the suite's
 // key schedule, and the HMAC-SHA256 pad states of the empty salt (the KEM's), as big-endian words.
-bool p3g::hpke_batch_consts(uint16_t kdf_id, uint16_t aead_id, const uint8_t* pk,
+bool p3g::hpke_batch_consts(uint16_t kem_id, uint16_t kdf_id, uint16_t aead_id, const uint8_t* pk,
                             const uint8_t* info, size_t info_len, HpkeBatchConsts* out) {
   Suite s;
-  if (!suite_of(KEM_X25519, kdf_id, aead_id, &s)) return false;
+  if (!suite_of(kem_id, kdf_id, aead_id, &s)) return false;
   const EVP_MD* md = algs().md[s.kdf];
   Bytes sid;
   sid.add("HPKE").u16(s.kem).u16(s.kdf).u16(s.aead);
@@ -805,7 +805,8 @@ bool p3g::hpke_batch_consts(uint16_t kdf_id, uint16_t aead_id, const uint8_t* pk
   };
   memset(out, 0, sizeof *out);
   out->kdf_id = s.kdf, out->aead_id = s.aead;
-  be(out->pk, pk, 8);
+  out->kem_lo = s.kem & 0xffu, out->nenc = uint32_t(s.nenc);
+  if (s.kem == KEM_X25519) be(out->pk, pk, 8);
   be(out->psk_id_hash, psk_id_hash, int(s.nh / 4));
   be(out->info_hash, info_hash, int(s.nh / 4));
   uint8_t pad[64];

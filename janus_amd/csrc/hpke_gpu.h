@@ -1,10 +1,12 @@
-// Batched HPKE open on the GPU for DHKEM(X25519, HKDF-SHA256) with every KDF and AEAD Janus
+// Batched HPKE open on the GPU for DHKEM(X25519, HKDF-SHA256) and, behind the context's
+// "hpke_gpu_p256" option, DHKEM(P-256, HKDF-SHA256) (p256.h) with every KDF and AEAD Janus
 // accepts, RFC 9180 base mode, single shot: 0x0020 / 1 / 1 is the suite Janus generates by default
 // (core/src/hpke.rs:204-231) and the helper opens once per report (aggregator.rs:1634-1700); the
 // other eight (KDF HKDF-SHA256 / -SHA384 / -SHA512 x AEAD AES-128-GCM / AES-256-GCM /
 // ChaCha20-Poly1305) are opened when the context's "hpke_gpu_suites" option is on.
 // One lane per report, every report of a launch under ONE private key, hence one suite:
 //   k_x25519                dh = X25519(skR, enc)                     RFC 7748 §5
+//   k_p256_dh               x([skR] enc), validity flag, shared_secret RFC 9180 §4.1, §7.1
 //   k_hpke_open<KDF, AEAD>  shared_secret, key schedule, the AEAD     RFC 9180 §4.1, §5.1;
 //                                                     NIST SP 800-38D (GCM); RFC 8439 (ChaCha20)
 // Each kernel is a thin shell around a per-lane device function (x25519_lane, hpke_open_lane over
@@ -15,6 +17,7 @@
 #include "hpke_prims.h"
 #include "hpke_shared.h"
 #include "sha256.h"
+#include "p256_kem.h"
 
 namespace p3g {
 
@@ -284,6 +287,42 @@ __global__ void __launch_bounds__(64) k_x25519(uint32_t n, X25519Scalar k, const
   }
 }
 
+// The batch-shared inputs of the P-256 DH kernels: pkRm's coordinates and the HMAC-SHA256 pad
+// states of the empty salt (the KEM half runs in the DH kernel).
+struct P256DhConsts {
+  P256PublicKey pk;
+  uint32_t salt0_i[8], salt0_o[8];
+};
+
+// One lane of k_p256_dh / k_p256_dh_idx: p256_dh_lane over enc (65 bytes, read only if present).
+// out gets 32 bytes as 8 words, zero for a refused enc: the shared_secret, or with raw set
+// (prio3gpu_test_p256_gpu) the big-endian x coordinate of [k] enc itself.
+DEVI bool p256_lane_out(const P256Scalar& k, const P256DhConsts& dc, uint32_t raw,
+                        const uint8_t* enc, bool present, uint32_t out[8]) {
+  uint32_t ss[8];
+  const bool ok = p256_dh_lane(k, dc.pk, dc.salt0_i, dc.salt0_o, enc, present, raw != 0u, ss);
+#pragma unroll
+  for (int i = 0; i < 8; ++i) out[i] = bswap32(ss[i]);
+  return ok;
+}
+
+// out[r] = the shared_secret of (k, points[r]) and ok[r] = 1, or zeros and ok[r] = 0 for an
+// encoding DeserializePublicKey refuses; one lane per packed 65-byte point.  The scalar is a
+// kernel argument: no device buffer ever holds the private key.
+__global__ void __launch_bounds__(64) k_p256_dh(uint32_t n, P256Scalar k, P256DhConsts dc,
+                                                uint32_t raw, const uint8_t* points, uint32_t* out,
+                                                uint8_t* ok) {
+  const uint32_t r = blockIdx.x * blockDim.x + threadIdx.x;
+  const bool live = r < n;
+  uint32_t w[8];
+  const bool good = p256_lane_out(k, dc, raw, points + (size_t)(live ? r : n - 1) * 65, true, w);
+  if (live) {
+#pragma unroll
+    for (int i = 0; i < 8; ++i) out[(size_t)r * 8 + i] = w[i];
+    ok[r] = good ? 1 : 0;
+  }
+}
+
 // ------------------------------------------------------------------------------------------------
 // HMAC-SHA256 over fixed-layout messages.  A message is built in registers as big-endian words at
 // compile-time byte offsets (constant bytes fold into the schedule); sha256_compress does the rest.
@@ -351,12 +390,13 @@ DEVI void msg_kem_prefix(uint32_t* w, int off) {
   msg_str(w, off + 7, "KEM");
   msg_byte(w, off + 11, 0x20u);
 }
-// "HPKE-v1" || suite_id("HPKE" || 0x0020 || 0x0001 || aead) at off (17 bytes)
+// "HPKE-v1" || suite_id("HPKE" || kem || 0x0001 || aead) at off (17 bytes); kem_lo is the KEM id's
+// low byte (wave-uniform)
 template <int AEAD>
-DEVI void msg_hpke_prefix(uint32_t* w, int off) {
+DEVI void msg_hpke_prefix(uint32_t* w, int off, uint32_t kem_lo) {
   msg_str(w, off, "HPKE-v1");
   msg_str(w, off + 7, "HPKE");
-  msg_byte(w, off + 12, 0x20u);
+  msg_byte(w, off + 12, kem_lo);
   msg_byte(w, off + 14, 0x01u);
   msg_byte(w, off + 16, (uint32_t)AEAD);
 }
@@ -364,41 +404,49 @@ DEVI void msg_hpke_prefix(uint32_t* w, int off) {
 // (dh, enc) -> the AEAD key (Nk / 4 BE words) and base nonce (3 BE words): ExtractAndExpand of
 // the DHKEM (RFC 9180 §4.1; HKDF-SHA256 for every suite) and KeySchedule(mode_base) (§5.1) under
 // the suite's KDF.  19 SHA-256 compressions for KDF 1; 9 and 12 SHA-512 compressions otherwise.
+// With bc.dh_ok set (P-256) dh already is the shared_secret and the KEM half is skipped, on a
+// wave-uniform branch.
 template <int KDF, int AEAD>
 DEVI void hpke_key_nonce(const HpkeBatchConsts& bc, const uint32_t dh[8], const uint32_t enc[8],
                          uint32_t* key, uint32_t nonce[3]) {
   constexpr int NK = hpke_aead_nk(AEAD);
   uint32_t w[32], ist[8], ost[8], prk[8], ss[8], secret[8], t[8];
-  // eae_prk = LabeledExtract("", "eae_prk", dh)
+  if (bc.dh_ok) {
 #pragma unroll
-  for (int i = 0; i < 16; ++i) w[i] = 0;
-  msg_kem_prefix(w, 0);
-  msg_str(w, 12, "eae_prk");
-  msg_words8(w, 19, dh);
-  msg_pad(w, 51, 1);
-  hmac_finish<1>(bc.salt0_i, bc.salt0_o, w, prk);
-  // shared_secret = LabeledExpand(eae_prk, "shared_secret", enc || pkR, 32)
-  hmac_pads(prk, ist, ost);
+    for (int i = 0; i < 8; ++i) ss[i] = dh[i];
+  } else {
+    // eae_prk = LabeledExtract("", "eae_prk", dh)
 #pragma unroll
-  for (int i = 0; i < 32; ++i) w[i] = 0;
-  msg_byte(w, 1, 32u);
-  msg_kem_prefix(w, 2);
-  msg_str(w, 14, "shared_secret");
-  msg_words8(w, 27, enc);
-  msg_words8(w, 59, bc.pk);
-  msg_byte(w, 91, 1u);
-  msg_pad(w, 92, 2);
-  hmac_finish<2>(ist, ost, w, ss);
+    for (int i = 0; i < 16; ++i) w[i] = 0;
+    msg_kem_prefix(w, 0);
+    msg_str(w, 12, "eae_prk");
+    msg_words8(w, 19, dh);
+    msg_pad(w, 51, 1);
+    hmac_finish<1>(bc.salt0_i, bc.salt0_o, w, prk);
+    // shared_secret = LabeledExpand(eae_prk, "shared_secret", enc || pkR, 32)
+    hmac_pads(prk, ist, ost);
+#pragma unroll
+    for (int i = 0; i < 32; ++i) w[i] = 0;
+    msg_byte(w, 1, 32u);
+    msg_kem_prefix(w, 2);
+    msg_str(w, 14, "shared_secret");
+    msg_words8(w, 27, enc);
+    msg_words8(w, 59, bc.pk);
+    msg_byte(w, 91, 1u);
+    msg_pad(w, 92, 2);
+    hmac_finish<2>(ist, ost, w, ss);
+  }
   if constexpr (KDF != 1) {
     uint64_t secret64[8];
-    hpke_kdf512_key_nonce<KDF, AEAD>(ss, bc.psk_id_hash, bc.info_hash, secret64, key, nonce);
+    hpke_kdf512_key_nonce<KDF, AEAD>(ss, bc.psk_id_hash, bc.info_hash, secret64, key, nonce,
+                                     bc.kem_lo);
     return;
   }
   // secret = LabeledExtract(shared_secret, "secret", psk = "")
   hmac_pads(ss, ist, ost);
 #pragma unroll
   for (int i = 0; i < 16; ++i) w[i] = 0;
-  msg_hpke_prefix<AEAD>(w, 0);
+  msg_hpke_prefix<AEAD>(w, 0, bc.kem_lo);
   msg_str(w, 17, "secret");
   msg_pad(w, 23, 1);
   hmac_finish<1>(ist, ost, w, secret);
@@ -408,7 +456,7 @@ DEVI void hpke_key_nonce(const HpkeBatchConsts& bc, const uint32_t dh[8], const 
 #pragma unroll
   for (int i = 0; i < 32; ++i) w[i] = 0;
   msg_byte(w, 1, (uint32_t)NK);
-  msg_hpke_prefix<AEAD>(w, 2);
+  msg_hpke_prefix<AEAD>(w, 2, bc.kem_lo);
   msg_str(w, 19, "key");
   msg_words8(w, 23, bc.psk_id_hash);
   msg_words8(w, 55, bc.info_hash);
@@ -421,7 +469,7 @@ DEVI void hpke_key_nonce(const HpkeBatchConsts& bc, const uint32_t dh[8], const 
 #pragma unroll
   for (int i = 0; i < 32; ++i) w[i] = 0;
   msg_byte(w, 1, 12u);
-  msg_hpke_prefix<AEAD>(w, 2);
+  msg_hpke_prefix<AEAD>(w, 2, bc.kem_lo);
   msg_str(w, 19, "base_nonce");
   msg_words8(w, 30, bc.psk_id_hash);
   msg_words8(w, 62, bc.info_hash);
@@ -560,23 +608,33 @@ DEVI void hpke_open_reject(uint8_t* pt, uint64_t pt_cap, uint8_t* status, bool s
   if (!skip) *status = ST_HPKE_DECRYPT;
 }
 
-// One report, one lane: derive (key, base_nonce) from the lane's dh (8 words as k_x25519 wrote
-// them) and enc (32 bytes), check the AEAD's tag over aad || ct[0 .. body), then write the
-// plaintext to pt[0 .. body) and zeros up to pt_cap -- or zeros and status 4 when the tag does not
-// match or dh is all zero (RFC 9180 §7.1.4): never unauthenticated plaintext.  ct holds body + 16
+// One report, one lane: derive (key, base_nonce) from the lane's dh (8 words as k_x25519 or
+// k_p256_dh wrote them) and enc (32 bytes; not read for P-256), check the AEAD's tag over aad ||
+// ct[0 .. body), then write the plaintext to pt[0 .. body) and zeros up to pt_cap -- or zeros and
+// status 4 when the tag does not match or the DH failed: never unauthenticated plaintext.  The DH
+// failed when dh is all zero (X25519, RFC 9180 §7.1.4) or, with bc.dh_ok set (P-256), when the
+// report's flag dh_flag is zero -- there an all-zero value is no marker.  ct holds body + 16
 // bytes.  sbox is unused (null) for ChaCha20-Poly1305.
 template <int KDF, int AEAD, class Aad>
 DEVI void hpke_open_lane(const uint8_t* sbox, const HpkeBatchConsts& bc, const uint32_t* dh,
-                         const uint8_t* enc, const Aad& aad, const uint8_t* ct, uint64_t body,
-                         uint8_t* pt, uint64_t pt_cap, uint8_t* status) {
+                         uint32_t dh_flag, const uint8_t* enc, const Aad& aad, const uint8_t* ct,
+                         uint64_t body, uint8_t* pt, uint64_t pt_cap, uint8_t* status) {
   uint32_t dhw[8], encw[8], nz = 0;
 #pragma unroll
   for (int i = 0; i < 8; ++i) {
     const uint32_t d = dh[i];
     nz |= d;
     dhw[i] = bswap32(d);
-    const uint8_t* e = enc + 4 * i;
-    encw[i] = ((uint32_t)e[0] << 24) | ((uint32_t)e[1] << 16) | ((uint32_t)e[2] << 8) | e[3];
+    encw[i] = 0;
+  }
+  if (bc.dh_ok) {
+    nz = dh_flag;
+  } else {
+#pragma unroll
+    for (int i = 0; i < 8; ++i) {
+      const uint8_t* e = enc + 4 * i;
+      encw[i] = ((uint32_t)e[0] << 24) | ((uint32_t)e[1] << 16) | ((uint32_t)e[2] << 8) | e[3];
+    }
   }
   constexpr int NKW = hpke_aead_nk(AEAD) / 4;
   uint32_t key[NKW], nonce[3];
@@ -663,9 +721,9 @@ __global__ void __launch_bounds__(256) k_hpke_open(
     hpke_open_reject(pt, pt_cap, status + r, skip);
     return;
   }
-  hpke_open_lane<KDF, AEAD>(sbox, bc, dh + (size_t)r * 8, encs + (size_t)r * 32,
-                            PackedBytes{aads + a0, a1 - a0}, cts + c0, c1 - c0 - 16, pt, pt_cap,
-                            status + r);
+  hpke_open_lane<KDF, AEAD>(sbox, bc, dh + (size_t)r * 8, bc.dh_ok ? bc.dh_ok[r] : 1u,
+                            encs + (size_t)r * bc.nenc, PackedBytes{aads + a0, a1 - a0}, cts + c0,
+                            c1 - c0 - 16, pt, pt_cap, status + r);
 }
 
 // TEST ONLY (prio3gpu_test_poly1305_gpu): tags[i] = Poly1305(keys[i], msgs[off[i] .. off[i + 1])),

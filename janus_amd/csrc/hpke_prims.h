@@ -195,12 +195,13 @@ P3G_HP void hmac512_finish(const uint64_t ist[8], const uint64_t ost[8], uint64_
 
 constexpr int hpke_aead_nk(int aead) { return aead == 1 ? 16 : 32; }  // AEAD key bytes (Nk)
 
-// "HPKE-v1" || suite_id("HPKE" || 0x0020 || kdf || aead) at off (17 bytes)
+// "HPKE-v1" || suite_id("HPKE" || kem || kdf || aead) at off (17 bytes); kem_lo is the KEM id's low
+// byte (0x20 X25519, 0x10 P-256; the high byte is zero)
 template <int KDF, int AEAD>
-P3G_HP void msg64_hpke_prefix(uint64_t* w, int off) {
+P3G_HP void msg64_hpke_prefix(uint64_t* w, int off, uint32_t kem_lo) {
   msg64_str(w, off, "HPKE-v1");
   msg64_str(w, off + 7, "HPKE");
-  msg64_byte(w, off + 12, 0x20u);
+  msg64_byte(w, off + 12, (uint64_t)kem_lo);
   msg64_byte(w, off + 14, (uint64_t)KDF);
   msg64_byte(w, off + 16, (uint64_t)AEAD);
 }
@@ -212,7 +213,7 @@ P3G_HP void msg64_hpke_prefix(uint64_t* w, int off) {
 template <int KDF, int AEAD>
 P3G_HP void hpke_kdf512_key_nonce(const uint32_t ss[8], const uint32_t* psk_id_hash,
                                   const uint32_t* info_hash, uint64_t secret[8], uint32_t* key,
-                                  uint32_t nonce[3]) {
+                                  uint32_t nonce[3], uint32_t kem_lo = 0x20u) {
   constexpr int NH = Kdf512<KDF>::NH, NHW = Kdf512<KDF>::NHW, NK = hpke_aead_nk(AEAD);
   uint64_t w[32], ist[8], ost[8], t[8], ssw[4];
 #pragma unroll
@@ -221,7 +222,7 @@ P3G_HP void hpke_kdf512_key_nonce(const uint32_t ss[8], const uint32_t* psk_id_h
   hmac512_pads<KDF>(ssw, 4, ist, ost);
 #pragma unroll
   for (int i = 0; i < 16; ++i) w[i] = 0;
-  msg64_hpke_prefix<KDF, AEAD>(w, 0);
+  msg64_hpke_prefix<KDF, AEAD>(w, 0, kem_lo);
   msg64_str(w, 17, "secret");
   msg64_pad(w, 23, 1, 128);
   hmac512_finish<KDF, 1>(ist, ost, w, secret);
@@ -231,7 +232,7 @@ P3G_HP void hpke_kdf512_key_nonce(const uint32_t ss[8], const uint32_t* psk_id_h
 #pragma unroll
   for (int i = 0; i < 32; ++i) w[i] = 0;
   msg64_byte(w, 1, (uint64_t)NK);
-  msg64_hpke_prefix<KDF, AEAD>(w, 2);
+  msg64_hpke_prefix<KDF, AEAD>(w, 2, kem_lo);
   msg64_str(w, 19, "key");
   msg64_words32(w, 23, psk_id_hash, NH / 4);
   msg64_words32(w, 23 + NH, info_hash, NH / 4);
@@ -244,7 +245,7 @@ P3G_HP void hpke_kdf512_key_nonce(const uint32_t ss[8], const uint32_t* psk_id_h
 #pragma unroll
   for (int i = 0; i < 32; ++i) w[i] = 0;
   msg64_byte(w, 1, 12u);
-  msg64_hpke_prefix<KDF, AEAD>(w, 2);
+  msg64_hpke_prefix<KDF, AEAD>(w, 2, kem_lo);
   msg64_str(w, 19, "base_nonce");
   msg64_words32(w, 30, psk_id_hash, NH / 4);
   msg64_words32(w, 30 + NH, info_hash, NH / 4);

@@ -7,7 +7,7 @@
 
 namespace p3g {
 
-// DHKEM(X25519, HKDF-SHA256) with KDF kdf_id (1 HKDF-SHA256, 2 -SHA384, 3 -SHA512) and AEAD
+// DHKEM(X25519, HKDF-SHA256) (KEM 0x0020) or DHKEM(P-256, HKDF-SHA256) (0x0010) with KDF kdf_id (1 HKDF-SHA256, 2 -SHA384, 3 -SHA512) and AEAD
 // aead_id (1 AES-128-GCM, 2 AES-256-GCM, 3 ChaCha20-Poly1305), base mode.  Every field is
 // big-endian 32-bit words (the form SHA-256 consumes and produces; SHA-512 pairs them); the two
 // hashes are Nh = 32 / 48 / 64 bytes of the suite's KDF, the rest zero.
@@ -18,10 +18,19 @@ struct HpkeBatchConsts {
   uint32_t info_hash[16];    // LabeledExtract("", "info_hash", info)
   uint32_t salt0_i[8];       // HMAC-SHA256 under the empty salt: state after the ipad block ...
   uint32_t salt0_o[8];       // ... and after the opad block (LabeledExtract("", "eae_prk", dh))
+  uint32_t kem_lo;           // the KEM id's low byte in the suite ids: 0x20 / 0x10
+  uint32_t nenc;             // bytes of an encapsulated key: 32 / 65
+  // Where a report's DH validity comes from.  Null (X25519): the 8-word per-report buffer holds
+  // the DH value, all zero is the failure, and the open kernel runs the KEM half with pk.
+  // Non-null (P-256, where an all-zero x coordinate is a legal DH value): one flag byte per
+  // report beside the buffer, which then holds the finished shared_secret (k_p256_dh has run
+  // the KEM half; pk is unused).  Set by the engine once the buffer exists.
+  const uint8_t* dh_ok;
 };
 
-// hpke.cpp.  false if the suite is not an X25519 suite above or its primitives are unavailable.
-bool hpke_batch_consts(uint16_t kdf_id, uint16_t aead_id, const uint8_t* pk, const uint8_t* info,
+// hpke.cpp.  false if the suite is not one above or its primitives are unavailable.  pk is pkR's
+// 32 bytes for X25519 and is not read for P-256.
+bool hpke_batch_consts(uint16_t kem_id, uint16_t kdf_id, uint16_t aead_id, const uint8_t* pk, const uint8_t* info,
                        size_t info_len, HpkeBatchConsts* out);
 
 }  // namespace p3g

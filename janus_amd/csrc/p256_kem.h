@@ -1,0 +1,196 @@
+// The KEM half of DHKEM(P-256, HKDF-SHA256) (RFC 9180 §4.1) over p256.h, and one lane of the DH
+// kernels (hpke_gpu.h: k_p256_dh, helper_request.h: k_p256_dh_idx).  Free of HIP like p256.h: in a
+// HIP unit it hashes with sha256.h (device code), in a plain C++ build (tests/native/p256_host.cpp)
+// with the SHA-256 compression below, which has the same contract.
+#pragma once
+#include "p256.h"
+
+#if defined(__HIPCC__)
+#include "sha256.h"
+#define P3G_P256_DEV __device__ __forceinline__
+#else
+#define P3G_P256_DEV inline
+#endif
+
+namespace p3g {
+
+#if !defined(__HIPCC__)
+// The CPU build's SHA-256 compression (sha256.h is device code): the same contract, h absorbs the
+// block given as 16 big-endian words.
+namespace p256_host {
+inline uint32_t rotr(uint32_t x, int n) { return (x >> n) | (x << (32 - n)); }
+constexpr uint32_t kK[64] = {
+    0x428a2f98, 0x71374491, 0xb5c0fbcf, 0xe9b5dba5, 0x3956c25b, 0x59f111f1, 0x923f82a4, 0xab1c5ed5,
+    0xd807aa98, 0x12835b01, 0x243185be, 0x550c7dc3, 0x72be5d74, 0x80deb1fe, 0x9bdc06a7, 0xc19bf174,
+    0xe49b69c1, 0xefbe4786, 0x0fc19dc6, 0x240ca1cc, 0x2de92c6f, 0x4a7484aa, 0x5cb0a9dc, 0x76f988da,
+    0x983e5152, 0xa831c66d, 0xb00327c8, 0xbf597fc7, 0xc6e00bf3, 0xd5a79147, 0x06ca6351, 0x14292967,
+    0x27b70a85, 0x2e1b2138, 0x4d2c6dfc, 0x53380d13, 0x650a7354, 0x766a0abb, 0x81c2c92e, 0x92722c85,
+    0xa2bfe8a1, 0xa81a664b, 0xc24b8b70, 0xc76c51a3, 0xd192e819, 0xd6990624, 0xf40e3585, 0x106aa070,
+    0x19a4c116, 0x1e376c08, 0x2748774c, 0x34b0bcb5, 0x391c0cb3, 0x4ed8aa4a, 0x5b9cca4f, 0x682e6ff3,
+    0x748f82ee, 0x78a5636f, 0x84c87814, 0x8cc70208, 0x90befffa, 0xa4506ceb, 0xbef9a3f7, 0xc67178f2};
+}  // namespace p256_host
+inline void sha256_iv(uint32_t h[8]) {
+  h[0] = 0x6a09e667; h[1] = 0xbb67ae85; h[2] = 0x3c6ef372; h[3] = 0xa54ff53a;
+  h[4] = 0x510e527f; h[5] = 0x9b05688c; h[6] = 0x1f83d9ab; h[7] = 0x5be0cd19;
+}
+inline void sha256_compress(uint32_t h[8], uint32_t w[16]) {
+  using p256_host::rotr;
+  uint32_t s[8];
+  for (int i = 0; i < 8; ++i) s[i] = h[i];
+  for (int t = 0; t < 64; ++t) {
+    if (t >= 16) {
+      const uint32_t w15 = w[(t + 1) & 15], w2 = w[(t + 14) & 15];
+      w[t & 15] += (rotr(w15, 7) ^ rotr(w15, 18) ^ (w15 >> 3)) + w[(t + 9) & 15] +
+                   (rotr(w2, 17) ^ rotr(w2, 19) ^ (w2 >> 10));
+    }
+    const uint32_t t1 = s[7] + (rotr(s[4], 6) ^ rotr(s[4], 11) ^ rotr(s[4], 25)) +
+                        ((s[4] & s[5]) ^ (~s[4] & s[6])) + p256_host::kK[t] + w[t & 15];
+    const uint32_t t2 = (rotr(s[0], 2) ^ rotr(s[0], 13) ^ rotr(s[0], 22)) +
+                        ((s[0] & s[1]) ^ (s[0] & s[2]) ^ (s[1] & s[2]));
+    for (int i = 7; i > 0; --i) s[i] = s[i - 1];
+    s[4] += t1;
+    s[0] = t1 + t2;
+  }
+  for (int i = 0; i < 8; ++i) h[i] += s[i];
+}
+#endif
+
+// ------------------------------------------------------------------------------------------------
+// DHKEM(P-256, HKDF-SHA256) ExtractAndExpand (RFC 9180 §4.1), suite_id = "KEM" || 0x0010.
+// Messages are built as big-endian words at compile-time byte offsets, as in hpke_gpu.h.
+// ------------------------------------------------------------------------------------------------
+P3G_P256_DEV void p256_msg_byte(uint32_t* w, int off, uint32_t b) {
+  w[off >> 2] |= b << (24 - 8 * (off & 3));
+}
+template <int N>
+P3G_P256_DEV void p256_msg_str(uint32_t* w, int off, const char (&s)[N]) {
+#pragma unroll
+  for (int i = 0; i < N - 1; ++i) p256_msg_byte(w, off + i, (uint32_t)(uint8_t)s[i]);
+}
+P3G_P256_DEV void p256_msg_words8(uint32_t* w, int off, const uint32_t v[8]) {
+#pragma unroll
+  for (int i = 0; i < 8; ++i) {
+    const int p = off + 4 * i, sh = 8 * (p & 3), idx = p >> 2;
+    if (sh == 0) {
+      w[idx] |= v[i];
+    } else {
+      w[idx] |= v[i] >> sh;
+      w[idx + 1] |= v[i] << (32 - sh);
+    }
+  }
+}
+// "HPKE-v1" || "KEM" || 0x0010 at off (12 bytes)
+P3G_P256_DEV void p256_msg_kem_prefix(uint32_t* w, int off) {
+  p256_msg_str(w, off, "HPKE-v1");
+  p256_msg_str(w, off + 7, "KEM");
+  p256_msg_byte(w, off + 11, 0x10u);
+}
+// HMAC-SHA256 of the padded NB-block message w (consumed) after the pad states ist / ost
+template <int NB>
+P3G_P256_DEV void p256_hmac_finish(const uint32_t ist[8], const uint32_t ost[8], uint32_t* w,
+                                   uint32_t out[8]) {
+  uint32_t st[8], o[16];
+#pragma unroll
+  for (int i = 0; i < 8; ++i) st[i] = ist[i];
+#pragma unroll
+  for (int b = 0; b < NB; ++b) sha256_compress(st, w + 16 * b);
+#pragma unroll
+  for (int i = 0; i < 16; ++i) o[i] = i < 8 ? st[i] : 0u;
+  o[8] = 0x80000000u;
+  o[15] = (64 + 32) * 8;
+#pragma unroll
+  for (int i = 0; i < 8; ++i) out[i] = ost[i];
+  sha256_compress(out, o);
+}
+
+// The recipient's public key as the kernels take it: the coordinates of pkRm, big-endian words.
+struct P256PublicKey {
+  uint32_t x[8], y[8];
+};
+
+// shared_secret (8 big-endian words) from dh (the x coordinate, 8 big-endian words), the lane's
+// enc = 0x04 || ex || ey and pkRm = 0x04 || pk.x || pk.y.  salt0_i / salt0_o are the HMAC-SHA256
+// pad states of the empty salt (HpkeBatchConsts).  kem_context is 130 bytes, so the expand's
+// message is 158 bytes: three blocks behind the pad block.  8 compressions.
+P3G_P256_DEV void p256_kem_shared_secret(const uint32_t salt0_i[8], const uint32_t salt0_o[8],
+                                         const uint32_t dh[8], const uint32_t ex[8],
+                                         const uint32_t ey[8], const P256PublicKey& pk,
+                                         uint32_t ss[8]) {
+  uint32_t w[48], prk[8], ist[8], ost[8];
+  // eae_prk = LabeledExtract("", "eae_prk", dh)
+#pragma unroll
+  for (int i = 0; i < 16; ++i) w[i] = 0;
+  p256_msg_kem_prefix(w, 0);
+  p256_msg_str(w, 12, "eae_prk");
+  p256_msg_words8(w, 19, dh);
+  p256_msg_byte(w, 51, 0x80u);
+  w[15] = (64 + 51) * 8;
+  p256_hmac_finish<1>(salt0_i, salt0_o, w, prk);
+  // shared_secret = LabeledExpand(eae_prk, "shared_secret", enc || pkRm, 32)
+#pragma unroll
+  for (int i = 0; i < 16; ++i) w[i] = (i < 8 ? prk[i] : 0u) ^ 0x36363636u;
+  sha256_iv(ist);
+  sha256_compress(ist, w);
+#pragma unroll
+  for (int i = 0; i < 16; ++i) w[i] = (i < 8 ? prk[i] : 0u) ^ 0x5c5c5c5cu;
+  sha256_iv(ost);
+  sha256_compress(ost, w);
+#pragma unroll
+  for (int i = 0; i < 48; ++i) w[i] = 0;
+  p256_msg_byte(w, 1, 32u);
+  p256_msg_kem_prefix(w, 2);
+  p256_msg_str(w, 14, "shared_secret");
+  p256_msg_byte(w, 27, 0x04u);
+  p256_msg_words8(w, 28, ex);
+  p256_msg_words8(w, 60, ey);
+  p256_msg_byte(w, 92, 0x04u);
+  p256_msg_words8(w, 93, pk.x);
+  p256_msg_words8(w, 125, pk.y);
+  p256_msg_byte(w, 157, 1u);
+  p256_msg_byte(w, 158, 0x80u);
+  w[47] = (64 + 158) * 8;
+  p256_hmac_finish<3>(ist, ost, w, ss);
+}
+
+// One lane of the P-256 DH kernels: decode and validate the 65-byte enc, x([k] enc), the KEM
+// half.  Returns the validity flag; an invalid enc runs the same instructions over the
+// recipient's own (valid) point and its shared secret is zeroed.  raw (wave-uniform; the test
+// hook's) leaves the KEM half out: ss is then x([k] enc) itself.
+P3G_P256_DEV bool p256_dh_lane(const P256Scalar& k, const P256PublicKey& pk,
+                               const uint32_t salt0_i[8], const uint32_t salt0_o[8],
+                               const uint8_t* enc, bool present, bool raw, uint32_t ss[8]) {
+  uint32_t ex[8], ey[8], dh[8];
+  Fp256 X, Y;
+  bool claim = false, ok = false;
+  if (present) {
+    p256_load_be_words8(enc + 1, ex);
+    p256_load_be_words8(enc + 33, ey);
+    claim = enc[0] == 0x04;
+  } else {
+#pragma unroll
+    for (int i = 0; i < 8; ++i) ex[i] = pk.x[i], ey[i] = pk.y[i];
+  }
+  // one copy of the validation's code: the second pass runs only for a refused enc, over pkRm
+  // (validated on the host, so always a point)
+#pragma unroll 1
+  for (int pass = 0; pass < 2; ++pass) {
+    const bool on = p256_validate(ex, ey, X, Y);
+    if (pass == 0) ok = on & claim;
+    if (ok) break;
+#pragma unroll
+    for (int i = 0; i < 8; ++i) ex[i] = pk.x[i], ey[i] = pk.y[i];
+  }
+  p256_dh_x(k, X, Y, dh);
+  if (raw) {
+#pragma unroll
+    for (int i = 0; i < 8; ++i) ss[i] = dh[i];
+  } else {
+    p256_kem_shared_secret(salt0_i, salt0_o, dh, ex, ey, pk, ss);
+  }
+  const uint32_t m = ok ? 0xffffffffu : 0u;
+#pragma unroll
+  for (int i = 0; i < 8; ++i) ss[i] &= m;
+  return ok;
+}
+
+}  // namespace p3g

@@ -14,6 +14,7 @@
 
 #include "../../include/prio3gpu.h"
 #include "cfg.h"
+#include "p256.h"
 #include "request_parse.h"
 
 namespace p3g {
@@ -41,12 +42,56 @@ inline void plaintext_offsets(const prio3gpu_prepare_init_view* views, size_t n,
     out[i + 1] = out[i] + (views[i].payload_len >= 16 ? views[i].payload_len - 16 : 0);
 }
 
+// The context options that widen what the GPU opens, as a bit mask (a plain `true` is
+// HPKE_OPT_SUITES, what the parameter meant while it was a bool).
+constexpr unsigned HPKE_OPT_SUITES = 1u;  // "hpke_gpu_suites": every KDF and AEAD
+constexpr unsigned HPKE_OPT_P256 = 2u;    // "hpke_gpu_p256": DHKEM(P-256, HKDF-SHA256) too
+
 // The suites the GPU opens: DHKEM(X25519, HKDF-SHA256) / HKDF-SHA256 / AES-128-GCM always; with
-// the "hpke_gpu_suites" option every X25519 suite Janus accepts.
-inline bool hpke_gpu_suite(bool gpu_suites_option, uint16_t kem, uint16_t kdf, uint16_t aead) {
-  if (kem != 0x0020) return false;
+// HPKE_OPT_P256 the same under DHKEM(P-256, HKDF-SHA256); with HPKE_OPT_SUITES every KDF and AEAD
+// Janus accepts, under the KEMs the other bit allows.
+inline bool hpke_gpu_suite(unsigned opts, uint16_t kem, uint16_t kdf, uint16_t aead) {
+  if (kem != 0x0020 && !(kem == 0x0010 && (opts & HPKE_OPT_P256))) return false;
   if (kdf == 1 && aead == 1) return true;
-  return gpu_suites_option && kdf >= 1 && kdf <= 3 && aead >= 1 && aead <= 3;
+  return (opts & HPKE_OPT_SUITES) && kdf >= 1 && kdf <= 3 && aead >= 1 && aead <= 3;
+}
+
+// Nenc = Npk of a KEM the GPU opens (RFC 9180 §7.1): 32 for X25519, 65 for P-256.
+inline uint32_t hpke_kem_nenc(uint16_t kem) { return kem == 0x0010 ? 65u : 32u; }
+
+// P-256 order n, big-endian
+constexpr uint8_t kP256Order[32] = {0xff, 0xff, 0xff, 0xff, 0x00, 0x00, 0x00, 0x00, 0xff, 0xff, 0xff,
+                                    0xff, 0xff, 0xff, 0xff, 0xff, 0xbc, 0xe6, 0xfa, 0xad, 0xa7, 0x17,
+                                    0x9e, 0x84, 0xf3, 0xb9, 0xca, 0xc2, 0xfc, 0x63, 0x25, 0x51};
+
+// 1 <= sk < n for a 32-byte big-endian scalar (no secret-dependent early exit).
+inline bool p256_scalar_valid(const uint8_t sk[32]) {
+  int borrow = 0;
+  uint8_t nz = 0;
+  for (int i = 31; i >= 0; --i) {
+    borrow = ((int)sk[i] - (int)kP256Order[i] - borrow) < 0;
+    nz |= sk[i];
+  }
+  return borrow && nz;
+}
+
+// A P-256 keypair the kernels may run under: the scalar in [1, n), the public key a valid point
+// (p256.h's own DeserializePublicKey).  Checked on the host before anything is launched.
+inline bool p256_keypair_valid(const uint8_t* sk, size_t sk_len, const uint8_t* pk, size_t pk_len) {
+  if (!sk || sk_len != 32 || !pk || pk_len != 65 || !p256_scalar_valid(sk)) return false;
+  uint32_t x[8], y[8];
+  Fp256 X, Y;
+  return p256_decode(pk, x, y, X, Y);
+}
+
+// What plan_hpke asks of a keypair before it gives it a group: 32-byte keys for X25519; for
+// P-256 a keypair that passes p256_keypair_valid (a malformed one is the host's, whose open
+// gives each report its status).
+inline bool hpke_gpu_keypair(const prio3gpu_hpke_keypair& kp) {
+  if (kp.kem_id == 0x0010)
+    return p256_keypair_valid(kp.private_key, kp.private_key_len, kp.public_key,
+                              kp.public_key_len);
+  return kp.private_key && kp.private_key_len == 32 && kp.public_key && kp.public_key_len == 32;
 }
 
 // Where one report goes: a GPU group (>= 0) or one of these.
@@ -55,12 +100,12 @@ constexpr int32_t ROUTE_UNKNOWN = -2;  // no key has its config id (request mode
 constexpr int32_t ROUTE_HOST = -3;     // the host path opens it
 
 // The first-choice key of a report is the task key of its config id, else the global key.  A
-// first choice of a suite the GPU opens, with 32-byte keys, puts the report into that keypair's
-// group (keypairs are told apart by address); any other key is the host's.  The two callers differ
-// in what they keep away from the kernels:
-//  * strict (prio3gpu_hpke_open_report_shares_gpu, which packs fixed 32-byte encapsulated keys):
-//    enc_len != 32 or payload_len < 16 is the host's, and so is an unknown id (the host pass
-//    gives it its status);
+// first choice of a suite the GPU opens, with well-formed keys (hpke_gpu_keypair), puts the report
+// into that keypair's group (keypairs are told apart by address); any other key is the host's.
+// The two callers differ in what they keep away from the kernels:
+//  * strict (prio3gpu_hpke_open_report_shares_gpu, which packs fixed Nenc-byte encapsulated keys,
+//    32 for X25519 and 65 for P-256): enc_len != Nenc or payload_len < 16 is the host's, and so
+//    is an unknown id (the host pass gives it its status);
 //  * request mode (prio3gpu_helper_init_request): such a report stays in its group and the kernel
 //    rejects it; an unknown id is ROUTE_UNKNOWN and the caller sets its status.
 struct HpkePlan {
@@ -76,13 +121,14 @@ struct HpkePlan {
 inline void plan_hpke(const prio3gpu_hpke_keypair* task_keys, size_t n_task_keys,
                       const prio3gpu_hpke_keypair* global_keys, size_t n_global_keys,
                       const prio3gpu_prepare_init_view* views, const uint8_t* status, size_t n,
-                      bool gpu_suites_option, bool strict, HpkePlan* out) {
+                      unsigned gpu_opts, bool strict, HpkePlan* out) {
   HpkePlan& p = *out;
   p = HpkePlan{};
   p.task_keys = task_keys, p.n_task_keys = n_task_keys;
   p.global_keys = global_keys, p.n_global_keys = n_global_keys;
   p.route.assign(n, ROUTE_FAILED);
   std::vector<size_t> count;
+  std::vector<const prio3gpu_hpke_keypair*> refused;  // keypairs found unfit, checked once each
   for (size_t i = 0; i < n; ++i) {
     if (status[i]) continue;
     const prio3gpu_prepare_init_view& v = views[i];
@@ -90,12 +136,24 @@ inline void plan_hpke(const prio3gpu_hpke_keypair* task_keys, size_t n_task_keys
     if (!kp) kp = find_keypair(global_keys, n_global_keys, v.hpke_config_id);
     if (!kp) {
       p.route[i] = strict ? ROUTE_HOST : ROUTE_UNKNOWN;
-    } else if (!hpke_gpu_suite(gpu_suites_option, kp->kem_id, kp->kdf_id, kp->aead_id) ||
-               !kp->private_key || kp->private_key_len != 32 || !kp->public_key ||
-               kp->public_key_len != 32 || (strict && (v.enc_len != 32 || v.payload_len < 16))) {
+      continue;
+    }
+    const size_t k = std::find(p.groups.begin(), p.groups.end(), kp) - p.groups.begin();
+    if (k == p.groups.size()) {  // not yet a group: is the keypair fit for one?
+      bool fit = std::find(refused.begin(), refused.end(), kp) == refused.end();
+      if (fit && !(hpke_gpu_suite(gpu_opts, kp->kem_id, kp->kdf_id, kp->aead_id) &&
+                   hpke_gpu_keypair(*kp))) {
+        refused.push_back(kp);
+        fit = false;
+      }
+      if (!fit) {
+        p.route[i] = ROUTE_HOST;
+        continue;
+      }
+    }
+    if (strict && (v.enc_len != hpke_kem_nenc(kp->kem_id) || v.payload_len < 16)) {
       p.route[i] = ROUTE_HOST;
     } else {
-      const size_t k = std::find(p.groups.begin(), p.groups.end(), kp) - p.groups.begin();
       if (k == p.groups.size()) {
         p.groups.push_back(kp);
         p.is_task_key.push_back(kp >= task_keys && kp < task_keys + n_task_keys);

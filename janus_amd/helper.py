@@ -9,7 +9,8 @@ Per aggregation job (one AggregationJobInitializeReq):
      each report's structural faults                                 codec.cpp   (aggregator.rs:1561-1612)
   2. HPKE-open every encrypted input share on host threads            hpke.cpp    (aggregator.rs:1634-1700)
      (hpke="gpu": X25519 / HKDF-SHA256 / AES-128-GCM shares on the GPU, hpke_gpu.h; with
-     hpke_gpu_suites=1 the shares of every X25519 suite)
+     hpke_gpu_suites=1 the shares of every X25519 suite; with hpke_gpu_p256=1 those of P-256
+     keys too)
   3. decode the PlaintextInputShares into the input-share array, then apply the structural
      faults to the reports still OK (Janus's precedence: HPKE 3/4, plaintext/input share 8,
      public share 8, ping-pong 5)                                                 (aggregator.rs:1702-1797)
@@ -121,7 +122,7 @@ class HelperAggregateInit:
                  global_keys: Sequence[hpke.HpkeKeypair] = (), query_type: int = C.TIME_INTERVAL,
                  hpke_threads: int = 0,
                  batch_slot_of: Optional[Callable[[np.ndarray], np.ndarray]] = None,
-                 hpke: str = "host", hpke_gpu_suites: int = 0):
+                 hpke: str = "host", hpke_gpu_suites: int = 0, hpke_gpu_p256: int = 0):
         """`batch_slot_of(times) -> slots` maps report times to aggregate slots (Janus's
         Q::to_batch_identifier, aggregator.rs:1614-1619); None = one slot.
 
@@ -141,11 +142,19 @@ class HelperAggregateInit:
         / ChaCha20-Poly1305), so a task whose key names one of those keeps its reports off the
         host threads.  In "gpu" mode it is set on the driver's own HPKE context; in "fused" mode
         on `vdaf`'s context, which keeps it after the driver is closed.  A non-zero value with
-        hpke="host" is a `ValueError`: nothing would open on the GPU."""
+        hpke="host" is a `ValueError`: nothing would open on the GPU.
+
+        `hpke_gpu_p256` is the engine option of that name, set in the same places: 0 (default)
+        keeps DHKEM(P-256, HKDF-SHA256) keys on the host threads; 1 lets the GPU open them too
+        (HKDF-SHA256 / AES-128-GCM with this option alone, every KDF and AEAD with
+        `hpke_gpu_suites` = 1 as well).  Like `hpke_gpu_suites` it is a `ValueError` together
+        with hpke="host"."""
         if hpke not in ("host", "gpu", "fused"):
             raise ValueError('hpke must be "host", "gpu" or "fused"')
         if hpke_gpu_suites and hpke == "host":
             raise ValueError('hpke_gpu_suites needs hpke="gpu" or "fused"')
+        if hpke_gpu_p256 and hpke == "host":
+            raise ValueError('hpke_gpu_p256 needs hpke="gpu" or "fused"')
         self.hpke_mode = hpke
         self._hpke_ctx = None
         if hpke == "gpu":
@@ -153,8 +162,10 @@ class HelperAggregateInit:
                                       length=vdaf.length, chunk_length=vdaf.chunk_length,
                                       device=vdaf.device, xof=vdaf.xof)
             self._hpke_ctx.set_option("hpke_gpu_suites", hpke_gpu_suites)
+            self._hpke_ctx.set_option("hpke_gpu_p256", hpke_gpu_p256)
         elif hpke == "fused":
             vdaf.set_option("hpke_gpu_suites", hpke_gpu_suites)
+            vdaf.set_option("hpke_gpu_p256", hpke_gpu_p256)
         self.vdaf = vdaf
         self.task_id = bytes(task_id)
         self.task_keys = list(task_keys)

@@ -170,9 +170,11 @@ def open_batch_gpu(gpu, keypair: HpkeKeypair, info: bytes, encs, aads, aad_offse
     """n HPKE opens under ONE keypair on the GPU (prio3gpu_hpke_open_batch).  By default only
     X25519 / HKDF-SHA256 / AES-128-GCM; after `gpu.set_option("hpke_gpu_suites", 1)` every X25519
     suite (KDF HKDF-SHA256 / -SHA384 / -SHA512 x AEAD AES-128-GCM / AES-256-GCM /
-    ChaCha20-Poly1305).  `ValueError` for any other suite (P-256 always), nothing launched.
+    ChaCha20-Poly1305); after `gpu.set_option("hpke_gpu_p256", 1)` the same choice under
+    DHKEM(P-256, HKDF-SHA256).  `ValueError` for any other suite, nothing launched.
 
-    `gpu` is a `Prio3Gpu` or a context handle.  Report i: enc = encs[32 i : 32 i + 32], aad =
+    `gpu` is a `Prio3Gpu` or a context handle.  Report i: enc = encs[Nenc i : Nenc i + Nenc] with
+    Nenc = 32 for X25519 and 65 for P-256 (the stride follows the keypair's KEM), aad =
     aads[aad_offsets[i] : aad_offsets[i+1]], ciphertext || tag = cts[ct_offsets[i] :
     ct_offsets[i+1]].  Buffers are numpy arrays (host) or integer device pointers (then `n`,
     `pts`, `pt_offsets` and `status` must be given).  By default plaintext i has the ciphertext's
@@ -213,9 +215,10 @@ def open_report_shares(task_id: bytes, req, task_keys: Sequence[HpkeKeypair],
     """Open every encrypted input share of a decoded AggregationJobInitializeReq
     (`janus_amd.codec.AggInitReq`) on `threads` host threads (0: all cores).  With `gpu` (a
     `Prio3Gpu` or a context handle) the reports whose first-choice key is X25519 / HKDF-SHA256 /
-    AES-128-GCM -- or, with that context's "hpke_gpu_suites" option at 1, any X25519 suite -- are
-    opened on that context's GPU instead (prio3gpu_hpke_open_report_shares_gpu); the rest (P-256,
-    the second trial with a global key) stay on the host threads.  Statuses, offsets and
+    AES-128-GCM -- or, with that context's "hpke_gpu_suites" option at 1, any X25519 suite, and
+    with its "hpke_gpu_p256" option at 1 the same under P-256 -- are opened on that context's GPU
+    instead (prio3gpu_hpke_open_report_shares_gpu); the rest (P-256 while that option is 0, the
+    second trial with a global key) stay on the host threads.  Statuses, offsets and
     plaintexts are the host path's.
 
     -> (plaintexts uint8 array, offsets (n + 1), status); report i's PlaintextInputShare is

@@ -11,6 +11,10 @@
                                                     the task key's suite(s), KEM/KDF/AEAD; a suite
                                                     other than 0x20/1/1 turns the context option
                                                     "hpke_gpu_suites" on for the GPU mode
+  python tools/hpke_bench.py both --n 4096,65536 --reps 9 --suite 0x10/1/1
+                                                    a P-256 key (KEM 0x10): the GPU mode turns
+                                                    "hpke_gpu_p256" on (and "hpke_gpu_suites" for
+                                                    a KDF / AEAD other than 1/1)
   python tools/hpke_bench.py 1,8,16 [scalar]        the former spelling of `host`
 
 Each figure is the median of --reps timed calls after one warm-up call, with the min..max spread;
@@ -97,13 +101,17 @@ def main():
     if args.mode != "host":
         from janus_amd.prio3 import Prio3Gpu
         gpu = Prio3Gpu.new_count(bytes(16))
-    wide_on = False
+    wide_on = p256_on = False
     for suite in [parse_suite(x) for x in args.suite.split(",")]:
         tk = H.generate_hpke_config_and_private_key(1, *suite)
-        wide = suite != (0x20, 1, 1)
+        wide = suite[1:] != (1, 1)
         if gpu is not None and wide != wide_on:  # the default suite needs no option
             gpu.set_option("hpke_gpu_suites", int(wide))
             wide_on = wide
+        p256 = suite[0] == H.KEM_P256_HKDF_SHA256
+        if gpu is not None and p256 != p256_on:
+            gpu.set_option("hpke_gpu_p256", int(p256))
+            p256_on = p256
         for n in [int(x) for x in args.n.split(",")]:
             req = build_request(n, tk, task_id)
             for th in [int(x) for x in args.threads.split(",")]:
