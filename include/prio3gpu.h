@@ -571,6 +571,56 @@ int prio3gpu_hpke_open_report_shares_gpu(prio3gpu_ctx* ctx, const uint8_t* task_
                                          uint8_t* plaintexts, uint64_t* offsets, uint8_t* status,
                                          int threads);
 
+/* ---- HPKE seal on the GPU (janus_amd/csrc/hpke_seal_gpu.h) -------------------------------------
+ * n seals to ONE recipient key, one GPU lane per report, each under its own ephemeral key: the
+ * batched hpke::seal (core/src/hpke.rs:158-182).  Suites: DHKEM(X25519, HKDF-SHA256) (KEM 0x0020)
+ * with KDF 1-3 and AEAD 1-3, no context option needed.  KEM 0x0010 (P-256) or an unknown KDF or
+ * AEAD is PRIO3GPU_E_UNSUPPORTED with nothing launched: P-256 seals stay on the host's
+ * prio3gpu_hpke_seal.  pk_len other than 32 is PRIO3GPU_E_ARG; n == 0 returns 0 and launches
+ * nothing.  pk and info are host memory; every other pointer may be host or device (detected).
+ * Report i is sealed under the ephemeral private key sk_es[32 i .. 32 i + 32) with
+ * aad = aads[aad_offsets[i] .. aad_offsets[i+1]) and plaintext = pts[pt_offsets[i] ..
+ * pt_offsets[i+1]); its encapsulated key goes to encs[32 i .. 32 i + 32) and its ciphertext || tag
+ * to cts[ct_offsets[i] .. ct_offsets[i+1]) (room for the plaintext length + 16; a longer slot is
+ * zero-filled).  The bytes are those of prio3gpu_hpke_seal with the same sk_e.
+ * status in/out: non-zero on entry = skipped; a report that is not sealed -- skipped, an all-zero
+ * DH value (pk of small order, RFC 9180 §7.1.4; prio3gpu_hpke_seal returns PRIO3GPU_E_HPKE
+ * there), a slot shorter than the plaintext + 16, offsets that do not fit -- gets zeros in its
+ * enc and ciphertext slots and, unless it was skipped, status 4 (PRIO3GPU_HPKE_DECRYPT_ERROR, the
+ * ABI's one per-report HPKE failure).
+ * Secrets: the engine's device copies of the ephemeral keys and of the plaintexts, and the buffer
+ * of the per-report DH values, are zeroed before the call returns, on the error paths too; keys
+ * and nonces never leave registers.  Scratch belongs to the context (see prio3gpu_state_create). */
+int prio3gpu_hpke_seal_batch(prio3gpu_ctx* ctx, uint16_t kem_id, uint16_t kdf_id, uint16_t aead_id,
+                             const uint8_t* pk, size_t pk_len, const uint8_t* info,
+                             size_t info_len, size_t n, const uint8_t* sk_es, const uint8_t* aads,
+                             const uint64_t* aad_offsets, const uint8_t* pts,
+                             const uint64_t* pt_offsets, uint8_t* encs, uint8_t* cts,
+                             const uint64_t* ct_offsets, uint8_t* status);
+/* Client: seal n Prio3 input shares to one aggregator (Client::prepare_report's per-aggregator
+ * half, client/src/lib.rs:228-251) without materialising a frame.  Report i's plaintext is the
+ * PlaintextInputShare with no extensions -- 00 00, the share length as u32 big-endian, then
+ * input_shares[i pitch .. i pitch + input_share_len) -- and its AAD the InputShareAad of task_id,
+ * report_ids[16 i ..], times[i] (u64, seconds; encoded big-endian) and public_shares[i
+ * public_share_len ..] with its u32 length prefix; both are read from the caller's rows lane by
+ * lane and never written to memory.  info = "dap-07 input share" || Client || recipient_role.
+ * Report i's encapsulated key (32 bytes) goes to out_encs + i enc_pitch and its payload, exactly
+ * 6 + input_share_len + 16 bytes, to out_payloads + i payload_pitch; no other byte of either
+ * buffer is written, so both may be columns of one fixed-stride Report buffer.  A pitch of 0 is
+ * the packed one (the row's own length); a pitch shorter than its row is PRIO3GPU_E_ARG.
+ * task_id and pk are host memory; every other pointer may be host or device (detected), the
+ * device outputs of the sharding call being the intended input.  Suites, sk_es, status and the
+ * handling of secrets are prio3gpu_hpke_seal_batch's. */
+int prio3gpu_seal_input_shares(prio3gpu_ctx* ctx, const uint8_t* task_id, uint16_t kem_id,
+                               uint16_t kdf_id, uint16_t aead_id, const uint8_t* pk,
+                               size_t pk_len, uint8_t recipient_role, size_t n,
+                               const uint8_t* report_ids, const uint64_t* times,
+                               const uint8_t* public_shares, uint32_t public_share_len,
+                               const uint8_t* input_shares, uint32_t input_share_len,
+                               size_t input_share_pitch, const uint8_t* sk_es, uint8_t* out_encs,
+                               size_t enc_pitch, uint8_t* out_payloads, size_t payload_pitch,
+                               uint8_t* status);
+
 /* ---- Helper aggregate-init from the request's bytes (janus_amd/csrc/helper_request.h) -----------
  * One call per aggregation job, on one context: the decoded AggregationJobInitializeReq in, prep
  * messages out.  Equivalent, with agg_id = 1, to

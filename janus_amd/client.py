@@ -1,0 +1,245 @@
+"""The DAP client, batched on the GPU: measurements in, upload-ready `Report` bytes out.
+
+Mirrors `Client::prepare_report` of Janus's client/src/lib.rs:212-258 for a whole batch: shard
+(prio3gpu_shard), wrap each input share in a `PlaintextInputShare`, `hpke::seal` it to its
+aggregator under the `InputShareAad` (prio3gpu_seal_input_shares: both frames are read lane by
+lane from the share rows and never built), and encode a `Report`.  Every report of one
+`ClientBatch` has the same length, so a batch is an (n, report_len) uint8 matrix whose columns
+are the fields of messages/src/lib.rs's `Report`:
+
+  ReportMetadata   report_id[16] | time u64
+  public_share     u32 length | bytes
+  HpkeCiphertext   config_id u8 | u16 length (32) | enc[32] | u32 length | payload     (leader)
+  HpkeCiphertext   the same                                                            (helper)
+  payload = AEAD(PlaintextInputShare = 00 00 | u32 length | input share) || tag[16]
+
+The framing is pinned by the reference's own KATs (tests/test_client_frames.py).
+"""
+from __future__ import annotations
+
+import os
+import struct
+import time as _time
+from typing import NamedTuple, Optional, Tuple
+
+import numpy as np
+
+from . import hpke as H
+
+ENC_LEN = 32        # Nenc of DHKEM(X25519, HKDF-SHA256), the KEM the GPU seals to
+TAG_LEN = 16
+PLAINTEXT_OVERHEAD = 6   # empty extension list (u16) + payload length (u32)
+
+
+def encode_plaintext_input_share(payload: bytes, extensions: bytes = b"") -> bytes:
+    """PlaintextInputShare (messages/src/lib.rs:1850-1895); `extensions` is the encoded list's
+    body (empty: what a client sends)."""
+    return struct.pack(">H", len(extensions)) + bytes(extensions) + struct.pack(
+        ">I", len(payload)) + bytes(payload)
+
+
+def encode_hpke_ciphertext(config_id: int, enc: bytes, payload: bytes) -> bytes:
+    return (bytes([config_id]) + struct.pack(">H", len(enc)) + bytes(enc)
+            + struct.pack(">I", len(payload)) + bytes(payload))
+
+
+def encode_report(report_id: bytes, time: int, public_share: bytes, leader_ciphertext,
+                  helper_ciphertext) -> bytes:
+    """Report (messages/src/lib.rs:1529-1610); a ciphertext is (config id, enc, payload)."""
+    assert len(report_id) == 16
+    return (bytes(report_id) + struct.pack(">Q", time) + struct.pack(">I", len(public_share))
+            + bytes(public_share) + encode_hpke_ciphertext(*leader_ciphertext)
+            + encode_hpke_ciphertext(*helper_ciphertext))
+
+
+class HpkeCiphertext(NamedTuple):
+    config_id: int
+    encapsulated_key: bytes
+    payload: bytes
+
+
+class Report(NamedTuple):
+    report_id: bytes
+    time: int
+    public_share: bytes
+    leader_encrypted_input_share: HpkeCiphertext
+    helper_encrypted_input_share: HpkeCiphertext
+
+
+def decode_report(data: bytes) -> Report:
+    """Report::get_decoded: `ValueError` for a truncated encoding or trailing bytes."""
+    data = bytes(data)
+    pos = 0
+
+    def take(k: int) -> bytes:
+        nonlocal pos
+        if k < 0 or pos + k > len(data):
+            raise ValueError("Report: unexpected end of input")
+        pos += k
+        return data[pos - k:pos]
+
+    def ciphertext() -> HpkeCiphertext:
+        cfg = take(1)[0]
+        enc = take(struct.unpack(">H", take(2))[0])
+        return HpkeCiphertext(cfg, enc, take(struct.unpack(">I", take(4))[0]))
+
+    rid = take(16)
+    t = struct.unpack(">Q", take(8))[0]
+    pub = take(struct.unpack(">I", take(4))[0])
+    leader, helper = ciphertext(), ciphertext()
+    if pos != len(data):
+        raise ValueError(f"Report: {len(data) - pos} trailing bytes")
+    return Report(rid, t, pub, leader, helper)
+
+
+def _like(dst, a: np.ndarray):
+    """The numpy array `a` as what can be assigned into `dst` (numpy array or torch tensor)."""
+    if isinstance(dst, np.ndarray):
+        return a
+    import torch
+    return torch.from_numpy(np.array(a)).to(dst.device)
+
+
+class ReportLayout:
+    """Column offsets of the fixed-stride Report matrix for given public-share and input-share
+    lengths (X25519 encapsulated keys)."""
+
+    def __init__(self, public_share: int, leader_share: int, helper_share: int):
+        self.public_share, self.leader_share, self.helper_share = (public_share, leader_share,
+                                                                   helper_share)
+        self.leader_payload = PLAINTEXT_OVERHEAD + leader_share + TAG_LEN
+        self.helper_payload = PLAINTEXT_OVERHEAD + helper_share + TAG_LEN
+        o = 0
+        self.o_report_id, o = o, o + 16
+        self.o_time, o = o, o + 8
+        self.o_public_len, o = o, o + 4
+        self.o_public, o = o, o + public_share
+        self.o_leader = o                          # config id, 00 20, enc, u32 length, payload
+        self.o_leader_enc = o + 3
+        self.o_leader_payload = o + 3 + ENC_LEN + 4
+        o = self.o_leader_payload + self.leader_payload
+        self.o_helper = o
+        self.o_helper_enc = o + 3
+        self.o_helper_payload = o + 3 + ENC_LEN + 4
+        self.report_len = self.o_helper_payload + self.helper_payload
+        assert self.report_len == (16 + 8 + 4 + public_share + 2 * (1 + 2 + 32 + 4 + 6 + 16)
+                                   + leader_share + helper_share)
+
+    def write_fixed(self, reports, report_ids: np.ndarray, times: np.ndarray, public_shares,
+                    leader_config_id: int, helper_config_id: int) -> None:
+        """Everything of `reports` (an (n, report_len) uint8 numpy array or torch tensor) except
+        the enc and payload columns: metadata, the public share with its length prefix, the
+        config ids and the `00 20` / u32 length prefixes of both ciphertexts.  `public_shares`:
+        (n, public_share) rows of the same kind as `reports`, or None when there are none."""
+        n = reports.shape[0]
+        head = np.empty((n, 28), np.uint8)
+        head[:, :16] = np.asarray(report_ids, np.uint8).reshape(n, 16)
+        head[:, 16:24] = np.asarray(times, np.uint64).astype(">u8").view(np.uint8).reshape(n, 8)
+        head[:, 24:28] = np.frombuffer(struct.pack(">I", self.public_share), np.uint8)
+        reports[:, :28] = _like(reports, head)
+        if self.public_share:
+            reports[:, self.o_public:self.o_public + self.public_share] = public_shares
+        for o, cfg, plen in ((self.o_leader, leader_config_id, self.leader_payload),
+                             (self.o_helper, helper_config_id, self.helper_payload)):
+            pre = np.frombuffer(bytes([cfg]) + struct.pack(">H", ENC_LEN), np.uint8)
+            reports[:, o:o + 3] = _like(reports, pre)
+            ln = np.frombuffer(struct.pack(">I", plen), np.uint8)
+            reports[:, o + 3 + ENC_LEN:o + 3 + ENC_LEN + 4] = _like(reports, ln)
+
+    def columns(self, reports, which: str):
+        """(enc column, payload column) views of `reports` for "leader" or "helper"."""
+        oe, op, pl = ((self.o_leader_enc, self.o_leader_payload, self.leader_payload)
+                      if which == "leader" else
+                      (self.o_helper_enc, self.o_helper_payload, self.helper_payload))
+        return reports[:, oe:oe + ENC_LEN], reports[:, op:op + pl]
+
+
+def round_times(times, time_precision: int) -> np.ndarray:
+    """Time::to_batch_interval_start: each time rounded down to a multiple of the precision."""
+    t = np.asarray(times, np.uint64)
+    return t - t % np.uint64(time_precision)
+
+
+class ClientBatch:
+    """The batched `Client` of one task: `vdaf` a `Prio3Gpu`, the two aggregators' `HpkeConfig`s
+    (DHKEM(X25519, HKDF-SHA256) with any KDF and AEAD) and the task's time precision in seconds."""
+
+    def __init__(self, vdaf, task_id: bytes, leader_config: H.HpkeConfig,
+                 helper_config: H.HpkeConfig, time_precision: int):
+        if len(task_id) != 32:
+            raise ValueError("TaskId is 32 bytes")
+        if time_precision <= 0:
+            raise ValueError("time precision must be positive")
+        for c in (leader_config, helper_config):
+            if c.kem_id != H.KEM_X25519_HKDF_SHA256:
+                raise ValueError("the GPU seals to DHKEM(X25519, HKDF-SHA256) configs only")
+        self.vdaf, self.task_id = vdaf, bytes(task_id)
+        self.leader_config, self.helper_config = leader_config, helper_config
+        self.time_precision = int(time_precision)
+        s = vdaf.sizes
+        self.layout = ReportLayout(s.public_share, s.leader_input_share, s.helper_input_share)
+        self.report_len = self.layout.report_len
+        self._state = None
+
+    def close(self):
+        if self._state is not None:
+            self._state.close()
+            self._state = None
+
+    def _shard_state(self, n: int):
+        if self._state is None or self._state.capacity < n:
+            self.close()
+            self._state = self.vdaf.new_state(1, n)
+        return self._state
+
+    def prepare_reports(self, measurements, report_ids=None, times=None, rand=None, sk_es=None,
+                        device_out: bool = False):
+        """The batched `prepare_report`: n measurements ((n,) or (n, length) integers, as
+        `Prio3Gpu.shard` takes them) -> the (n, report_len) uint8 matrix of their encoded
+        Reports (a numpy array; with `device_out` the torch tensor on the GPU it was built in).
+        report_ids (n, 16), rand (n, vdaf.random_size()) and sk_es (2, n, 32: the leader's and the
+        helper's ephemeral private keys) default to os.urandom, times (n,) seconds to now; times
+        are rounded down to the time precision.  Shares, frames and ciphertexts never leave the
+        GPU; only the report matrix is copied back."""
+        import torch
+        v, L = self.vdaf, self.layout
+        meas = np.asarray(measurements)
+        n = meas.shape[0]
+        dev = torch.device("cuda", v.device)
+
+        def rnd(shape):
+            return np.frombuffer(os.urandom(int(np.prod(shape))), np.uint8).reshape(shape).copy()
+
+        ids = rnd((n, 16)) if report_ids is None else \
+            np.ascontiguousarray(report_ids, np.uint8).reshape(n, 16)
+        tm = round_times(np.full(n, int(_time.time())) if times is None else times,
+                         self.time_precision)
+        rand = rnd((n, v.random_size())) if rand is None else np.asarray(rand, np.uint8)
+        sk = rnd((2, n, 32)) if sk_es is None else \
+            np.ascontiguousarray(sk_es, np.uint8).reshape(2, n, 32)
+        reports = torch.zeros((n, L.report_len), dtype=torch.uint8, device=dev)
+        if n == 0:
+            return reports if device_out else reports.cpu().numpy()
+        d_ids = torch.from_numpy(ids.copy()).to(dev)
+        d_tm = torch.from_numpy(tm.astype(np.int64)).to(dev)   # the same 64 bits
+        d_meas = torch.from_numpy(np.ascontiguousarray(meas).astype(np.int64)).to(dev)
+        d_rand = torch.from_numpy(np.ascontiguousarray(rand)).to(dev)
+        d_sk = torch.from_numpy(sk.copy()).to(dev)
+        d_pub = torch.empty((n, L.public_share), dtype=torch.uint8, device=dev) \
+            if L.public_share else None
+        d_lin = torch.empty((n, L.leader_share), dtype=torch.uint8, device=dev)
+        d_hin = torch.empty((n, L.helper_share), dtype=torch.uint8, device=dev)
+        torch.cuda.synchronize(dev)   # the engine works on its own stream
+        v.shard(self._shard_state(n), d_ids, d_meas, d_rand, out=(d_pub, d_lin, d_hin))
+        L.write_fixed(reports, ids, tm, d_pub, self.leader_config.id, self.helper_config.id)
+        torch.cuda.synchronize(dev)
+        for which, cfg, role, shares, k in (("leader", self.leader_config, H.ROLE_LEADER, d_lin, 0),
+                                            ("helper", self.helper_config, H.ROLE_HELPER, d_hin, 1)):
+            encs, payloads = L.columns(reports, which)
+            _, _, st = H.seal_input_shares_gpu(v, self.task_id, cfg, role, d_ids, d_tm, d_pub,
+                                               shares, d_sk[k], encs, payloads)
+            if st[:n].any():
+                raise H.HpkeError(f"sealing to the {which} failed for {int((st[:n] != 0).sum())} "
+                                  "reports (a public key of small order)")
+        d_sk.zero_()
+        return reports if device_out else reports.cpu().numpy()

@@ -67,7 +67,8 @@ const char* const kKernelNames[KID_COUNT] = {
     "k_flp_wires_mfma", "k_fpv_regen", "k_x25519", "k_hpke_open", "k_req_gather", "k_x25519_idx",
     "k_hpke_open_req", "k_decode_plaintext_input_shares", "k_req_scatter",
     // not a kernel: the request's one host-to-device copy in prio3gpu_helper_init_request
-    "copy_request", "k_p256_dh", "k_p256_dh_idx"};
+    "copy_request", "k_p256_dh", "k_p256_dh_idx", "k_x25519_eph", "k_hpke_seal",
+    "k_hpke_seal_shares"};
 
 }  // namespace
 

@@ -1,6 +1,7 @@
 // Host side of the GPU HPKE open and of the helper's aggregate-init from the request's bytes
 // (include/prio3gpu.h: prio3gpu_hpke_open_batch, prio3gpu_hpke_open_report_shares_gpu,
-// prio3gpu_helper_init_request) and the test hooks that launch only their kernels.  No Prio3
+// prio3gpu_helper_init_request), of the GPU HPKE seal (prio3gpu_hpke_seal_batch,
+// prio3gpu_seal_input_shares) and the test hooks that launch only their kernels.  No Prio3
 // kernel is in scope here: the request path hands over to the Prio3 side (engine.hip) through the
 // public prio3gpu_helper_init alone.
 #include <hip/hip_runtime.h>
@@ -18,6 +19,7 @@
 #include "plan_hpke.h"
 #include "hpke_gpu.h"
 #include "helper_request.h"
+#include "hpke_seal_gpu.h"
 
 using namespace p3g;
 using namespace p3g::eng;
@@ -571,9 +573,262 @@ int req_clear_secrets(ReqCall& q, int rc) {
   return rc;
 }
 
+// ---- batched HPKE seal on the GPU (hpke_seal_gpu.h) ---------------------------------------------
+// The suites the GPU seals: DHKEM(X25519, HKDF-SHA256) with KDF 1-3 and AEAD 1-3 (no option: the
+// seal has entry points of its own).
+bool hpke_seal_suite(uint16_t kem, uint16_t kdf, uint16_t aead) {
+  return kem == 0x0020 && kdf >= 1 && kdf <= 3 && aead >= 1 && aead <= 3;
+}
+
+// The per-report secrets of one seal call on the device: the engine's copies of the ephemeral
+// keys and of the plaintexts (null where the caller's own device buffer is read in place) and the
+// ladders' output (n encapsulated keys, then n DH values, 8 words each).
+struct SealSecrets {
+  const uint8_t* d_sk = nullptr;
+  size_t sk_bytes = 0;
+  const uint8_t* d_pt = nullptr;
+  size_t pt_bytes = 0;
+  uint32_t* d_eph = nullptr;
+  size_t eph_bytes = 0;
+};
+
+// Stage the n ephemeral keys and run both ladders of every report: s->d_eph.
+int seal_ladders(prio3gpu_ctx* c, const uint8_t* pk, size_t n, const uint8_t* sk_es,
+                 SealSecrets* s) {
+  CHK(c->seal[1].ensure(n * 64));
+  s->d_eph = static_cast<uint32_t*>(c->seal[1].p);
+  s->eph_bytes = n * 64;
+  s->sk_bytes = n * 32;
+  CHK(stage_in(c, c->seal[0], sk_es, n * 32, &s->d_sk, kHpkeMinStage));
+  X25519Point pkw;
+  memcpy(pkw.w, pk, 32);  // little-endian host
+  {
+    PROF(KID_X25519_EPH);
+    hipLaunchKernelGGL(k_x25519_eph, dim3((unsigned)((n + 63) / 64), 2), dim3(64), 0, c->stream,
+                       (uint32_t)n, s->d_sk, pkw, s->d_eph);
+  }
+  HIPCHK(hipGetLastError());
+  return 0;
+}
+
+// Zero the engine's copies of a seal call's secrets, after its launches ended with rc.
+int seal_clear_secrets(prio3gpu_ctx* c, const SealSecrets& s, int rc) {
+  bool cleared = true;
+  if (s.d_sk && s.d_sk == c->seal[0].u8())
+    cleared &= hipMemsetAsync(c->seal[0].p, 0, s.sk_bytes, c->stream) == hipSuccess;
+  if (s.d_pt && s.d_pt == c->seal[2].u8() && s.pt_bytes)
+    cleared &= hipMemsetAsync(c->seal[2].p, 0, s.pt_bytes, c->stream) == hipSuccess;
+  if (s.d_eph) cleared &= hipMemsetAsync(s.d_eph, 0, s.eph_bytes, c->stream) == hipSuccess;
+  if (!cleared && !rc) {
+    set_err("clearing the seal's secrets failed");
+    rc = PRIO3GPU_E_HIP;
+  }
+  if (rc) (void)hipStreamSynchronize(c->stream);
+  return rc;
+}
+
+// Where a seal writes an output of `bytes` bytes: the caller's buffer when it is device memory,
+// else staging (zeroed, so what no lane writes reads as zero).
+int seal_out(prio3gpu_ctx* c, DevBuf& buf, uint8_t* dst, size_t bytes, uint8_t** d_out) {
+  if (dst && is_device_ptr(dst)) {
+    *d_out = dst;
+    return 0;
+  }
+  CHK(buf.ensure(std::max<size_t>(bytes, kHpkeMinStage)));
+  *d_out = buf.u8();
+  if (bytes) HIPCHK(hipMemsetAsync(*d_out, 0, bytes, c->stream));
+  return 0;
+}
+
+int hpke_seal_batch_impl(prio3gpu_ctx* c, uint16_t kem_id, uint16_t kdf_id, uint16_t aead_id,
+                         const uint8_t* pk, const uint8_t* info, size_t info_len, size_t n,
+                         const uint8_t* sk_es, const uint8_t* aads, const uint64_t* aad_offsets,
+                         const uint8_t* pts, const uint64_t* pt_offsets, uint8_t* encs,
+                         uint8_t* cts, const uint64_t* ct_offsets, uint8_t* status) {
+  HpkeBatchConsts bc;
+  if (!hpke_batch_consts(kem_id, kdf_id, aead_id, pk, info, info_len, &bc)) {
+    set_err("HPKE primitives unavailable");
+    return PRIO3GPU_E_UNSUPPORTED;
+  }
+  HIPCHK(hipSetDevice(c->device));
+  uint64_t aad_total = 0, pt_total = 0, ct_total = 0, ct_first = 0;
+  CHK(hpke_fetch_u64(c, aad_offsets + n, &aad_total));
+  CHK(hpke_fetch_u64(c, pt_offsets + n, &pt_total));
+  CHK(hpke_fetch_u64(c, ct_offsets + n, &ct_total));
+  CHK(hpke_fetch_u64(c, ct_offsets, &ct_first));
+  if ((aad_total && !aads) || (pt_total && !pts) || (ct_total && !cts) || ct_first > ct_total) {
+    set_err("HPKE seal: null data buffer or offsets out of order");
+    return PRIO3GPU_E_ARG;
+  }
+  SealSecrets s;
+  uint8_t *d_enc = nullptr, *d_ct = nullptr, *d_st = nullptr;
+  int rc = [&]() -> int {
+    const uint8_t *d_aad, *d_aoff, *d_poff, *d_coff, *d_st_in;
+    CHK(stage_in(c, c->hpke[1], aads, aad_total, &d_aad, kHpkeMinStage));
+    CHK(stage_in(c, c->hpke[2], aad_offsets, (n + 1) * 8, &d_aoff, kHpkeMinStage));
+    CHK(stage_in(c, c->seal[3], pt_offsets, (n + 1) * 8, &d_poff, kHpkeMinStage));
+    CHK(stage_in(c, c->hpke[4], ct_offsets, (n + 1) * 8, &d_coff, kHpkeMinStage));
+    CHK(stage_in(c, c->hpke[7], status, n, &d_st_in, kHpkeMinStage));
+    d_st = const_cast<uint8_t*>(d_st_in);
+    CHK(seal_out(c, c->seal[7], encs, n * 32, &d_enc));
+    CHK(seal_out(c, c->seal[8], cts, ct_total, &d_ct));
+    s.pt_bytes = pt_total;
+    CHK(stage_in(c, c->seal[2], pts, pt_total, &s.d_pt, kHpkeMinStage));
+    CHK(seal_ladders(c, pk, n, sk_es, &s));
+    {
+      PROF(KID_HPKE_SEAL);
+      hpke_suite_dispatch(bc, [&](auto kdf, auto aead) {
+        hipLaunchKernelGGL((k_hpke_seal<decltype(kdf)::value, decltype(aead)::value>),
+                           dim3((unsigned)((n + 255) / 256)), dim3(256), 0, c->stream, (uint32_t)n,
+                           bc, s.d_eph, d_aad, reinterpret_cast<const uint64_t*>(d_aoff),
+                           aad_total, s.d_pt, reinterpret_cast<const uint64_t*>(d_poff), pt_total,
+                           d_enc, d_ct, reinterpret_cast<const uint64_t*>(d_coff), ct_total, d_st);
+      });
+    }
+    HIPCHK(hipGetLastError());
+    return 0;
+  }();
+  CHK(seal_clear_secrets(c, s, rc));
+  CHK(copy_out(c, encs, d_enc, n * 32));
+  if (d_ct != cts && ct_total > ct_first)
+    HIPCHK(hipMemcpyAsync(cts + ct_first, d_ct + ct_first, ct_total - ct_first,
+                          hipMemcpyDeviceToHost, c->stream));
+  CHK(copy_out(c, status, d_st, n));
+  return finish_call(c, {sk_es, aads, aad_offsets, pts, pt_offsets, encs, cts, ct_offsets, status});
+}
+
+// `rows` rows of `width` bytes from packed device rows to the caller's host rows `pitch` apart,
+// through host memory: only the rows' own bytes are written.
+int seal_rows_to_host(prio3gpu_ctx* c, uint8_t* dst, size_t pitch, const uint8_t* d_src,
+                      size_t width, size_t rows) {
+  if (pitch == width) {
+    HIPCHK(hipMemcpyAsync(dst, d_src, rows * width, hipMemcpyDeviceToHost, c->stream));
+    return 0;
+  }
+  std::vector<uint8_t> tmp(rows * width);
+  HIPCHK(hipMemcpyAsync(tmp.data(), d_src, tmp.size(), hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(hipStreamSynchronize(c->stream));
+  for (size_t i = 0; i < rows; ++i) memcpy(dst + i * pitch, tmp.data() + i * width, width);
+  return 0;
+}
+
 }  // namespace
 
 extern "C" {
+
+int prio3gpu_hpke_seal_batch(prio3gpu_ctx* c, uint16_t kem_id, uint16_t kdf_id, uint16_t aead_id,
+                             const uint8_t* pk, size_t pk_len, const uint8_t* info,
+                             size_t info_len, size_t n, const uint8_t* sk_es, const uint8_t* aads,
+                             const uint64_t* aad_offsets, const uint8_t* pts,
+                             const uint64_t* pt_offsets, uint8_t* encs, uint8_t* cts,
+                             const uint64_t* ct_offsets, uint8_t* status) {
+  if (!c) {
+    set_err("null context");
+    return PRIO3GPU_E_ARG;
+  }
+  if (!hpke_seal_suite(kem_id, kdf_id, aead_id)) {
+    set_err("HPKE suite 0x%04x/%u/%u is not sealed on the GPU", kem_id, kdf_id, aead_id);
+    return PRIO3GPU_E_UNSUPPORTED;
+  }
+  if (!pk || pk_len != 32 || (info_len && !info)) {
+    set_err("HPKE seal: the public key is 32 bytes");
+    return PRIO3GPU_E_ARG;
+  }
+  if (n == 0) return 0;
+  if (!sk_es || !aad_offsets || !pt_offsets || !encs || !ct_offsets || !status ||
+      n > 0x7FFFFFFFu) {
+    set_err("HPKE seal: null argument");
+    return PRIO3GPU_E_ARG;
+  }
+  return hpke_seal_batch_impl(c, kem_id, kdf_id, aead_id, pk, info, info_len, n, sk_es, aads,
+                              aad_offsets, pts, pt_offsets, encs, cts, ct_offsets, status);
+}
+
+int prio3gpu_seal_input_shares(prio3gpu_ctx* c, const uint8_t* task_id, uint16_t kem_id,
+                               uint16_t kdf_id, uint16_t aead_id, const uint8_t* pk,
+                               size_t pk_len, uint8_t recipient_role, size_t n,
+                               const uint8_t* report_ids, const uint64_t* times,
+                               const uint8_t* public_shares, uint32_t public_share_len,
+                               const uint8_t* input_shares, uint32_t input_share_len,
+                               size_t input_share_pitch, const uint8_t* sk_es, uint8_t* out_encs,
+                               size_t enc_pitch, uint8_t* out_payloads, size_t payload_pitch,
+                               uint8_t* status) {
+  if (!c) {
+    set_err("null context");
+    return PRIO3GPU_E_ARG;
+  }
+  if (!hpke_seal_suite(kem_id, kdf_id, aead_id)) {
+    set_err("HPKE suite 0x%04x/%u/%u is not sealed on the GPU", kem_id, kdf_id, aead_id);
+    return PRIO3GPU_E_UNSUPPORTED;
+  }
+  if (!pk || pk_len != 32 || !task_id) {
+    set_err("seal_input_shares: the public key and the task id are 32 bytes");
+    return PRIO3GPU_E_ARG;
+  }
+  if (n == 0) return 0;
+  const size_t plen = 6 + (size_t)input_share_len + 16;
+  const size_t spitch = input_share_pitch ? input_share_pitch : input_share_len;
+  const size_t epitch = enc_pitch ? enc_pitch : 32;
+  const size_t ppitch = payload_pitch ? payload_pitch : plen;
+  if (!report_ids || !times || (public_share_len && !public_shares) ||
+      (input_share_len && !input_shares) || !sk_es || !out_encs || !out_payloads || !status ||
+      n > 0x7FFFFFFFu) {
+    set_err("seal_input_shares: null argument");
+    return PRIO3GPU_E_ARG;
+  }
+  if (spitch < input_share_len || epitch < 32 || ppitch < plen) {
+    set_err("seal_input_shares: a pitch is shorter than its row");
+    return PRIO3GPU_E_ARG;
+  }
+  uint8_t info[20];
+  input_share_info(/*ROLE_CLIENT*/ 1, recipient_role, info);
+  HpkeBatchConsts bc;
+  if (!hpke_batch_consts(kem_id, kdf_id, aead_id, pk, info, sizeof info, &bc)) {
+    set_err("HPKE primitives unavailable");
+    return PRIO3GPU_E_UNSUPPORTED;
+  }
+  ReqTaskId tid;
+  memcpy(tid.w, task_id, 32);  // little-endian host: byte j at bits 8 (j & 3) of word j >> 2
+  HIPCHK(hipSetDevice(c->device));
+  const size_t share_bytes = (n - 1) * spitch + input_share_len;
+  SealSecrets s;
+  // host outputs are sealed into packed staging rows, device outputs in place at their pitches
+  const bool enc_host = !is_device_ptr(out_encs), pay_host = !is_device_ptr(out_payloads);
+  uint8_t *d_enc = nullptr, *d_pay = nullptr, *d_st = nullptr;
+  int rc = [&]() -> int {
+    const uint8_t *d_rid, *d_time, *d_pub, *d_st_in;
+    CHK(stage_in(c, c->seal[4], report_ids, n * 16, &d_rid, kHpkeMinStage));
+    CHK(stage_in(c, c->seal[5], times, n * 8, &d_time, kHpkeMinStage));
+    CHK(stage_in(c, c->seal[6], public_shares, n * (size_t)public_share_len, &d_pub,
+                 kHpkeMinStage));
+    CHK(stage_in(c, c->hpke[7], status, n, &d_st_in, kHpkeMinStage));
+    d_st = const_cast<uint8_t*>(d_st_in);
+    CHK(seal_out(c, c->seal[7], enc_host ? nullptr : out_encs, n * 32, &d_enc));
+    CHK(seal_out(c, c->seal[8], pay_host ? nullptr : out_payloads, n * plen, &d_pay));
+    s.pt_bytes = share_bytes;
+    CHK(stage_in(c, c->seal[2], input_shares, share_bytes, &s.d_pt, kHpkeMinStage));
+    CHK(seal_ladders(c, pk, n, sk_es, &s));
+    {
+      PROF(KID_HPKE_SEAL_SHARES);
+      hpke_suite_dispatch(bc, [&](auto kdf, auto aead) {
+        hipLaunchKernelGGL((k_hpke_seal_shares<decltype(kdf)::value, decltype(aead)::value>),
+                           dim3((unsigned)((n + 255) / 256)), dim3(256), 0, c->stream, (uint32_t)n,
+                           bc, tid, s.d_eph, d_rid, reinterpret_cast<const uint64_t*>(d_time),
+                           d_pub, public_share_len, s.d_pt, input_share_len, (uint64_t)spitch,
+                           d_enc, (uint64_t)(enc_host ? 32 : epitch), d_pay,
+                           (uint64_t)(pay_host ? plen : ppitch), d_st);
+      });
+    }
+    HIPCHK(hipGetLastError());
+    return 0;
+  }();
+  CHK(seal_clear_secrets(c, s, rc));
+  if (enc_host) CHK(seal_rows_to_host(c, out_encs, epitch, d_enc, 32, n));
+  if (pay_host) CHK(seal_rows_to_host(c, out_payloads, ppitch, d_pay, plen, n));
+  CHK(copy_out(c, status, d_st, n));
+  return finish_call(c, {report_ids, times, public_shares, input_shares, sk_es, out_encs,
+                         out_payloads, status});
+}
 
 int prio3gpu_hpke_open_batch(prio3gpu_ctx* c, uint16_t kem_id, uint16_t kdf_id, uint16_t aead_id,
                              const uint8_t* sk, size_t sk_len, const uint8_t* pk, size_t pk_len,

@@ -86,7 +86,8 @@ enum KernelId {
   KID_SHARD_MEAS, KID_SHARD_JR, KID_PROVE, KID_SHARD_PROOF, KID_REPORT_META, KID_REPORT_META_FOLD,
   KID_SHARD_NORM, KID_JR_RING, KID_FLP_QUERY_LANE, KID_FLP_WIRES_COLS, KID_FLP_WIRES_MFMA,
   KID_FPV_REGEN, KID_X25519, KID_HPKE_OPEN, KID_REQ_GATHER, KID_X25519_IDX, KID_HPKE_OPEN_REQ,
-  KID_DECODE_PT, KID_REQ_SCATTER, KID_REQ_COPY, KID_P256_DH, KID_P256_DH_IDX, KID_COUNT
+  KID_DECODE_PT, KID_REQ_SCATTER, KID_REQ_COPY, KID_P256_DH, KID_P256_DH_IDX, KID_X25519_EPH,
+  KID_HPKE_SEAL, KID_HPKE_SEAL_SHARES, KID_COUNT
 };
 
 // Per-kernel HIP-event timing on the context's stream (opt-in; used by bench.py).
@@ -139,6 +140,11 @@ struct prio3gpu_ctx {
   // plaintexts, plaintext offsets, faults, and the host-fallback reports' compact rows; grown on
   // demand to the largest job seen
   DevBuf req[8];
+  // prio3gpu_hpke_seal_batch / prio3gpu_seal_input_shares: staging of host inputs (ephemeral keys,
+  // plaintexts or share rows, plaintext offsets, report IDs, times, public shares), the ladders'
+  // encapsulated keys and DH values, and staging of host outputs (encs, ciphertexts); grown on
+  // demand.  The AADs, their offsets, the ciphertext offsets and the statuses share hpke[]
+  DevBuf seal[9];
   // Engine options (prio3gpu_ctx_set_option; include/prio3gpu.h lists them).  The defaults are the
   // measured-fastest paths; every alternative is parity-tested against the oracle.
   bool speculate = true;     // "speculate": accumulation from k_jr's column sums (0: direct)

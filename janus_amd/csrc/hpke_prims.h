@@ -6,7 +6,9 @@
 //                                               HKDF-SHA384 (KDF 2) and HKDF-SHA512 (KDF 3)
 //   chacha20_block, Poly1305                    RFC 8439 §2.3, §2.5
 //   chacha20poly1305_open                       RFC 8439 §2.8 over GHASH's byte-source interface
+//   chacha20poly1305_seal                       its mirror for the GPU seal (hpke_seal_gpu.h)
 //   load_block / PackedBytes                    that interface's contiguous source
+//   store_block / mask_block                    a block's bytes out; zeros past a short block's end
 // Nothing here indexes memory or branches by key material: rotations are plain shifts, Poly1305's
 // final subtraction is a select, the tag comparison has no early exit.
 #pragma once
@@ -465,6 +467,68 @@ P3G_HP bool chacha20poly1305_open(const uint32_t key[8], const uint32_t nonce[3]
     }
   }
   return true;
+}
+
+// The first min(rem, 16) bytes of block words c to p: four word stores where p is word-aligned and
+// the block whole, byte stores otherwise (the choice depends on the address and the length only).
+P3G_HP void store_block(uint8_t* p, uint64_t rem, const uint32_t c[4]) {
+  if (rem >= 16 && ((uintptr_t)p & 3u) == 0) {
+    __builtin_memcpy(__builtin_assume_aligned(p, 4), c, 16);
+    return;
+  }
+#pragma unroll
+  for (int j = 0; j < 16; ++j)
+    if ((uint64_t)j < rem) p[j] = (uint8_t)(c[j >> 2] >> (8 * (j & 3)));
+}
+
+// c &= the first min(rem, 16) bytes: what enters a MAC of a short last block is zero past its end
+P3G_HP void mask_block(uint32_t c[4], uint64_t rem) {
+#pragma unroll
+  for (int i = 0; i < 4; ++i) {
+    const uint64_t lo = 4u * (uint64_t)i;
+    c[i] &= rem >= lo + 4 ? 0xffffffffu : rem <= lo ? 0u : (1u << (8 * (uint32_t)(rem - lo))) - 1u;
+  }
+}
+
+// ------------------------------------------------------------------------------------------------
+// AEAD_CHACHA20_POLY1305 seal (RFC 8439 §2.8), the mirror of the open: key 8 and nonce 3
+// little-endian words; aad and pt are byte sources.  ct gets pt.len() ciphertext bytes and the
+// 16-byte tag.  One pass over the plaintext: each 16-byte piece is XORed with the keystream
+// (counter 1 onwards), stored, and absorbed by the MAC (zero past the end of a short last piece);
+// the MAC covers pad16(aad) || pad16(ct) || len(aad) || len(ct) under the one-time key of block 0.
+// ------------------------------------------------------------------------------------------------
+template <class Aad, class Pt>
+P3G_HP void chacha20poly1305_seal(const uint32_t key[8], const uint32_t nonce[3], const Aad& aad,
+                                  const Pt& pt, uint8_t* ct) {
+  uint32_t ks[16], d[4], t[4];
+  chacha20_block(key, 0u, nonce, ks);
+  Poly1305 mac;
+  poly1305_init(mac, ks);
+  const uint64_t alen = aad.len(), plen = pt.len();
+  for (uint64_t o = 0; o < alen; o += 16) {
+    aad.block(o, d);
+    poly1305_block(mac, d, 1u << 24);
+  }
+  for (uint64_t o = 0; o < plen; o += 64) {
+    chacha20_block(key, (uint32_t)(o >> 6) + 1u, nonce, ks);
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+      const uint64_t oo = o + 16 * q;
+      if (oo < plen) {
+        pt.block(oo, d);
+#pragma unroll
+        for (int i = 0; i < 4; ++i) d[i] ^= ks[4 * q + i];
+        mask_block(d, plen - oo);
+        store_block(ct + oo, plen - oo, d);
+        poly1305_block(mac, d, 1u << 24);
+      }
+    }
+  }
+  d[0] = (uint32_t)alen; d[1] = (uint32_t)(alen >> 32);
+  d[2] = (uint32_t)plen; d[3] = (uint32_t)(plen >> 32);
+  poly1305_block(mac, d, 1u << 24);
+  poly1305_finish(mac, t);
+  store_block(ct + plen, 16, t);
 }
 
 }  // namespace p3g

@@ -8,6 +8,8 @@
   HpkeKeypair                        core/src/hpke.rs:233-255
   open_report_shares                 the helper's per-report open loop, batched over host threads
                                      (aggregator/src/aggregator.rs:1634-1700)
+  seal_batch_gpu / seal_input_shares_gpu   the client's per-share seal (client/src/lib.rs:228-251),
+                                     batched on the GPU (janus_amd/csrc/hpke_seal_gpu.h)
 
 Errors: `HpkeError` where hpke::open / hpke::seal return `Error::Hpke`, `ValueError` for an
 unsupported suite (`Error::InvalidConfiguration`).
@@ -206,6 +208,122 @@ def open_batch_gpu(gpu, keypair: HpkeKeypair, info: bytes, encs, aads, aad_offse
                                        len(info), n, *args), "HPKE GPU open")
     del keep
     return pts, pt_offsets, status
+
+
+def _dev_ptr(x, dtype):
+    """_ptr that also takes a torch tensor (host or device): its pointer, the tensor kept alive."""
+    if hasattr(x, "data_ptr"):
+        if not x.is_contiguous():
+            raise ValueError("tensors must be contiguous")
+        return x.data_ptr(), x
+    return _ptr(x, dtype)
+
+
+def seal_batch_gpu(gpu, config: HpkeConfig, info: bytes, sk_es, aads, aad_offsets, pts,
+                   pt_offsets, status=None, encs=None, cts=None, ct_offsets=None,
+                   n: Optional[int] = None):
+    """n HPKE seals to ONE recipient config on the GPU (prio3gpu_hpke_seal_batch), each under its
+    own ephemeral private key: any DHKEM(X25519, HKDF-SHA256) suite (KDF HKDF-SHA256 / -SHA384 /
+    -SHA512 x AEAD AES-128-GCM / AES-256-GCM / ChaCha20-Poly1305), no option needed.  `ValueError`
+    for any other suite (P-256 seals stay on `seal`), nothing launched.
+
+    `gpu` is a `Prio3Gpu` or a context handle.  Report i: ephemeral key = sk_es[32 i : 32 i + 32],
+    aad = aads[aad_offsets[i] : aad_offsets[i+1]], plaintext = pts[pt_offsets[i] :
+    pt_offsets[i+1]].  Buffers are numpy arrays (host), torch tensors (host or device) or integer
+    device pointers (then `n`, `encs`, `cts`, `ct_offsets` and `status` must be given).  By
+    default ciphertext i has the plaintext's length + 16 and the ciphertexts are packed.
+    -> (encs, cts, ct_offsets, status): enc i = encs[32 i : 32 i + 32], ciphertext || tag i =
+    cts[ct_offsets[i] : ct_offsets[i+1]] -- the bytes `seal` gives with the same ephemeral key.  A
+    report that is not sealed (status non-zero on entry, a public key of small order, a slot that
+    is too short) has zeros in both and, unless it was skipped, status 4."""
+    if n is None:
+        n = len(np.asarray(pt_offsets)) - 1
+    if ct_offsets is None:
+        lens = np.diff(np.asarray(pt_offsets, np.uint64).astype(np.int64)) + 16
+        ct_offsets = np.concatenate([[0], np.cumsum(lens)]).astype(np.uint64)
+    if cts is None:
+        cts = np.zeros(max(1, int(np.asarray(ct_offsets)[-1])), np.uint8)
+    if encs is None:
+        encs = np.zeros(max(1, n) * 32, np.uint8)
+    if status is None:
+        status = np.zeros(max(1, n), np.uint8)
+    keep, args = [], []
+    for x, dt in ((sk_es, np.uint8), (aads, np.uint8), (aad_offsets, np.uint64), (pts, np.uint8),
+                  (pt_offsets, np.uint64), (encs, np.uint8), (cts, np.uint8),
+                  (ct_offsets, np.uint64), (status, np.uint8)):
+        p, k = _dev_ptr(x, dt)
+        args.append(p)
+        keep.append(k)
+    for out, k in ((encs, keep[5]), (cts, keep[6]), (status, keep[8])):  # written in place
+        assert k is None or k is out, "encs / cts / status must be contiguous uint8 arrays"
+    _rc(lib().prio3gpu_hpke_seal_batch(_ctx_handle(gpu), config.kem_id, config.kdf_id,
+                                       config.aead_id, _buf(config.public_key),
+                                       len(config.public_key), _buf(info), len(info), n, *args),
+        "HPKE GPU seal")
+    del keep
+    return encs, cts, ct_offsets, status
+
+
+def _rows(x, n: int, width: int, what: str):
+    """(pointer, row pitch, keep-alive) of n rows of `width` bytes: a 2-D uint8 numpy array or
+    torch tensor whose rows are contiguous inside and `pitch` >= width bytes apart (a column slice
+    of a wider buffer keeps its pitch), or an (integer device pointer, pitch) pair."""
+    if isinstance(x, tuple):
+        return int(x[0]), int(x[1]), None
+    if hasattr(x, "data_ptr"):
+        if tuple(x.shape) != (n, width) or x.element_size() != 1 or (width and x.stride(1) != 1):
+            raise ValueError(f"{what}: expected a ({n}, {width}) uint8 tensor with contiguous rows")
+        return x.data_ptr(), (x.stride(0) if n > 1 else width), x
+    a = np.asarray(x)
+    if a.shape != (n, width) or a.dtype != np.uint8 or (width and a.strides[1] != 1):
+        raise ValueError(f"{what}: expected a ({n}, {width}) uint8 array with contiguous rows")
+    return a.ctypes.data, (a.strides[0] if n > 1 else width), a
+
+
+def seal_input_shares_gpu(gpu, task_id: bytes, config: HpkeConfig, recipient_role: int,
+                          report_ids, times, public_shares, input_shares, sk_es, out_encs=None,
+                          out_payloads=None, status=None):
+    """Seal n Prio3 input shares to one aggregator on the GPU (prio3gpu_seal_input_shares): for
+    report i, `seal(config, application_info(INPUT_SHARE, CLIENT, recipient_role),
+    PlaintextInputShare(no extensions, input_shares[i]), input_share_aad(task_id, report_ids[i],
+    times[i], public_shares[i]), sk_es[i])` -- neither frame is built in memory.
+
+    report_ids (n, 16), public_shares (n, public_share_len) or None, sk_es (n, 32): uint8 numpy
+    arrays or torch tensors, packed; times (n,) uint64; input_shares (n, len) uint8 whose rows may
+    be a column slice of a wider buffer, like out_encs (n, 32) and out_payloads (n, 6 + len + 16):
+    only those columns are written (host or device; e.g. the columns of a fixed-stride Report
+    buffer; allocated as numpy arrays by default).  -> (out_encs, out_payloads, status); a report
+    that is not sealed has zeros in both columns and, unless skipped on entry, status 4."""
+    tid = np.frombuffer(bytes(task_id), np.uint8).copy()
+    if tid.size != 32:
+        raise ValueError("TaskId is 32 bytes")
+    n, slen = int(input_shares.shape[0]), int(input_shares.shape[1])
+    plen = 6 + slen + 16
+    if out_encs is None:
+        out_encs = np.zeros((n, 32), np.uint8)
+    if out_payloads is None:
+        out_payloads = np.zeros((n, plen), np.uint8)
+    if status is None:
+        status = np.zeros(max(1, n), np.uint8)
+    pslen = 0 if public_shares is None else int(public_shares.shape[1])
+    p_sh, sh_pitch, k0 = _rows(input_shares, n, slen, "input shares")
+    p_enc, enc_pitch, k1 = _rows(out_encs, n, 32, "out_encs")
+    p_pay, pay_pitch, k2 = _rows(out_payloads, n, plen, "out_payloads")
+    assert (k1 is out_encs or k1 is None) and (k2 is out_payloads or k2 is None)
+    p_rid, k3 = _dev_ptr(report_ids, np.uint8)
+    p_tm, k4 = _dev_ptr(times, np.uint64)
+    p_pub, k5 = _dev_ptr(public_shares, np.uint8) if pslen else (None, None)
+    p_sk, k6 = _dev_ptr(sk_es, np.uint8)
+    p_st, k7 = _dev_ptr(status, np.uint8)
+    assert k7 is None or k7 is status, "status must be a contiguous uint8 array"
+    _rc(lib().prio3gpu_seal_input_shares(_ctx_handle(gpu), tid.ctypes.data, config.kem_id,
+                                         config.kdf_id, config.aead_id, _buf(config.public_key),
+                                         len(config.public_key), recipient_role, n, p_rid, p_tm,
+                                         p_pub, pslen, p_sh, slen, sh_pitch, p_sk, p_enc,
+                                         enc_pitch, p_pay, pay_pitch, p_st),
+        "seal input shares (GPU)")
+    del k0, k1, k2, k3, k4, k5, k6, k7
+    return out_encs, out_payloads, status
 
 
 def open_report_shares(task_id: bytes, req, task_keys: Sequence[HpkeKeypair],

@@ -5,7 +5,8 @@ out, pipelined over jobs by HelperAggregateInit.handle_jobs (decode + HPKE of jo
 while the GPU prepares job k).  --config picks the VDAF (bench.py's CONFIGS; default
 Prio3SumVec(8, 1000, 89)).  Inputs: seeded random nonces, client
 randomness and measurements, shares from the GPU client shard, leader prep shares from the GPU leader prepare_init, helper shares sealed to
-one X25519/HKDF-SHA256/AES-128-GCM key -- all made before timing.
+one X25519/HKDF-SHA256/AES-128-GCM key (on the GPU, hpke.seal_input_shares_gpu; a P-256 --suite
+seals on the host) -- all made before timing.
 
 --hpke takes one mode or a comma-separated list (host, gpu, fused).  With a list the same
 requests run through every mode in turn within each repetition (mode A, B, C, A, B, C, ...), so
@@ -95,11 +96,20 @@ def main():
         hin = d_hin.cpu().numpy()
         job_nonces.append(nonces)
         times = [1_700_000_000 + (j * M + i) % 3600 for i in range(M)]
-        cts = []
-        for i in range(M):
-            pt = b"\0\0" + len(hin[i]).to_bytes(4, "big") + hin[i].tobytes()
-            aad = H.input_share_aad(task_id, nonces[i].tobytes(), times[i], pub[i].tobytes())
-            cts.append(H.seal(tk.config, info, pt, aad))
+        if tk.config.kem_id == H.KEM_X25519_HKDF_SHA256:    # sealed on the GPU, from device rows
+            sk_es = np.frombuffer(os.urandom(32 * M), np.uint8).reshape(M, 32).copy()
+            encs, pays, sst = H.seal_input_shares_gpu(
+                v, task_id, tk.config, H.ROLE_HELPER, d_nonces,
+                torch.from_numpy(np.array(times, np.int64)).to(dev), d_pub, d_hin,
+                torch.from_numpy(sk_es).to(dev))
+            assert not sst[:M].any()
+            cts = [(tk.config.id, encs[i].tobytes(), pays[i].tobytes()) for i in range(M)]
+        else:                                               # P-256 seals stay on the host
+            cts = []
+            for i in range(M):
+                pt = b"\0\0" + len(hin[i]).to_bytes(4, "big") + hin[i].tobytes()
+                aad = H.input_share_aad(task_id, nonces[i].tobytes(), times[i], pub[i].tobytes())
+                cts.append(H.seal(tk.config, info, pt, aad))
         reqs.append(C.encode_agg_init_req(C.TIME_INTERVAL, None, b"", nonces, times, pub, cts, lp))
         del d_lin, d_rand, d_meas
         print(f"generated job {j + 1}/{J}", file=sys.stderr, flush=True)
