@@ -7,8 +7,8 @@
 //   k_x25519_idx        k_x25519 over a key group (a list of report indices), enc read in place
 //   k_p256_dh_idx       k_p256_dh over a key group, enc read in place
 //   k_hpke_open_req     hpke_open_lane (of the group's suite) over a key group: enc and ciphertext
-//                       in place, the InputShareAad assembled from its five pieces, never
-//                       materialised
+//                       in place, the InputShareAad assembled from its five pieces (hpke_lane.h's
+//                       ReqAad), never materialised
 //   k_decode_plaintext_input_shares   PlaintextInputShare -> helper input share row, then faults
 //   k_req_scatter       host-fallback reports' rows and statuses into place
 // Included by engine_hpke.hip after include/prio3gpu.h.
@@ -115,40 +115,6 @@ __global__ void __launch_bounds__(64) k_p256_dh_idx(uint32_t m, P256Scalar k, P2
   }
 }
 
-struct ReqTaskId {  // the 32-byte TaskId as block words (byte j at bits 8 (j & 3) of word j >> 2)
-  uint32_t w[8];
-};
-
-// InputShareAad (messages/src/lib.rs:1790-1827; hpke.cpp's open_i) as a GHASH / Poly1305 byte
-// source:
-//   task_id[32] | report_id[16] | time u64 BE | public_share_len u32 BE | public share
-// Blocks 0, 1: the task id; block 2: the report ID; block 3: time, length and the first four
-// public-share bytes; block k >= 4: public-share bytes 16 k - 60 ..., none on a block boundary.
-struct ReqAad {
-  ReqTaskId tid;
-  const uint8_t* rid;
-  uint64_t time;
-  uint32_t pslen;
-  const uint8_t* ps;
-  DEVI uint64_t len() const { return 60 + (uint64_t)pslen; }
-  DEVI void block(uint64_t o, uint32_t d[4]) const {
-    if (o < 32) {
-#pragma unroll
-      for (int i = 0; i < 4; ++i) d[i] = o ? tid.w[4 + i] : tid.w[i];
-    } else if (o == 32) {
-      load_block(rid, 16, d);
-    } else if (o == 48) {
-      d[0] = bswap32((uint32_t)(time >> 32));
-      d[1] = bswap32((uint32_t)time);
-      d[2] = bswap32(pslen);
-      d[3] = 0;
-      for (uint32_t j = 0; j < 4 && j < pslen; ++j) d[3] |= (uint32_t)ps[j] << (8 * j);
-    } else {
-      load_block(ps + (o - 60), (uint64_t)pslen - (o - 60), d);
-    }
-  }
-};
-
 // One lane per report of a key group: hpke_open_lane with enc, ciphertext and AAD read where the
 // request has them; report r's plaintext goes to pts[pt_off[r] .. pt_off[r + 1]).  An enc_len
 // other than the KEM's Nenc (32; 65 for P-256), a payload shorter than the tag or longer than its slot: status 4, nothing read.
@@ -161,7 +127,7 @@ __global__ void __launch_bounds__(256) k_hpke_open_req(
   const uint8_t* sbox = nullptr;
   if constexpr (AEAD != 3) {
     __shared__ uint8_t sbox_lds[256];
-    aes_sbox_init(sbox_lds);
+    aes_sbox_fill(sbox_lds, threadIdx.x, blockDim.x);
     __syncthreads();
     sbox = sbox_lds;
   }

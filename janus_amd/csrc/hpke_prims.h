@@ -1,12 +1,13 @@
-// The primitives of the GPU HPKE open (hpke_gpu.h) beyond HKDF-SHA256 / AES-128-GCM, free of HIP
-// so the device kernels and a CPU test (tests/native/hpke_prims_host.cpp) run the same code:
+// The primitives of the GPU HPKE open and seal (hpke_lane.h) beyond HKDF-SHA256 (hpke_kdf256.h) and
+// AES-GCM (aes_gcm.h), free of HIP so the device kernels and a CPU test
+// (tests/native/hpke_prims_host.cpp) run the same code:
 //   sha512_compress, sha384_iv / sha512_iv      FIPS 180-4, 64-bit big-endian words
 //   msg64_* / hmac512_pads / hmac512_finish     HMAC over fixed-layout messages, 128-byte block
 //   hpke_kdf512_key_nonce                       RFC 9180 §5.1 KeySchedule(mode_base) for
 //                                               HKDF-SHA384 (KDF 2) and HKDF-SHA512 (KDF 3)
 //   chacha20_block, Poly1305                    RFC 8439 §2.3, §2.5
 //   chacha20poly1305_open                       RFC 8439 §2.8 over GHASH's byte-source interface
-//   chacha20poly1305_seal                       its mirror for the GPU seal (hpke_seal_gpu.h)
+//   chacha20poly1305_seal                       its mirror for the GPU seal
 //   load_block / PackedBytes                    that interface's contiguous source
 //   store_block / mask_block                    a block's bytes out; zeros past a short block's end
 // Nothing here indexes memory or branches by key material: rotations are plain shifts, Poly1305's
@@ -117,7 +118,7 @@ P3G_HP void sha512_compress(uint64_t h[8], uint64_t w[16]) {
 }
 
 // ------------------------------------------------------------------------------------------------
-// HMAC-SHA384 / HMAC-SHA512 over fixed-layout messages: the counterpart of hpke_gpu.h's msg_* /
+// HMAC-SHA384 / HMAC-SHA512 over fixed-layout messages: the counterpart of hpke_kdf256.h's msg_* /
 // hmac_* for a 128-byte block.  KDF is the HPKE KDF id: 2 (SHA-384, Nh = 48) or 3 (SHA-512,
 // Nh = 64).  A message is built as big-endian 64-bit words at byte offsets that are compile-time
 // constants in the kernels (constant bytes fold into the schedule).

@@ -1,4 +1,4 @@
-// What the host half (hpke.cpp) and the GPU half (hpke_gpu.h, engine_hpke.hip) of the batched HPKE
+// What the host half (hpke.cpp) and the GPU half (hpke_lane.h, engine_hpke.hip) of the batched HPKE
 // open share: the values one batch of opens under ONE keypair has in common, computed once on the
 // host.
 #pragma once

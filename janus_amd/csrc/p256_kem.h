@@ -1,12 +1,12 @@
 // The KEM half of DHKEM(P-256, HKDF-SHA256) (RFC 9180 §4.1) over p256.h, and one lane of the DH
-// kernels (hpke_gpu.h: k_p256_dh, helper_request.h: k_p256_dh_idx).  Free of HIP like p256.h: in a
-// HIP unit it hashes with sha256.h (device code), in a plain C++ build (tests/native/p256_host.cpp)
-// with the SHA-256 compression below, which has the same contract.
+// kernels (hpke_gpu.h: k_p256_dh, helper_request.h: k_p256_dh_idx).  Free of HIP like p256.h; it
+// hashes with sha256.h, device code in a HIP unit and host code in a plain C++ build
+// (tests/native/p256_host.cpp).
 #pragma once
 #include "p256.h"
+#include "sha256.h"
 
 #if defined(__HIPCC__)
-#include "sha256.h"
 #define P3G_P256_DEV __device__ __forceinline__
 #else
 #define P3G_P256_DEV inline
@@ -14,50 +14,9 @@
 
 namespace p3g {
 
-#if !defined(__HIPCC__)
-// The CPU build's SHA-256 compression (sha256.h is device code): the same contract, h absorbs the
-// block given as 16 big-endian words.
-namespace p256_host {
-inline uint32_t rotr(uint32_t x, int n) { return (x >> n) | (x << (32 - n)); }
-constexpr uint32_t kK[64] = {
-    0x428a2f98, 0x71374491, 0xb5c0fbcf, 0xe9b5dba5, 0x3956c25b, 0x59f111f1, 0x923f82a4, 0xab1c5ed5,
-    0xd807aa98, 0x12835b01, 0x243185be, 0x550c7dc3, 0x72be5d74, 0x80deb1fe, 0x9bdc06a7, 0xc19bf174,
-    0xe49b69c1, 0xefbe4786, 0x0fc19dc6, 0x240ca1cc, 0x2de92c6f, 0x4a7484aa, 0x5cb0a9dc, 0x76f988da,
-    0x983e5152, 0xa831c66d, 0xb00327c8, 0xbf597fc7, 0xc6e00bf3, 0xd5a79147, 0x06ca6351, 0x14292967,
-    0x27b70a85, 0x2e1b2138, 0x4d2c6dfc, 0x53380d13, 0x650a7354, 0x766a0abb, 0x81c2c92e, 0x92722c85,
-    0xa2bfe8a1, 0xa81a664b, 0xc24b8b70, 0xc76c51a3, 0xd192e819, 0xd6990624, 0xf40e3585, 0x106aa070,
-    0x19a4c116, 0x1e376c08, 0x2748774c, 0x34b0bcb5, 0x391c0cb3, 0x4ed8aa4a, 0x5b9cca4f, 0x682e6ff3,
-    0x748f82ee, 0x78a5636f, 0x84c87814, 0x8cc70208, 0x90befffa, 0xa4506ceb, 0xbef9a3f7, 0xc67178f2};
-}  // namespace p256_host
-inline void sha256_iv(uint32_t h[8]) {
-  h[0] = 0x6a09e667; h[1] = 0xbb67ae85; h[2] = 0x3c6ef372; h[3] = 0xa54ff53a;
-  h[4] = 0x510e527f; h[5] = 0x9b05688c; h[6] = 0x1f83d9ab; h[7] = 0x5be0cd19;
-}
-inline void sha256_compress(uint32_t h[8], uint32_t w[16]) {
-  using p256_host::rotr;
-  uint32_t s[8];
-  for (int i = 0; i < 8; ++i) s[i] = h[i];
-  for (int t = 0; t < 64; ++t) {
-    if (t >= 16) {
-      const uint32_t w15 = w[(t + 1) & 15], w2 = w[(t + 14) & 15];
-      w[t & 15] += (rotr(w15, 7) ^ rotr(w15, 18) ^ (w15 >> 3)) + w[(t + 9) & 15] +
-                   (rotr(w2, 17) ^ rotr(w2, 19) ^ (w2 >> 10));
-    }
-    const uint32_t t1 = s[7] + (rotr(s[4], 6) ^ rotr(s[4], 11) ^ rotr(s[4], 25)) +
-                        ((s[4] & s[5]) ^ (~s[4] & s[6])) + p256_host::kK[t] + w[t & 15];
-    const uint32_t t2 = (rotr(s[0], 2) ^ rotr(s[0], 13) ^ rotr(s[0], 22)) +
-                        ((s[0] & s[1]) ^ (s[0] & s[2]) ^ (s[1] & s[2]));
-    for (int i = 7; i > 0; --i) s[i] = s[i - 1];
-    s[4] += t1;
-    s[0] = t1 + t2;
-  }
-  for (int i = 0; i < 8; ++i) h[i] += s[i];
-}
-#endif
-
 // ------------------------------------------------------------------------------------------------
 // DHKEM(P-256, HKDF-SHA256) ExtractAndExpand (RFC 9180 §4.1), suite_id = "KEM" || 0x0010.
-// Messages are built as big-endian words at compile-time byte offsets, as in hpke_gpu.h.
+// Messages are built as big-endian words at compile-time byte offsets, as in hpke_kdf256.h.
 // ------------------------------------------------------------------------------------------------
 P3G_P256_DEV void p256_msg_byte(uint32_t* w, int off, uint32_t b) {
   w[off >> 2] |= b << (24 - 8 * (off & 3));

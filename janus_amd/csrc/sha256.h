@@ -1,10 +1,17 @@
-// SHA-256 on the device (FIPS 180-4), one compression at a time: the report-ID checksum of
-// prio3_kernels.h and the HKDF-SHA256 / HMAC of hpke_gpu.h chain it.
+// SHA-256 (FIPS 180-4), one compression at a time: the report-ID checksum of prio3_kernels.h and
+// the HKDF-SHA256 / HMAC of hpke_kdf256.h and p256_kem.h chain it.  Device code under hipcc; a plain
+// C++ compiler gets the same functions as host code (DEVI is `inline`, the round constants a
+// constexpr table, the rotation two shifts), so the per-lane HPKE headers built on it (x25519.h,
+// hpke_kdf256.h, aes_gcm.h, hpke_lane.h, p256_kem.h) run in CPU tests too.
 #pragma once
 #include <stdint.h>
 
+#if defined(__HIPCC__)
 #ifndef DEVI
 #define DEVI __device__ __forceinline__
+#endif
+#else
+#define DEVI inline
 #endif
 
 namespace p3g {
@@ -12,7 +19,11 @@ namespace p3g {
 // An inline variable: every translation unit that hashes carries the table in its own code
 // object, and the host side gets no shadow of it.  Not `static`: the compiler then folds the 64
 // words into the hashing kernels as literals, which changes their registers and spills.
+#if defined(__HIPCC__)
 inline __constant__ uint32_t kSha256K[64] = {
+#else
+constexpr uint32_t kSha256K[64] = {
+#endif
     0x428a2f98, 0x71374491, 0xb5c0fbcf, 0xe9b5dba5, 0x3956c25b, 0x59f111f1, 0x923f82a4, 0xab1c5ed5,
     0xd807aa98, 0x12835b01, 0x243185be, 0x550c7dc3, 0x72be5d74, 0x80deb1fe, 0x9bdc06a7, 0xc19bf174,
     0xe49b69c1, 0xefbe4786, 0x0fc19dc6, 0x240ca1cc, 0x2de92c6f, 0x4a7484aa, 0x5cb0a9dc, 0x76f988da,
@@ -22,7 +33,11 @@ inline __constant__ uint32_t kSha256K[64] = {
     0x19a4c116, 0x1e376c08, 0x2748774c, 0x34b0bcb5, 0x391c0cb3, 0x4ed8aa4a, 0x5b9cca4f, 0x682e6ff3,
     0x748f82ee, 0x78a5636f, 0x84c87814, 0x8cc70208, 0x90befffa, 0xa4506ceb, 0xbef9a3f7, 0xc67178f2};
 
+#if defined(__HIPCC__)
 DEVI uint32_t rotr32(uint32_t x, uint32_t n) { return __builtin_amdgcn_alignbit(x, x, n); }
+#else
+DEVI uint32_t rotr32(uint32_t x, uint32_t n) { return (x >> n) | (x << (32 - n)); }  // 0 < n < 32
+#endif
 DEVI uint32_t bswap32(uint32_t x) { return __builtin_bswap32(x); }
 
 DEVI void sha256_iv(uint32_t h[8]) {
@@ -32,7 +47,7 @@ DEVI void sha256_iv(uint32_t h[8]) {
 
 // One SHA-256 compression: h (8 big-endian state words) absorbs the 64-byte block given as 16
 // big-endian words (w is consumed as the message schedule).  Multi-block messages and HMAC
-// (hpke_gpu.h) chain it; fully unrolled, so constant block words fold away.
+// (hpke_kdf256.h) chain it; fully unrolled, so constant block words fold away.
 DEVI void sha256_compress(uint32_t h[8], uint32_t w[16]) {
   const uint32_t iv[8] = {h[0], h[1], h[2], h[3], h[4], h[5], h[6], h[7]};
   uint32_t a = iv[0], b = iv[1], c = iv[2], d = iv[3], e = iv[4], f = iv[5], g = iv[6], hh = iv[7];

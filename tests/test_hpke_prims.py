@@ -1,7 +1,9 @@
 """janus_amd/csrc/hpke_prims.h (no HIP in it): the SHA-384/512, HMAC, RFC 9180 key schedule, ChaCha20
 and Poly1305 that the kernels of hpke_gpu.h run per report for the wider HPKE suites, built with
 g++ and checked on the CPU against hashlib / hmac, a big-integer Poly1305, a pure-Python RFC 9180
-key schedule and messages sealed by the host library.  Every command also runs through a
+key schedule and messages sealed by the host library.  (KDF 1's SHA-256 schedule, hpke_kdf256.h,
+runs on the CPU in tests/test_hpke_lane_prims.py; here its keys come from the Python model, the
+independent reference.)  Every command also runs through a
 -fsanitize=address,undefined build of the stand-alone driver (tests/native/hpke_prims_host.cpp),
 which is its own program and uses every input from a heap block of exactly its length."""
 import ctypes

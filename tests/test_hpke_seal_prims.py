@@ -2,8 +2,9 @@
 hpke_seal_gpu.h run per report for ChaCha20-Poly1305, built with g++ and checked on the CPU against
 RFC 8439's vector, its own open, and messages sealed by the host library under a fixed ephemeral
 key.  For KDF 2 / 3 the key and base nonce come from the header's hpke_kdf512_key_nonce; for KDF 1
-the SHA-256 key schedule is device code (hpke_gpu.h), so its key and nonce come from the
-pure-Python RFC 9180 schedule of tests/hpke_suite_model.py, as in tests/test_hpke_prims.py.
+they come from the pure-Python RFC 9180 schedule of tests/hpke_suite_model.py, as in
+tests/test_hpke_prims.py: an independent reference for the AEAD alone (the SHA-256 key schedule
+of hpke_kdf256.h and the whole seal lane run on the CPU in tests/test_hpke_lane_prims.py).
 Every command also runs through a -fsanitize=address,undefined build of the stand-alone driver
 (tests/native/hpke_seal_host.cpp), which is its own program and uses every input from, and writes
 every output to, a heap block of exactly its length."""

@@ -12,6 +12,14 @@ def test_every_unit_is_built():
     assert units == sorted(SOURCES)
 
 
+def test_per_lane_hpke_headers_are_free_of_hip():
+    """What a lane of the HPKE kernels computes lives in headers a plain C++ compiler builds (the
+    CPU tests run them); the kernels stay in hpke_gpu.h, helper_request.h and hpke_seal_gpu.h."""
+    for name in ("x25519.h", "hpke_kdf256.h", "aes_gcm.h", "hpke_lane.h"):
+        text = (CSRC / name).read_text()
+        assert "hip_runtime" not in text and "__global__" not in text, name
+
+
 def test_hpke_unit_includes_no_prio3_kernel_header():
     """engine_hpke.hip reaches the Prio3 side through the public prio3gpu_helper_init alone; the
     header it shares with engine.hip carries no kernel either."""
