@@ -221,7 +221,11 @@ int prio3gpu_agg_destroy(prio3gpu_agg* agg);
 int prio3gpu_agg_reset(prio3gpu_agg* agg);
 /* Read one slot's aggregate share (aggregate_share bytes) and report count. */
 int prio3gpu_agg_read(prio3gpu_agg* agg, uint32_t slot, uint8_t* out_share, uint64_t* out_count);
-/* Aggregatable::merge: slot += share (aggregate_share bytes, host or device), count += count. */
+/* Aggregatable::merge: slot += share (aggregate_share bytes, host or device), count += count.
+ * Every element of `share` must be canonical (< p), as prio's AggregateShare decoding requires:
+ * the share is checked before anything is launched (a device share through a host copy), and an
+ * element >= p returns PRIO3GPU_E_ARG, prio3gpu_last_error naming its index, with the slot's
+ * share and count unchanged. */
 int prio3gpu_agg_merge_bytes(prio3gpu_agg* agg, uint32_t slot, const uint8_t* share,
                              uint64_t count);
 

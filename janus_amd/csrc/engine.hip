@@ -1285,7 +1285,30 @@ int prio3gpu_agg_merge_bytes(prio3gpu_agg* a, uint32_t slot, const uint8_t* shar
   }
   prio3gpu_ctx* c = a->ctx;
   const size_t nel = c->cfg.out_len;
-  const size_t bytes = nel * c->cfg.es;
+  const uint32_t es = c->cfg.es;
+  const size_t bytes = nel * es;
+  HIPCHK(hipSetDevice(c->device));
+  // prio's AggregateShare decoding refuses an element >= p, and k_merge's FO::add takes
+  // canonical operands: check the caller's bytes (a device share through a host copy) before
+  // anything is launched
+  std::vector<uint8_t> host;
+  const uint8_t* h_src = share;
+  if (is_device_ptr(share)) {
+    host.resize(bytes);
+    HIPCHK(hipMemcpyAsync(host.data(), share, bytes, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    h_src = host.data();
+  }
+  const u128 p = es == 16 ? P128 : P64;
+  for (size_t e = 0; e < nel; ++e) {
+    u128 x = 0;
+    for (uint32_t b = 0; b < es; ++b) x |= (u128)h_src[e * es + b] << (8 * b);
+    if (x >= p) {
+      set_err("agg_merge_bytes: aggregate share element %zu of %zu is out of range (>= p)", e,
+              nel);
+      return PRIO3GPU_E_ARG;
+    }
+  }
   const uint8_t* d_src;
   CHK(stage_in(c, c->io[0], share, bytes, &d_src));
   uint8_t* dst = a->share.u8() + slot * bytes;

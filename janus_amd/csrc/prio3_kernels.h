@@ -23,6 +23,7 @@
 #pragma once
 #include <type_traits>
 
+#include "accum_fold.h"
 #include "cfg.h"
 #include "field.h"
 #include "keccak.h"
@@ -2051,15 +2052,7 @@ __global__ void __launch_bounds__(256) k_accum_spec(Cfg cfg, uint32_t n, CRows m
   const uint64_t blo = __shfl_xor(alo, 1, 64), bhi = __shfl_xor(ahi, 1, 64);
   if (act && (tid & 1u) == 0u) {
     // value = alo + 2^64 (ahi + blo) + 2^128 bhi
-    const u128 P = ((u128)0xFFFFFFFFFFFFFFFFull << 64) - ((u128)27ull << 64) + 1;  // 2^128-28*2^64+1
-    const u128 x1 = (u128)ahi + blo;                  // < 2^65
-    const u128 x2 = (u128)bhi + (uint64_t)(x1 >> 64);  // small
-    const u128 v = ((u128)(uint64_t)x1 << 64) | alo;   // < 2^128
-    const u128 k = (u128)(uint64_t)x2 * 28u;           // 2^128 x2 = x2 (28 2^64 - 1)
-    u128 t = v + (k << 64);
-    if (t < v) t += ((u128)28u << 64) - 1;              // carry out of 2^128
-    t -= (uint64_t)x2;                                  // no underflow: k << 64 >= x2
-    while (t >= P) t -= P;
+    const u128 t = accum_fold::fold128(alo, ahi, blo, bhi);
     uint8_t* dst = partials + ((size_t)ch * cfg.meas_len + e) * 16u;
     st64(dst, (uint64_t)t);
     st64(dst + 8, (uint64_t)(t >> 64));
