@@ -625,6 +625,53 @@ int prio3gpu_seal_input_shares(prio3gpu_ctx* ctx, const uint8_t* task_id, uint16
                                size_t enc_pitch, uint8_t* out_payloads, size_t payload_pitch,
                                uint8_t* status);
 
+/* ---- HPKE open of long ciphertexts on the GPU (janus_amd/csrc/hpke_open_team.h) -----------------
+ * n opens under ONE keypair, one GPU WAVE per report: what the leader does once per upload with an
+ * input share of a hundred kilobytes (aggregator.rs:1325-1497), where a lane per report would walk
+ * each ciphertext alone.  Suites: DHKEM(X25519, HKDF-SHA256) (KEM 0x0020) with KDF 1-3 and
+ * AES-128-GCM / AES-256-GCM (AEAD 1, 2), no context option needed.  KEM 0x0010 (P-256), AEAD 3
+ * (ChaCha20-Poly1305) or an unknown id is PRIO3GPU_E_UNSUPPORTED with nothing launched; n == 0
+ * returns 0 and launches nothing.
+ * prio3gpu_hpke_open_long_batch has the arguments and contracts of prio3gpu_hpke_open_batch --
+ * host or device pointers, status in/out, zero-filled slots, zeros and status 4 for a failed
+ * open, the handling of secrets -- and the same plaintexts, for every ciphertext length from 16
+ * (an empty plaintext) up. */
+int prio3gpu_hpke_open_long_batch(prio3gpu_ctx* ctx, uint16_t kem_id, uint16_t kdf_id,
+                                  uint16_t aead_id, const uint8_t* sk, size_t sk_len,
+                                  const uint8_t* pk, size_t pk_len, const uint8_t* info,
+                                  size_t info_len, size_t n, const uint8_t* encs,
+                                  const uint8_t* aads, const uint64_t* aad_offsets,
+                                  const uint8_t* cts, const uint64_t* ct_offsets, uint8_t* pts,
+                                  const uint64_t* pt_offsets, uint8_t* status);
+/* Upload: open n Prio3 input shares sealed to this aggregator (handle_upload_generic's decrypt and
+ * decode, aggregator.rs:1325-1497), the mirror of prio3gpu_seal_input_shares.  Report i's
+ * encapsulated key (32 bytes) is read from encs + i enc_pitch and its payload, exactly
+ * 6 + input_share_len + 16 bytes, from payloads + i payload_pitch, so both may be columns of one
+ * fixed-stride Report buffer; its AAD is the InputShareAad of task_id, report_ids[16 i ..],
+ * times[i] and public_shares[i public_share_len ..], never written to memory;
+ * info = "dap-07 input share" || Client || recipient_role.  The plaintext must be the
+ * PlaintextInputShare with no extensions -- 00 00, input_share_len as u32 big-endian, the share
+ * -- and the share goes to out_shares + i share_pitch; no other byte of out_shares is written.
+ * out_shares may be device memory at a 128-byte-aligned pitch: after
+ * prio3gpu_state_set_input_pitch, prio3gpu_prepare_init reads the rows in place.  A pitch of 0 is
+ * the packed one (the row's own length); a pitch shorter than its row is PRIO3GPU_E_ARG.
+ * status in/out: non-zero on entry = skipped (the row is zeroed); a failed open (bad tag, an
+ * all-zero DH value) sets 4 and writes zeros; an authentic plaintext with any other six leading
+ * bytes -- extensions, another length: at this payload length either means a share of the wrong
+ * size -- sets 8 (InvalidMessage, "Leader input share decoding failed") and writes zeros.
+ * task_id, sk and pk are host memory; every other pointer may be host or device (detected).
+ * Secrets: the private key reaches the GPU only as a kernel argument; the buffer of the DH values
+ * and the engine's staged copy of the opened rows (host out_shares) are zeroed before the call
+ * returns; keys, nonces and round keys never leave registers. */
+int prio3gpu_open_input_shares(prio3gpu_ctx* ctx, const uint8_t* task_id, uint16_t kem_id,
+                               uint16_t kdf_id, uint16_t aead_id, const uint8_t* sk, size_t sk_len,
+                               const uint8_t* pk, size_t pk_len, uint8_t recipient_role, size_t n,
+                               const uint8_t* report_ids, const uint64_t* times,
+                               const uint8_t* public_shares, uint32_t public_share_len,
+                               const uint8_t* encs, size_t enc_pitch, const uint8_t* payloads,
+                               size_t payload_pitch, uint32_t input_share_len,
+                               uint8_t* out_shares, size_t share_pitch, uint8_t* status);
+
 /* ---- Helper aggregate-init from the request's bytes (janus_amd/csrc/helper_request.h) -----------
  * One call per aggregation job, on one context: the decoded AggregationJobInitializeReq in, prep
  * messages out.  Equivalent, with agg_id = 1, to

@@ -1,0 +1,176 @@
+// AES-GCM opened by a team of lanes (one wave per report in hpke_open_team.h's kernels), for
+// ciphertexts far longer than one lane should walk: the leader's input shares at upload.  CTR is
+// parallel over blocks and GHASH is parallel over blocks through powers of H (NIST SP 800-38D
+// §6.4), so lane l of a team of T takes blocks l, l + T, ... -- a stripe of T consecutive 16-byte
+// blocks is one contiguous load per lane.
+//   gf128_mul                         a product in GF(2^128), GCM bit order, bit-serial
+//   gf128_powers_step                 the table H^1 .. H^T by doubling, log2 T products per lane
+//   gcm_team_power, gcm_team_stripe   one lane's share of GHASH and of the CTR decryption
+//   gcm_team_join                     the GHASH of the whole ciphertext from the lanes' XOR
+//   gcm_team_wipe, team_zero          zeros where a report failed, and in a slot's tail
+//   PackedSink, ShareSink             where the plaintext goes: a packed slot, or a share row with
+//                                     the PlaintextInputShare header checked and dropped
+// Written per lane, with the lane index and the team size as parameters.  What crosses lanes is the
+// caller's: the table lives in memory the team shares (LDS; ordered between steps by the caller),
+// the lanes' accumulators are XORed by the caller, and every lane then computes the same tag.
+// Round keys, H, the AAD's GHASH and the tag mask are aes_gcm.h's aes_gcm_start / aes_gcm_tag,
+// unchanged, computed alike by every lane.  Free of HIP like aes_gcm.h: the kernels and a CPU test
+// (tests/native/aes_gcm_team_host.cpp, 64 lanes in a loop) run the same text.
+// No branch and no global-memory address depends on a key-derived value: the table is indexed by
+// block counts only, and the products are the masked bit-serial form of ghash_step.
+#pragma once
+#include "aes_gcm.h"
+
+namespace p3g {
+
+// out = a * b in GF(2^128), GCM bit order; all as four big-endian words (ghash_step(y, x, h) is
+// gf128_mul(y ^ x, h)).  out may be a or b.
+DEVI void gf128_mul(const uint32_t a[4], const uint32_t b[4], uint32_t out[4]) {
+  uint32_t v0 = b[0], v1 = b[1], v2 = b[2], v3 = b[3];
+  uint32_t z0 = 0, z1 = 0, z2 = 0, z3 = 0;
+#pragma unroll
+  for (int wd = 0; wd < 4; ++wd) {
+    uint32_t xb = a[wd];
+#pragma unroll 4
+    for (int bit = 0; bit < 32; ++bit) {
+      const uint32_t m = 0u - (xb >> 31);
+      xb <<= 1;
+      z0 ^= v0 & m; z1 ^= v1 & m; z2 ^= v2 & m; z3 ^= v3 & m;
+      const uint32_t lsb = 0u - (v3 & 1u);
+      v3 = (v3 >> 1) | (v2 << 31);
+      v2 = (v2 >> 1) | (v1 << 31);
+      v1 = (v1 >> 1) | (v0 << 31);
+      v0 = (v0 >> 1) ^ (lsb & 0xe1000000u);
+    }
+  }
+  out[0] = z0; out[1] = z1; out[2] = z2; out[3] = z3;
+}
+
+// The table of powers, tbl[4 e .. 4 e + 4) = H^(e + 1) for e < team (a power of two): entry 0 is H,
+// and the step `half` = 1, 2, 4, ..., team / 2 fills entries half .. 2 half - 1 from the entries
+// below: lane l in that range sets entry l = entry (l - half) * entry (half - 1).  Every lane
+// multiplies; a step reads entries below `half` only and writes entries from `half` up, and the
+// caller orders each step's writes before the next step's reads.
+DEVI void gf128_powers_step(uint32_t* tbl, uint32_t lane, uint32_t half) {
+  const bool mine = lane >= half && lane < 2 * half;
+  uint32_t p[4];
+  gf128_mul(tbl + 4 * (mine ? lane - half : 0u), tbl + 4 * (half - 1), p);
+  if (mine) {
+#pragma unroll
+    for (int i = 0; i < 4; ++i) tbl[4 * lane + i] = p[i];
+  }
+}
+
+// The power a lane multiplies by once it has absorbed block b of nb: H^team while a later block of
+// its own follows, else H^(nb - b), which carries its sum to the end of the ciphertext.
+DEVI const uint32_t* gcm_team_power(const uint32_t* tbl, uint64_t b, uint64_t nb, uint32_t team) {
+  const uint64_t d = nb - b;
+  return tbl + 4 * ((d > team ? (uint64_t)team : d) - 1);
+}
+
+// 16 bytes at p (any alignment) as block words
+DEVI void load_block16(const uint8_t* p, uint32_t d[4]) { __builtin_memcpy(d, p, 16); }
+
+// One lane's stripe of a ciphertext of clen bytes (nb = ceil(clen / 16) blocks, the last one
+// zero-padded): blocks lane, lane + team, ...  With GHASH, acc (zero on entry) absorbs them as
+// acc = (acc ^ X_b) * power(b); block 0 also takes y0, the GHASH of the AAD, so the XOR of all
+// lanes' acc is the GHASH of pad16(aad) || pad16(ct).  With CTR, block b is XORed with
+// E(K, nonce || b + 2) (ctr is aes_gcm_start's; its last word is not read) and handed to
+// sink.put(b, words, bytes): all sixteen bytes, or the partial last block's.
+template <int NK, bool GHASH, bool CTR, class Sink>
+DEVI void gcm_team_stripe(const uint8_t* sbox, const uint32_t* rk, const uint32_t ctr[4],
+                          const uint32_t* tbl, const uint32_t y0[4], const uint8_t* ct,
+                          uint64_t clen, uint32_t lane, uint32_t team, uint32_t acc[4],
+                          Sink& sink) {
+  const uint64_t nb = (clen + 15) / 16;
+  for (uint64_t b = lane; b < nb; b += team) {
+    const uint64_t o = 16 * b, rem = clen - o;
+    uint32_t d[4];
+    if (rem >= 16) load_block16(ct + o, d);
+    else load_block(ct + o, rem, d);
+    if constexpr (GHASH) {
+      uint32_t x[4];
+#pragma unroll
+      for (int i = 0; i < 4; ++i) x[i] = bswap32(d[i]) ^ acc[i] ^ (b == 0 ? y0[i] : 0u);
+      gf128_mul(x, gcm_team_power(tbl, b, nb, team), acc);
+    }
+    if constexpr (CTR) {
+      const uint32_t c[4] = {ctr[0], ctr[1], ctr[2], bswap32((uint32_t)b + 2u)};
+      uint32_t ek[4];
+      aes_encrypt<NK>(sbox, rk, c, ek);
+#pragma unroll
+      for (int i = 0; i < 4; ++i) d[i] ^= ek[i];
+      sink.put(b, d, rem < 16 ? (uint32_t)rem : 16u);
+    }
+  }
+}
+
+// y = the GHASH so far, given sum = the XOR of every lane's acc: sum itself, or y0 when there was
+// no block to carry it.
+DEVI void gcm_team_join(uint32_t y[4], const uint32_t sum[4], const uint32_t y0[4], uint64_t clen) {
+#pragma unroll
+  for (int i = 0; i < 4; ++i) y[i] = clen ? sum[i] : y0[i];
+}
+
+// Zeros over what the lane's stripe wrote (sink.store with the stripe's own block-to-lane map, so
+// a lane overwrites its own stores).
+template <class Sink>
+DEVI void gcm_team_wipe(Sink& sink, uint64_t clen, uint32_t lane, uint32_t team) {
+  const uint32_t zero[4] = {0, 0, 0, 0};
+  for (uint64_t o = 16 * (uint64_t)lane; o < clen; o += 16 * (uint64_t)team)
+    sink.store(o >> 4, zero, clen - o < 16 ? (uint32_t)(clen - o) : 16u);
+}
+
+// p[0 .. n) = 0, by the whole team: sixteen bytes per lane and round.
+DEVI void team_zero(uint8_t* p, uint64_t n, uint32_t lane, uint32_t team) {
+  const uint32_t zero[4] = {0, 0, 0, 0};
+  for (uint64_t o = 16 * (uint64_t)lane; o < n; o += 16 * (uint64_t)team)
+    store_block(p + o, n - o, zero);
+}
+
+// The plaintext to a packed slot: block b at pt + 16 b.
+struct PackedSink {
+  uint8_t* pt;
+  DEVI void store(uint64_t b, const uint32_t d[4], uint32_t n) { store_block(pt + 16 * b, n, d); }
+  DEVI void put(uint64_t b, const uint32_t d[4], uint32_t n) { store(b, d, n); }
+};
+
+// The plaintext of a PlaintextInputShare to a share row: 00 00 | u32 BE slen | share.  The six
+// header bytes (block 0's first) are compared, never stored, and bad set on the lane that holds
+// them when they differ; plaintext byte p >= 6 goes to row[p - 6].  A block's sixteen bytes start
+// ten bytes into a sixteen-byte piece of the row, so on a row aligned to 16 they leave as
+// naturally aligned pieces of 2, 4, 8 and 2 bytes (block 0: 8 and 2); bytes otherwise.
+struct ShareSink {
+  uint8_t* row;
+  uint32_t slen;
+  uint32_t bad;
+  DEVI void store(uint64_t b, const uint32_t d[4], uint32_t n) {
+    if (n == 16 && ((uintptr_t)row & 15u) == 0) {
+      uint8_t* q = row + 16 * b;  // the row piece that takes bytes 6 .. 15
+      const uint32_t w1 = (d[0] >> 16) | (d[1] << 16);
+      const uint32_t w2[2] = {(d[1] >> 16) | (d[2] << 16), (d[2] >> 16) | (d[3] << 16)};
+      const uint16_t h0 = (uint16_t)d[0], h3 = (uint16_t)(d[3] >> 16);
+      if (b) {
+        __builtin_memcpy(__builtin_assume_aligned(q - 6, 2), &h0, 2);
+        __builtin_memcpy(__builtin_assume_aligned(q - 4, 4), &w1, 4);
+      }
+      __builtin_memcpy(__builtin_assume_aligned(q, 8), w2, 8);
+      __builtin_memcpy(__builtin_assume_aligned(q + 8, 2), &h3, 2);
+      return;
+    }
+#pragma unroll
+    for (uint32_t j = 0; j < 16; ++j) {
+      const uint64_t p = 16 * b + j;
+      if (j < n && p >= 6) row[p - 6] = (uint8_t)(d[j >> 2] >> (8 * (j & 3)));
+    }
+  }
+  DEVI void put(uint64_t b, const uint32_t d[4], uint32_t n) {
+    if (b == 0) {
+      const uint32_t be = bswap32(slen);  // SharePlaintext's header words
+      bad |= (d[0] ^ (be << 16)) | ((d[1] ^ (be >> 16)) & 0xffffu);
+    }
+    store(b, d, n);
+  }
+};
+
+}  // namespace p3g

@@ -1,7 +1,9 @@
 // Host side of the GPU HPKE open and of the helper's aggregate-init from the request's bytes
 // (include/prio3gpu.h: prio3gpu_hpke_open_batch, prio3gpu_hpke_open_report_shares_gpu,
-// prio3gpu_helper_init_request), of the GPU HPKE seal (prio3gpu_hpke_seal_batch,
-// prio3gpu_seal_input_shares) and the test hooks that launch only their kernels.  No Prio3
+// prio3gpu_helper_init_request), of the wave-per-report open of long ciphertexts
+// (prio3gpu_hpke_open_long_batch, prio3gpu_open_input_shares), of the GPU HPKE seal
+// (prio3gpu_hpke_seal_batch, prio3gpu_seal_input_shares) and the test hooks that launch only
+// their kernels.  No Prio3
 // kernel is in scope here: the request path hands over to the Prio3 side (engine.hip) through the
 // public prio3gpu_helper_init alone.
 #include <hip/hip_runtime.h>
@@ -20,6 +22,7 @@
 #include "hpke_gpu.h"
 #include "helper_request.h"
 #include "hpke_seal_gpu.h"
+#include "hpke_open_team.h"
 
 using namespace p3g;
 using namespace p3g::eng;
@@ -186,6 +189,43 @@ void hpke_suite_dispatch(const HpkeBatchConsts& bc, F&& f) {
   else with_aead(std::integral_constant<int, 3>{});
 }
 
+// The suites the wave-per-report open takes (hpke_open_team.h; no option: it has entry points of
+// its own): DHKEM(X25519, HKDF-SHA256) with KDF 1-3 and AES-128-GCM / AES-256-GCM.
+bool hpke_team_suite(uint16_t kem, uint16_t kdf, uint16_t aead) {
+  return kem == 0x0020 && kdf >= 1 && kdf <= 3 && (aead == 1 || aead == 2);
+}
+
+// f(KDF, AEAD) for such a suite.
+template <class F>
+void hpke_team_dispatch(const HpkeBatchConsts& bc, F&& f) {
+  auto with_aead = [&](auto kdf) {
+    if (bc.aead_id == 1) f(kdf, std::integral_constant<int, 1>{});
+    else f(kdf, std::integral_constant<int, 2>{});
+  };
+  if (bc.kdf_id == 1) with_aead(std::integral_constant<int, 1>{});
+  else if (bc.kdf_id == 2) with_aead(std::integral_constant<int, 2>{});
+  else with_aead(std::integral_constant<int, 3>{});
+}
+
+// k_hpke_open_team, instantiated for the suite of bc: k_hpke_open's arguments, a wave per report.
+int launch_hpke_open_team(prio3gpu_ctx* c, const HpkeBatchConsts& bc, size_t n,
+                          const uint32_t* d_dh, const uint8_t* d_enc, const uint8_t* d_aad,
+                          const uint64_t* d_aoff, uint64_t aad_total, const uint8_t* d_ct,
+                          const uint64_t* d_coff, uint64_t ct_total, uint8_t* d_pt,
+                          const uint64_t* d_poff, uint64_t pt_total, uint8_t* d_st) {
+  {
+    PROF(KID_HPKE_OPEN_TEAM);
+    hpke_team_dispatch(bc, [&](auto kdf, auto aead) {
+      hipLaunchKernelGGL((k_hpke_open_team<decltype(kdf)::value, decltype(aead)::value>),
+                         dim3((unsigned)((n + kTeamsPerBlock - 1) / kTeamsPerBlock)), dim3(256), 0,
+                         c->stream, (uint32_t)n, bc, d_dh, d_enc, d_aad, d_aoff, aad_total, d_ct,
+                         d_coff, ct_total, d_pt, d_poff, pt_total, d_st);
+    });
+  }
+  HIPCHK(hipGetLastError());
+  return 0;
+}
+
 // k_hpke_open / k_hpke_open_req, instantiated for the suite of bc.
 int launch_hpke_open(prio3gpu_ctx* c, const HpkeBatchConsts& bc, size_t n, const uint32_t* d_dh,
                      const uint8_t* d_enc, const uint8_t* d_aad, const uint64_t* d_aoff,
@@ -226,7 +266,7 @@ int hpke_open_batch_impl(prio3gpu_ctx* c, uint16_t kem_id, uint16_t kdf_id, uint
                          const uint8_t* pk, const uint8_t* info, size_t info_len, size_t n,
                          const uint8_t* encs, const uint8_t* aads, const uint64_t* aad_offsets,
                          const uint8_t* cts, const uint64_t* ct_offsets, uint8_t* pts,
-                         const uint64_t* pt_offsets, uint8_t* status) {
+                         const uint64_t* pt_offsets, uint8_t* status, bool team = false) {
   HpkeBatchConsts bc;
   if (!hpke_batch_consts(kem_id, kdf_id, aead_id, pk, info, info_len, &bc)) {
     set_err("HPKE primitives unavailable");
@@ -271,10 +311,11 @@ int hpke_open_batch_impl(prio3gpu_ctx* c, uint16_t kem_id, uint16_t kdf_id, uint
   } else {
     rc = launch_x25519(c, sk, n, d_enc, d_dh);
   }
-  if (!rc)
-    rc = launch_hpke_open(c, bc, n, d_dh, d_enc, d_aad, reinterpret_cast<const uint64_t*>(d_aoff),
-                          aad_total, d_ct, reinterpret_cast<const uint64_t*>(d_coff), ct_total,
-                          d_pt, reinterpret_cast<const uint64_t*>(d_poff), pt_total, d_st);
+  if (!rc)  // a lane per report, or (prio3gpu_hpke_open_long_batch) a wave per report
+    rc = (team ? launch_hpke_open_team : launch_hpke_open)(
+        c, bc, n, d_dh, d_enc, d_aad, reinterpret_cast<const uint64_t*>(d_aoff), aad_total, d_ct,
+        reinterpret_cast<const uint64_t*>(d_coff), ct_total, d_pt,
+        reinterpret_cast<const uint64_t*>(d_poff), pt_total, d_st);
   // the per-report secrets: the DH values (keys and nonces never leave registers)
   if (hipMemsetAsync(d_dh, 0, dh_bytes, c->stream) != hipSuccess && !rc) {
     set_err("clearing the DH values failed");
@@ -862,6 +903,145 @@ int prio3gpu_hpke_open_batch(prio3gpu_ctx* c, uint16_t kem_id, uint16_t kdf_id, 
   }
   return hpke_open_batch_impl(c, kem_id, kdf_id, aead_id, sk, pk, info, info_len, n, encs, aads,
                               aad_offsets, cts, ct_offsets, pts, pt_offsets, status);
+}
+
+int prio3gpu_hpke_open_long_batch(prio3gpu_ctx* c, uint16_t kem_id, uint16_t kdf_id,
+                                  uint16_t aead_id, const uint8_t* sk, size_t sk_len,
+                                  const uint8_t* pk, size_t pk_len, const uint8_t* info,
+                                  size_t info_len, size_t n, const uint8_t* encs,
+                                  const uint8_t* aads, const uint64_t* aad_offsets,
+                                  const uint8_t* cts, const uint64_t* ct_offsets, uint8_t* pts,
+                                  const uint64_t* pt_offsets, uint8_t* status) {
+  if (!c) {
+    set_err("null context");
+    return PRIO3GPU_E_ARG;
+  }
+  if (!hpke_team_suite(kem_id, kdf_id, aead_id)) {
+    set_err("HPKE suite 0x%04x/%u/%u is not opened a wave per report", kem_id, kdf_id, aead_id);
+    return PRIO3GPU_E_UNSUPPORTED;
+  }
+  if (!sk || sk_len != 32 || !pk || pk_len != 32 || (info_len && !info)) {
+    set_err("HPKE open: the private key and the public key are 32 bytes");
+    return PRIO3GPU_E_ARG;
+  }
+  if (n == 0) return 0;
+  if (!encs || !aad_offsets || !ct_offsets || !pt_offsets || !status || n > 0x7FFFFFFFu) {
+    set_err("HPKE open: null argument");
+    return PRIO3GPU_E_ARG;
+  }
+  return hpke_open_batch_impl(c, kem_id, kdf_id, aead_id, sk, pk, info, info_len, n, encs, aads,
+                              aad_offsets, cts, ct_offsets, pts, pt_offsets, status,
+                              /*team=*/true);
+}
+
+int prio3gpu_open_input_shares(prio3gpu_ctx* c, const uint8_t* task_id, uint16_t kem_id,
+                               uint16_t kdf_id, uint16_t aead_id, const uint8_t* sk, size_t sk_len,
+                               const uint8_t* pk, size_t pk_len, uint8_t recipient_role, size_t n,
+                               const uint8_t* report_ids, const uint64_t* times,
+                               const uint8_t* public_shares, uint32_t public_share_len,
+                               const uint8_t* encs, size_t enc_pitch, const uint8_t* payloads,
+                               size_t payload_pitch, uint32_t input_share_len,
+                               uint8_t* out_shares, size_t share_pitch, uint8_t* status) {
+  if (!c) {
+    set_err("null context");
+    return PRIO3GPU_E_ARG;
+  }
+  if (!hpke_team_suite(kem_id, kdf_id, aead_id)) {
+    set_err("HPKE suite 0x%04x/%u/%u is not opened a wave per report", kem_id, kdf_id, aead_id);
+    return PRIO3GPU_E_UNSUPPORTED;
+  }
+  if (!sk || sk_len != 32 || !pk || pk_len != 32 || !task_id) {
+    set_err("open_input_shares: the keys and the task id are 32 bytes");
+    return PRIO3GPU_E_ARG;
+  }
+  if (n == 0) return 0;
+  const size_t plen = 6 + (size_t)input_share_len + 16;
+  const size_t epitch = enc_pitch ? enc_pitch : 32;
+  const size_t ppitch = payload_pitch ? payload_pitch : plen;
+  const size_t spitch = share_pitch ? share_pitch : input_share_len;
+  if (!report_ids || !times || (public_share_len && !public_shares) || !encs || !payloads ||
+      (input_share_len && !out_shares) || !status || n > 0x7FFFFFFFu) {
+    set_err("open_input_shares: null argument");
+    return PRIO3GPU_E_ARG;
+  }
+  if (epitch < 32 || ppitch < plen || spitch < input_share_len) {
+    set_err("open_input_shares: a pitch is shorter than its row");
+    return PRIO3GPU_E_ARG;
+  }
+  uint8_t info[20];
+  input_share_info(/*ROLE_CLIENT*/ 1, recipient_role, info);
+  HpkeBatchConsts bc;
+  if (!hpke_batch_consts(kem_id, kdf_id, aead_id, pk, info, sizeof info, &bc)) {
+    set_err("HPKE primitives unavailable");
+    return PRIO3GPU_E_UNSUPPORTED;
+  }
+  ReqTaskId tid;
+  memcpy(tid.w, task_id, 32);  // little-endian host: byte j at bits 8 (j & 3) of word j >> 2
+  HIPCHK(hipSetDevice(c->device));
+  // host rows are staged with their gaps, one span per column; a host output is opened into
+  // packed staging rows (zeroed after the copy: they are input shares), a device one in place
+  const bool out_host = !(out_shares && is_device_ptr(out_shares));
+  const size_t out_bytes = n * (size_t)input_share_len, dh_bytes = n * 32;
+  const uint8_t *d_rid, *d_time, *d_pub, *d_enc, *d_pay, *d_st_in;
+  CHK(stage_in(c, c->seal[4], report_ids, n * 16, &d_rid, kHpkeMinStage));
+  CHK(stage_in(c, c->seal[5], times, n * 8, &d_time, kHpkeMinStage));
+  CHK(stage_in(c, c->seal[6], public_shares, n * (size_t)public_share_len, &d_pub,
+               kHpkeMinStage));
+  CHK(stage_in(c, c->hpke[0], encs, (n - 1) * epitch + 32, &d_enc, kHpkeMinStage));
+  CHK(stage_in(c, c->hpke[3], payloads, (n - 1) * ppitch + plen, &d_pay, kHpkeMinStage));
+  CHK(stage_in(c, c->hpke[7], status, n, &d_st_in, kHpkeMinStage));
+  uint8_t* d_st = const_cast<uint8_t*>(d_st_in);
+  uint8_t* d_out = out_shares;
+  if (out_host) {
+    CHK(c->hpke[5].ensure(std::max<size_t>(out_bytes, kHpkeMinStage)));
+    d_out = c->hpke[5].u8();
+  }
+  CHK(c->hpke[8].ensure(dh_bytes));
+  uint32_t* d_dh = static_cast<uint32_t*>(c->hpke[8].p);
+  // the ladder reads packed encapsulated keys: a pitched column is gathered first
+  const uint8_t* d_enc_packed = d_enc;
+  if (epitch != 32) {
+    CHK(c->seal[7].ensure(n * 32));
+    HIPCHK(hipMemcpy2DAsync(c->seal[7].p, 32, d_enc, epitch, 32, n, hipMemcpyDeviceToDevice,
+                            c->stream));
+    d_enc_packed = c->seal[7].u8();
+  }
+  int rc = launch_x25519(c, sk, n, d_enc_packed, d_dh);
+  if (!rc) {
+    {
+      PROF(KID_HPKE_OPEN_TEAM_SHARES);
+      hpke_team_dispatch(bc, [&](auto kdf, auto aead) {
+        hipLaunchKernelGGL((k_hpke_open_team_shares<decltype(kdf)::value, decltype(aead)::value>),
+                           dim3((unsigned)((n + kTeamsPerBlock - 1) / kTeamsPerBlock)), dim3(256),
+                           0, c->stream, (uint32_t)n, bc, tid, d_dh, d_rid,
+                           reinterpret_cast<const uint64_t*>(d_time), d_pub, public_share_len,
+                           d_enc, (uint64_t)epitch, d_pay, (uint64_t)ppitch, input_share_len,
+                           d_out, (uint64_t)(out_host ? input_share_len : spitch), d_st);
+      });
+    }
+    if (hipGetLastError() != hipSuccess) {
+      set_err("launching k_hpke_open_team_shares failed");
+      rc = PRIO3GPU_E_HIP;
+    }
+  }
+  // the per-report secrets: the DH values (keys, nonces and round keys never leave registers)
+  if (hipMemsetAsync(d_dh, 0, dh_bytes, c->stream) != hipSuccess && !rc) {
+    set_err("clearing the DH values failed");
+    rc = PRIO3GPU_E_HIP;
+  }
+  if (!rc && out_host && out_bytes) {
+    rc = seal_rows_to_host(c, out_shares, spitch, d_out, input_share_len, n);
+    if (hipMemsetAsync(d_out, 0, out_bytes, c->stream) != hipSuccess && !rc) {
+      set_err("clearing the staged input shares failed");
+      rc = PRIO3GPU_E_HIP;
+    }
+  }
+  if (rc) {
+    (void)hipStreamSynchronize(c->stream);
+    return rc;
+  }
+  CHK(copy_out(c, status, d_st, n));
+  return finish_call(c, {report_ids, times, public_shares, encs, payloads, out_shares, status});
 }
 
 int prio3gpu_hpke_open_report_shares_gpu(

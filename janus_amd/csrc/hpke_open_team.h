@@ -1,0 +1,179 @@
+// Batched HPKE open of long ciphertexts on the GPU, one WAVE per report: DHKEM(X25519,
+// HKDF-SHA256) with HKDF-SHA256 / -SHA384 / -SHA512 and AES-128-GCM / AES-256-GCM, RFC 9180 base
+// mode, single shot.  What the leader does once per upload (aggregator.rs:1325-1497) with an input
+// share of a hundred kilobytes, where hpke_gpu.h's lane per report would walk it alone:
+//   k_hpke_open_team<KDF, AEAD>          packed inputs with offsets, as k_hpke_open takes them
+//   k_hpke_open_team_shares<KDF, AEAD>   enc and payload columns in, Prio3 input-share rows out: the
+//                                        InputShareAad is a byte source over the caller's rows and
+//                                        the PlaintextInputShare's header is checked, not stored
+// The DH is hpke_gpu.h's k_x25519, one lane per report, launched before.  Four reports per block;
+// the only block barrier is the one after the S-box build (reports differ in length).  Every lane
+// of a wave derives the same key, nonce, round keys, H and AAD hash (registers only); the lanes
+// then share the ciphertext by stripes (aes_gcm_team.h).  One pass: a block is absorbed by GHASH,
+// decrypted and stored; the lanes' sums are XORed, every lane computes the tag, and on a mismatch
+// each lane overwrites what it stored with zeros -- no unauthenticated plaintext outlives the
+// kernel.  The wave's table of H^1 .. H^64 (LDS, key-derived) is zeroed before the wave ends.
+// Only the kernels and what crosses lanes are here; a lane's arithmetic is aes_gcm_team.h's, free
+// of HIP and run by a CPU test too.  Included by engine_hpke.hip.
+#pragma once
+#include "aes_gcm_team.h"
+#include "cfg.h"
+#include "hpke_lane.h"
+
+namespace p3g {
+
+constexpr uint32_t kTeam = 64;          // lanes per report: one wave
+constexpr uint32_t kTeamsPerBlock = 4;  // reports per 256-thread block
+
+// Orders a wave's LDS writes before its later LDS reads (other lanes' entries of the table).
+__device__ __forceinline__ void team_lds_sync() {
+  __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "workgroup");
+  __builtin_amdgcn_wave_barrier();
+}
+
+// The wave's open of one report after the DH: true when the tag matches and the DH value is not
+// all zero.  The plaintext has then gone through sink (body bytes); otherwise what the sink stored
+// is zeros again.  tbl: 4 kTeam words of LDS of this wave's own, zero when the call returns.
+template <int KDF, int AEAD, class Aad, class Sink>
+__device__ __forceinline__ bool hpke_open_team_wave(const uint8_t* sbox, uint32_t* tbl,
+                                                    const HpkeBatchConsts& bc, const uint32_t* dh,
+                                                    const uint8_t* enc, const Aad& aad,
+                                                    const uint8_t* ct, uint64_t body,
+                                                    uint32_t lane, Sink& sink) {
+  uint32_t dhw[8], encw[8], nz = 0;
+#pragma unroll
+  for (int i = 0; i < 8; ++i) {
+    const uint32_t d = dh[i];
+    nz |= d;
+    dhw[i] = bswap32(d);
+    const uint8_t* e = enc + 4 * i;
+    encw[i] = ((uint32_t)e[0] << 24) | ((uint32_t)e[1] << 16) | ((uint32_t)e[2] << 8) | e[3];
+  }
+  constexpr int NKW = hpke_aead_nk(AEAD) / 4;
+  uint32_t key[NKW], nonce[3], rk[4 * (NKW + 7)], h[4], y0[4], ctr[4], tag[4], t[4];
+  hpke_key_nonce<KDF, AEAD>(bc, dhw, encw, key, nonce);
+  aes_gcm_start<NKW>(sbox, key, nonce, aad, rk, h, y0, ctr);
+  if (lane == 0) {
+#pragma unroll
+    for (int i = 0; i < 4; ++i) tbl[i] = h[i];
+  }
+  for (uint32_t half = 1; half < kTeam; half *= 2) {
+    team_lds_sync();
+    gf128_powers_step(tbl, lane, half);
+  }
+  team_lds_sync();
+  uint32_t acc[4] = {0, 0, 0, 0}, y[4];
+  gcm_team_stripe<NKW, true, true>(sbox, rk, ctr, tbl, y0, ct, body, lane, kTeam, acc, sink);
+#pragma unroll
+  for (int i = 0; i < 4; ++i) {  // the XOR of the 64 sums, on every lane
+#pragma unroll
+    for (int m = 1; m < (int)kTeam; m *= 2) acc[i] ^= (uint32_t)__shfl_xor((int)acc[i], m);
+  }
+  gcm_team_join(y, acc, y0, body);
+  aes_gcm_tag<NKW>(sbox, rk, h, y, ctr, aad.len(), body, t);
+  load_block(ct + body, 16, tag);
+  uint32_t diff = 0;
+#pragma unroll
+  for (int i = 0; i < 4; ++i) diff |= t[i] ^ tag[i];  // no early exit
+  const bool ok = diff == 0u && nz != 0u;
+  if (!ok) gcm_team_wipe(sink, body, lane, kTeam);
+#pragma unroll
+  for (int i = 0; i < 4; ++i) tbl[4 * lane + i] = 0;
+  return ok;
+}
+
+// A wave's place in its block: the block's S-box (built here, with the kernel's only block
+// barrier), the wave's own table of powers, its lane and its report.
+struct TeamWave {
+  const uint8_t* sbox;
+  uint32_t* tbl;
+  uint32_t lane, r;
+};
+
+__device__ __forceinline__ TeamWave team_wave_setup() {
+  __shared__ uint8_t sbox[256];
+  __shared__ uint32_t tbls[kTeamsPerBlock][4 * kTeam];
+  aes_sbox_fill(sbox, threadIdx.x, blockDim.x);
+  __syncthreads();
+  // the wave's index stays a per-lane value: made a scalar, everything a report's lanes derive
+  // alike (the whole key schedule) would be compiled for the scalar unit
+  const uint32_t wave = threadIdx.x / kTeam;
+  return TeamWave{sbox, tbls[wave], threadIdx.x % kTeam, blockIdx.x * kTeamsPerBlock + wave};
+}
+
+// One wave per report over packed inputs, with k_hpke_open's arguments and contracts: report r's
+// plaintext goes to pts[pt_off[r] ..] and zeros up to pt_off[r + 1]; zeros in the whole slot and
+// status 4 for a tag that does not match, an all-zero DH value, a ciphertext shorter than 16 bytes,
+// a slot shorter than the plaintext or offsets that do not fit.  A report whose status is non-zero
+// on entry keeps it and gets zeros.
+template <int KDF, int AEAD>
+__global__ void __launch_bounds__(256) k_hpke_open_team(
+    uint32_t n, HpkeBatchConsts bc, const uint32_t* dh, const uint8_t* encs, const uint8_t* aads,
+    const uint64_t* aad_off, uint64_t aad_total, const uint8_t* cts, const uint64_t* ct_off,
+    uint64_t ct_total, uint8_t* pts, const uint64_t* pt_off, uint64_t pt_total, uint8_t* status) {
+  const TeamWave w = team_wave_setup();
+  const uint32_t r = w.r, lane = w.lane;
+  if (r >= n) return;
+  const uint64_t a0 = aad_off[r], a1 = aad_off[r + 1], c0 = ct_off[r], c1 = ct_off[r + 1];
+  const uint64_t p0 = pt_off[r], p1 = pt_off[r + 1];
+  const bool pt_fits = p0 <= p1 && p1 <= pt_total;
+  const uint64_t pt_cap = pt_fits ? p1 - p0 : 0;
+  uint8_t* pt = pts + (pt_fits ? p0 : 0);
+  const bool skip = status[r] != 0;
+  const bool fits = !skip && pt_fits && a0 <= a1 && a1 <= aad_total && c0 <= c1 &&
+                    c1 <= ct_total && c1 - c0 >= 16 && c1 - c0 - 16 <= pt_cap;
+  if (!fits) {  // nothing to read: skip the work, not just the result
+    team_zero(pt, pt_cap, lane, kTeam);
+    if (!skip && lane == 0) status[r] = ST_HPKE_DECRYPT;
+    return;
+  }
+  const uint64_t body = c1 - c0 - 16;
+  PackedSink sink{pt};
+  const bool ok = hpke_open_team_wave<KDF, AEAD>(w.sbox, w.tbl, bc, dh + (size_t)r * 8,
+                                                 encs + (size_t)r * 32,
+                                                 PackedBytes{aads + a0, a1 - a0}, cts + c0, body,
+                                                 lane, sink);
+  team_zero(pt + body, pt_cap - body, lane, kTeam);
+  if (!ok && lane == 0) status[r] = ST_HPKE_DECRYPT;
+}
+
+// One wave per report over the columns of a batch of uploads to one aggregator: report r's enc is
+// encs[r enc_pitch ..] (32 bytes), its payload payloads[r ppitch ..], exactly 6 + slen + 16 bytes,
+// its AAD the InputShareAad of (tid, rids[16 r ..], times[r], pubs[r pslen ..]), never built in
+// memory.  The plaintext must be 00 00 | u32 BE slen | share: the share goes to
+// out[r spitch .. + slen) and nothing else of out is written.  Zeros in the row and status 4 for
+// a failed open; zeros and status 8 for an authentic plaintext with another header (extensions,
+// or another length: at this ciphertext length either leaves a share of the wrong size).  A report
+// whose status is non-zero on entry keeps it and gets zeros.
+template <int KDF, int AEAD>
+__global__ void __launch_bounds__(256) k_hpke_open_team_shares(
+    uint32_t n, HpkeBatchConsts bc, ReqTaskId tid, const uint32_t* dh, const uint8_t* rids,
+    const uint64_t* times, const uint8_t* pubs, uint32_t pslen, const uint8_t* encs,
+    uint64_t enc_pitch, const uint8_t* payloads, uint64_t ppitch, uint32_t slen, uint8_t* out,
+    uint64_t spitch, uint8_t* status) {
+  const TeamWave w = team_wave_setup();
+  const uint32_t r = w.r, lane = w.lane;
+  if (r >= n) return;
+  uint8_t* row = out + (uint64_t)r * spitch;
+  if (status[r] != 0) {
+    team_zero(row, slen, lane, kTeam);
+    return;
+  }
+  const ReqAad aad{tid, rids + (size_t)r * 16, times[r], pslen, pubs + (size_t)r * pslen};
+  ShareSink sink{row, slen, 0u};
+  const bool ok = hpke_open_team_wave<KDF, AEAD>(w.sbox, w.tbl, bc, dh + (size_t)r * 8,
+                                                 encs + (uint64_t)r * enc_pitch, aad,
+                                                 payloads + (uint64_t)r * ppitch,
+                                                 6 + (uint64_t)slen, lane, sink);
+  if (!ok) {
+    if (lane == 0) status[r] = ST_HPKE_DECRYPT;
+    return;
+  }
+  const uint32_t bad = (uint32_t)__shfl((int)sink.bad, 0);  // block 0 is lane 0's
+  if (bad) {
+    gcm_team_wipe(sink, 6 + (uint64_t)slen, lane, kTeam);
+    if (lane == 0) status[r] = ST_INVALID_MESSAGE;
+  }
+}
+
+}  // namespace p3g

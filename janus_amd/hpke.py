@@ -10,6 +10,9 @@
                                      (aggregator/src/aggregator.rs:1634-1700)
   seal_batch_gpu / seal_input_shares_gpu   the client's per-share seal (client/src/lib.rs:228-251),
                                      batched on the GPU (janus_amd/csrc/hpke_seal_gpu.h)
+  open_long_batch_gpu / open_input_shares_gpu   the leader's open at upload
+                                     (aggregator.rs:1325-1497), a GPU wave per report
+                                     (janus_amd/csrc/hpke_open_team.h)
 
 Errors: `HpkeError` where hpke::open / hpke::seal return `Error::Hpke`, `ValueError` for an
 unsupported suite (`Error::InvalidConfiguration`).
@@ -324,6 +327,91 @@ def seal_input_shares_gpu(gpu, task_id: bytes, config: HpkeConfig, recipient_rol
         "seal input shares (GPU)")
     del k0, k1, k2, k3, k4, k5, k6, k7
     return out_encs, out_payloads, status
+
+
+def open_long_batch_gpu(gpu, keypair: HpkeKeypair, info: bytes, encs, aads, aad_offsets, cts,
+                        ct_offsets, pts=None, pt_offsets=None, status=None,
+                        n: Optional[int] = None):
+    """`open_batch_gpu` with one GPU wave per report instead of one lane
+    (prio3gpu_hpke_open_long_batch): for ciphertexts of many kilobytes, the leader's input shares
+    at upload.  DHKEM(X25519, HKDF-SHA256) with any KDF and AES-128-GCM / AES-256-GCM, no option
+    needed; `ValueError` for any other suite (P-256, ChaCha20-Poly1305), nothing launched.  Same
+    arguments, plaintexts and statuses; buffers are numpy arrays (host), torch tensors (host or
+    device) or integer device pointers (then `n`, `pts`, `pt_offsets` and `status` must be given).
+    -> (plaintexts, pt_offsets, status); a failed open has status 4 and zeros."""
+    c = keypair.config
+    if n is None:
+        n = len(np.asarray(ct_offsets)) - 1
+    if pt_offsets is None:
+        lens = np.diff(np.asarray(ct_offsets, np.uint64).astype(np.int64)) - 16
+        pt_offsets = np.concatenate([[0], np.cumsum(np.maximum(lens, 0))]).astype(np.uint64)
+    if pts is None:
+        pts = np.zeros(max(1, int(np.asarray(pt_offsets)[-1])), np.uint8)
+    if status is None:
+        status = np.zeros(max(1, n), np.uint8)
+    keep, args = [], []
+    for x, dt in ((encs, np.uint8), (aads, np.uint8), (aad_offsets, np.uint64), (cts, np.uint8),
+                  (ct_offsets, np.uint64), (pts, np.uint8), (pt_offsets, np.uint64),
+                  (status, np.uint8)):
+        p, k = _dev_ptr(x, dt)
+        args.append(p)
+        keep.append(k)
+    for out, k in ((pts, keep[5]), (status, keep[7])):  # outputs must be written in place
+        assert k is None or k is out, "pts / status must be contiguous uint8 arrays"
+    _rc(lib().prio3gpu_hpke_open_long_batch(_ctx_handle(gpu), c.kem_id, c.kdf_id, c.aead_id,
+                                            _buf(keypair.private_key), len(keypair.private_key),
+                                            _buf(c.public_key), len(c.public_key), _buf(info),
+                                            len(info), n, *args), "HPKE GPU open (long)")
+    del keep
+    return pts, pt_offsets, status
+
+
+def open_input_shares_gpu(gpu, task_id: bytes, keypair: HpkeKeypair, recipient_role: int,
+                          report_ids, times, public_shares, encs, payloads, out_shares=None,
+                          status=None):
+    """Open n Prio3 input shares sealed to one aggregator on the GPU, a wave per report
+    (prio3gpu_open_input_shares), the mirror of `seal_input_shares_gpu`: report i's share is the
+    payload of `open_(keypair, application_info(INPUT_SHARE, CLIENT, recipient_role), encs[i],
+    payloads[i], input_share_aad(task_id, report_ids[i], times[i], public_shares[i]))`, which
+    must be the PlaintextInputShare with no extensions -- neither frame is built in memory.
+
+    report_ids (n, 16), public_shares (n, public_share_len) or None: uint8 numpy arrays or torch
+    tensors, packed; times (n,) uint64; encs (n, 32) and payloads (n, 6 + len + 16) uint8 whose
+    rows may be column slices of a wider buffer (host or device; e.g. the columns of a
+    fixed-stride Report matrix), like out_shares (n, len): only those columns are written (a numpy
+    array by default).  -> (out_shares, status); status 4 and a zero row for a failed open, 8 and
+    a zero row for an authentic plaintext that is not an extension-free share of this length.
+    Suites as `open_long_batch_gpu`; `ValueError` otherwise."""
+    tid = np.frombuffer(bytes(task_id), np.uint8).copy()
+    if tid.size != 32:
+        raise ValueError("TaskId is 32 bytes")
+    c = keypair.config
+    n, plen = int(payloads.shape[0]), int(payloads.shape[1])
+    slen = plen - 6 - 16
+    if slen < 0:
+        raise ValueError("a payload holds at least the 6-byte header and the 16-byte tag")
+    if out_shares is None:
+        out_shares = np.zeros((n, slen), np.uint8)
+    if status is None:
+        status = np.zeros(max(1, n), np.uint8)
+    pslen = 0 if public_shares is None else int(public_shares.shape[1])
+    p_enc, enc_pitch, k0 = _rows(encs, n, 32, "encs")
+    p_pay, pay_pitch, k1 = _rows(payloads, n, plen, "payloads")
+    p_out, out_pitch, k2 = _rows(out_shares, n, slen, "out_shares")
+    assert k2 is out_shares or k2 is None
+    p_rid, k3 = _dev_ptr(report_ids, np.uint8)
+    p_tm, k4 = _dev_ptr(times, np.uint64)
+    p_pub, k5 = _dev_ptr(public_shares, np.uint8) if pslen else (None, None)
+    p_st, k6 = _dev_ptr(status, np.uint8)
+    assert k6 is None or k6 is status, "status must be a contiguous uint8 array"
+    _rc(lib().prio3gpu_open_input_shares(_ctx_handle(gpu), tid.ctypes.data, c.kem_id, c.kdf_id,
+                                         c.aead_id, _buf(keypair.private_key),
+                                         len(keypair.private_key), _buf(c.public_key),
+                                         len(c.public_key), recipient_role, n, p_rid, p_tm, p_pub,
+                                         pslen, p_enc, enc_pitch, p_pay, pay_pitch, slen, p_out,
+                                         out_pitch, p_st), "open input shares (GPU)")
+    del k0, k1, k2, k3, k4, k5, k6
+    return out_shares, status
 
 
 def open_report_shares(task_id: bytes, req, task_keys: Sequence[HpkeKeypair],

@@ -327,6 +327,24 @@ extern "C" {
                                       out_payloads: *mut u8, payload_pitch: usize,
                                       status: *mut u8) -> c_int;
 
+    // -- HPKE open of long ciphertexts on the GPU (X25519 x AES-GCM; one wave per report) -------
+    pub fn prio3gpu_hpke_open_long_batch(ctx: *mut prio3gpu_ctx, kem_id: u16, kdf_id: u16,
+                                         aead_id: u16, sk: *const u8, sk_len: usize,
+                                         pk: *const u8, pk_len: usize, info: *const u8,
+                                         info_len: usize, n: usize, encs: *const u8,
+                                         aads: *const u8, aad_offsets: *const u64,
+                                         cts: *const u8, ct_offsets: *const u64, pts: *mut u8,
+                                         pt_offsets: *const u64, status: *mut u8) -> c_int;
+    pub fn prio3gpu_open_input_shares(ctx: *mut prio3gpu_ctx, task_id: *const u8, kem_id: u16,
+                                      kdf_id: u16, aead_id: u16, sk: *const u8, sk_len: usize,
+                                      pk: *const u8, pk_len: usize, recipient_role: u8, n: usize,
+                                      report_ids: *const u8, times: *const u64,
+                                      public_shares: *const u8, public_share_len: u32,
+                                      encs: *const u8, enc_pitch: usize, payloads: *const u8,
+                                      payload_pitch: usize, input_share_len: u32,
+                                      out_shares: *mut u8, share_pitch: usize,
+                                      status: *mut u8) -> c_int;
+
     // -- helper aggregate-init from the request's bytes (one call per job, one context) ---------
     pub fn prio3gpu_helper_init_request(ctx: *mut prio3gpu_ctx, st: *mut prio3gpu_state,
                                         task_id: *const u8,
