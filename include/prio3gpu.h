@@ -672,6 +672,41 @@ int prio3gpu_open_input_shares(prio3gpu_ctx* ctx, const uint8_t* task_id, uint16
                                size_t payload_pitch, uint32_t input_share_len,
                                uint8_t* out_shares, size_t share_pitch, uint8_t* status);
 
+/* ---- HPKE seal of long plaintexts on the GPU (janus_amd/csrc/hpke_seal_team.h) ------------------
+ * n seals to ONE recipient key, one GPU WAVE per report, each under its own ephemeral key: what a
+ * client does with the leader's input share of a hundred kilobytes, where a lane per report would
+ * walk each plaintext alone; the mirror of prio3gpu_hpke_open_long_batch.  Suites:
+ * DHKEM(X25519, HKDF-SHA256) (KEM 0x0020) with KDF 1-3 and AES-128-GCM / AES-256-GCM (AEAD 1, 2),
+ * no context option needed.  KEM 0x0010 (P-256), AEAD 3 (ChaCha20-Poly1305: it stays on
+ * prio3gpu_hpke_seal_batch) or an unknown id is PRIO3GPU_E_UNSUPPORTED with nothing launched;
+ * n == 0 returns 0 and launches nothing.
+ * prio3gpu_hpke_seal_long_batch has the arguments and contracts of prio3gpu_hpke_seal_batch --
+ * host or device pointers, status in/out, zero-filled slots, zeros and status 4 for a report that
+ * is not sealed, the handling of secrets (round keys too never leave registers; the wave's table
+ * of powers of H in LDS is zeroed before the wave ends) -- and the same bytes, for every plaintext
+ * length from 0 up and a ciphertext slot at any alignment. */
+int prio3gpu_hpke_seal_long_batch(prio3gpu_ctx* ctx, uint16_t kem_id, uint16_t kdf_id,
+                                  uint16_t aead_id, const uint8_t* pk, size_t pk_len,
+                                  const uint8_t* info, size_t info_len, size_t n,
+                                  const uint8_t* sk_es, const uint8_t* aads,
+                                  const uint64_t* aad_offsets, const uint8_t* pts,
+                                  const uint64_t* pt_offsets, uint8_t* encs, uint8_t* cts,
+                                  const uint64_t* ct_offsets, uint8_t* status);
+/* Client: prio3gpu_seal_input_shares with a wave per report, for the suites above: the same
+ * arguments, pitches (0 = packed; shorter than the row = PRIO3GPU_E_ARG), statuses, handling of
+ * secrets and bytes.  The enc and payload columns may sit at any alignment (a whole 16-byte block
+ * leaves as the widest naturally aligned pieces its address allows); no byte outside the two
+ * columns is written. */
+int prio3gpu_seal_input_shares_long(prio3gpu_ctx* ctx, const uint8_t* task_id, uint16_t kem_id,
+                                    uint16_t kdf_id, uint16_t aead_id, const uint8_t* pk,
+                                    size_t pk_len, uint8_t recipient_role, size_t n,
+                                    const uint8_t* report_ids, const uint64_t* times,
+                                    const uint8_t* public_shares, uint32_t public_share_len,
+                                    const uint8_t* input_shares, uint32_t input_share_len,
+                                    size_t input_share_pitch, const uint8_t* sk_es,
+                                    uint8_t* out_encs, size_t enc_pitch, uint8_t* out_payloads,
+                                    size_t payload_pitch, uint8_t* status);
+
 /* ---- Helper aggregate-init from the request's bytes (janus_amd/csrc/helper_request.h) -----------
  * One call per aggregation job, on one context: the decoded AggregationJobInitializeReq in, prep
  * messages out.  Equivalent, with agg_id = 1, to

@@ -219,6 +219,15 @@ def _declare(lib):
                                                  c.c_size_t, u8p, P, u8p, c.c_uint32, u8p,
                                                  c.c_size_t, u8p, c.c_size_t, c.c_uint32, u8p,
                                                  c.c_size_t, u8p]),
+        # HPKE seal of long plaintexts on the GPU, a wave per report (hpke_seal_team.h)
+        "prio3gpu_hpke_seal_long_batch": (c.c_int, [P, c.c_uint16, c.c_uint16, c.c_uint16, u8p,
+                                                    c.c_size_t, u8p, c.c_size_t, c.c_size_t, u8p,
+                                                    u8p, P, u8p, P, u8p, u8p, P, u8p]),
+        "prio3gpu_seal_input_shares_long": (c.c_int, [P, u8p, c.c_uint16, c.c_uint16, c.c_uint16,
+                                                      u8p, c.c_size_t, c.c_uint8, c.c_size_t, u8p,
+                                                      P, u8p, c.c_uint32, u8p, c.c_uint32,
+                                                      c.c_size_t, u8p, u8p, c.c_size_t, u8p,
+                                                      c.c_size_t, u8p]),
         # helper aggregate-init from the request's bytes (helper_request.h)
         "prio3gpu_helper_init_request": (c.c_int, [P, P, u8p, P, c.c_size_t, P, c.c_size_t,
                                                    c.c_uint8, c.c_uint8, u8p, c.c_size_t, P,
@@ -263,6 +272,7 @@ EXPORTED = [
     "prio3gpu_hpke_open_batch", "prio3gpu_hpke_open_report_shares_gpu",
     "prio3gpu_helper_init_request", "prio3gpu_hpke_seal_batch", "prio3gpu_seal_input_shares",
     "prio3gpu_hpke_open_long_batch", "prio3gpu_open_input_shares",
+    "prio3gpu_hpke_seal_long_batch", "prio3gpu_seal_input_shares_long",
 ]
 # The test / benchmark hooks of include/prio3gpu_test.h (same library, not part of the product ABI).
 TEST_EXPORTED = [

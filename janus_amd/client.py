@@ -3,7 +3,8 @@
 Mirrors `Client::prepare_report` of Janus's client/src/lib.rs:212-258 for a whole batch: shard
 (prio3gpu_shard), wrap each input share in a `PlaintextInputShare`, `hpke::seal` it to its
 aggregator under the `InputShareAad` (prio3gpu_seal_input_shares: both frames are read lane by
-lane from the share rows and never built), and encode a `Report`.  Every report of one
+lane from the share rows and never built; for long AES-GCM shares
+prio3gpu_seal_input_shares_long, a wave per report), and encode a `Report`.  Every report of one
 `ClientBatch` has the same length, so a batch is an (n, report_len) uint8 matrix whose columns
 are the fields of messages/src/lib.rs's `Report`:
 
@@ -162,10 +163,23 @@ def round_times(times, time_precision: int) -> np.ndarray:
 
 class ClientBatch:
     """The batched `Client` of one task: `vdaf` a `Prio3Gpu`, the two aggregators' `HpkeConfig`s
-    (DHKEM(X25519, HKDF-SHA256) with any KDF and AEAD) and the task's time precision in seconds."""
+    (DHKEM(X25519, HKDF-SHA256) with any KDF and AEAD) and the task's time precision in seconds.
+
+    `long_seal` picks the seal's kernels per aggregator; the report bytes never depend on it.
+    False: a GPU lane per report (`hpke.seal_input_shares_gpu`).  True: a wave per report
+    (`hpke.seal_input_shares_long_gpu`) for both aggregators; `ValueError` here unless both AEADs
+    are AES-GCM.  None: the wave per report where the AEAD is AES-GCM and the input share has at
+    least `LONG_SEAL_MIN_SHARE` bytes, else the lane."""
+
+    # The shortest input share from which the wave-per-report seal is measured to win at every
+    # longer length too: the Sum32 leader share, 1.7x at 4,096 reports; at 1,024 bytes the lane per
+    # report is still ahead (DESIGN.md §8b "Seal at the client, a wave per report").  None would
+    # keep the lane per report everywhere under long_seal=None.
+    LONG_SEAL_MIN_SHARE: Optional[int] = 2576
 
     def __init__(self, vdaf, task_id: bytes, leader_config: H.HpkeConfig,
-                 helper_config: H.HpkeConfig, time_precision: int):
+                 helper_config: H.HpkeConfig, time_precision: int,
+                 long_seal: Optional[bool] = None):
         if len(task_id) != 32:
             raise ValueError("TaskId is 32 bytes")
         if time_precision <= 0:
@@ -173,10 +187,20 @@ class ClientBatch:
         for c in (leader_config, helper_config):
             if c.kem_id != H.KEM_X25519_HKDF_SHA256:
                 raise ValueError("the GPU seals to DHKEM(X25519, HKDF-SHA256) configs only")
+        gcm = [c.aead_id in (H.AEAD_AES128GCM, H.AEAD_AES256GCM)
+               for c in (leader_config, helper_config)]
+        if long_seal and not all(gcm):
+            raise ValueError("long_seal=True needs AES-128-GCM or AES-256-GCM configs")
+        s = vdaf.sizes
+        floor = self.LONG_SEAL_MIN_SHARE
+        # (leader, helper): whether a wave per report seals that aggregator's shares
+        self._wave = tuple(
+            bool(long_seal) if long_seal is not None else
+            (g and floor is not None and share >= floor)
+            for g, share in zip(gcm, (s.leader_input_share, s.helper_input_share)))
         self.vdaf, self.task_id = vdaf, bytes(task_id)
         self.leader_config, self.helper_config = leader_config, helper_config
         self.time_precision = int(time_precision)
-        s = vdaf.sizes
         self.layout = ReportLayout(s.public_share, s.leader_input_share, s.helper_input_share)
         self.report_len = self.layout.report_len
         self._state = None
@@ -236,8 +260,9 @@ class ClientBatch:
         for which, cfg, role, shares, k in (("leader", self.leader_config, H.ROLE_LEADER, d_lin, 0),
                                             ("helper", self.helper_config, H.ROLE_HELPER, d_hin, 1)):
             encs, payloads = L.columns(reports, which)
-            _, _, st = H.seal_input_shares_gpu(v, self.task_id, cfg, role, d_ids, d_tm, d_pub,
-                                               shares, d_sk[k], encs, payloads)
+            seal = H.seal_input_shares_long_gpu if self._wave[k] else H.seal_input_shares_gpu
+            _, _, st = seal(v, self.task_id, cfg, role, d_ids, d_tm, d_pub, shares, d_sk[k], encs,
+                            payloads)
             if st[:n].any():
                 raise H.HpkeError(f"sealing to the {which} failed for {int((st[:n] != 0).sum())} "
                                   "reports (a public key of small order)")

@@ -10,6 +10,9 @@
 //   gcm_team_wipe, team_zero          zeros where a report failed, and in a slot's tail
 //   PackedSink, ShareSink             where the plaintext goes: a packed slot, or a share row with
 //                                     the PlaintextInputShare header checked and dropped
+//   gcm_team_seal_stripe              the seal's stripe (hpke_seal_team.h's kernels): a plaintext
+//                                     source encrypted, stored and then absorbed by GHASH
+//   store_block_any, CtSink           where the ciphertext goes: a slot at any alignment
 // Written per lane, with the lane index and the team size as parameters.  What crosses lanes is the
 // caller's: the table lives in memory the team shares (LDS; ordered between steps by the caller),
 // the lanes' accumulators are XORed by the caller, and every lane then computes the same tag.
@@ -105,6 +108,44 @@ DEVI void gcm_team_stripe(const uint8_t* sbox, const uint32_t* rk, const uint32_
   }
 }
 
+// The sixteen bytes at offset o of a byte source, all of which exist: the source's own whole-block
+// form where it has one (whole(o, d): one 16-byte load), else block(o, d).
+template <class Src>
+DEVI auto src_whole_block(const Src& s, uint64_t o, uint32_t d[4], int) -> decltype(s.whole(o, d)) {
+  s.whole(o, d);
+}
+template <class Src>
+DEVI void src_whole_block(const Src& s, uint64_t o, uint32_t d[4], long) {
+  s.block(o, d);
+}
+
+// The seal's mirror of gcm_team_stripe: one lane's stripe of a plaintext, a byte source (len(),
+// block(o, d)) of nb = ceil(len / 16) blocks.  Block b = lane, lane + team, ... is XORed with
+// E(K, nonce || b + 2), zeroed past the end of a partial last block, handed to
+// sink.put(b, words, bytes) and then absorbed: acc = (acc ^ C_b [^ y0 when b == 0]) * power(b), so
+// the XOR of all lanes' acc (zero on entry) is the GHASH of pad16(aad) || pad16(ciphertext).
+template <int NK, class Src, class Sink>
+DEVI void gcm_team_seal_stripe(const uint8_t* sbox, const uint32_t* rk, const uint32_t ctr[4],
+                               const uint32_t* tbl, const uint32_t y0[4], const Src& pt,
+                               uint32_t lane, uint32_t team, uint32_t acc[4], Sink& sink) {
+  const uint64_t plen = pt.len(), nb = (plen + 15) / 16;
+  for (uint64_t b = lane; b < nb; b += team) {
+    const uint64_t o = 16 * b, rem = plen - o;
+    uint32_t d[4], ek[4], x[4];
+    if (rem >= 16) src_whole_block(pt, o, d, 0);
+    else pt.block(o, d);
+    const uint32_t c[4] = {ctr[0], ctr[1], ctr[2], bswap32((uint32_t)b + 2u)};
+    aes_encrypt<NK>(sbox, rk, c, ek);
+#pragma unroll
+    for (int i = 0; i < 4; ++i) d[i] ^= ek[i];
+    mask_block(d, rem);
+    sink.put(b, d, rem < 16 ? (uint32_t)rem : 16u);
+#pragma unroll
+    for (int i = 0; i < 4; ++i) x[i] = bswap32(d[i]) ^ acc[i] ^ (b == 0 ? y0[i] : 0u);
+    gf128_mul(x, gcm_team_power(tbl, b, nb, team), acc);
+  }
+}
+
 // y = the GHASH so far, given sum = the XOR of every lane's acc: sum itself, or y0 when there was
 // no block to carry it.
 DEVI void gcm_team_join(uint32_t y[4], const uint32_t sum[4], const uint32_t y0[4], uint64_t clen) {
@@ -170,6 +211,80 @@ struct ShareSink {
       bad |= (d[0] ^ (be << 16)) | ((d[1] ^ (be >> 16)) & 0xffffu);
     }
     store(b, d, n);
+  }
+};
+
+// The eight bytes from byte p (< 16) of a block on, as a little-endian value (zeros past byte 15).
+DEVI uint64_t block_bytes_from(const uint32_t d[4], uint32_t p) {
+  const uint64_t lo = d[0] | ((uint64_t)d[1] << 32), hi = d[2] | ((uint64_t)d[3] << 32);
+  const uint32_t s = 8 * (p & 7u);
+  const uint64_t mid = (lo >> s) | (s ? hi << (64 - s) : 0);  // p < 8
+  return p < 8 ? mid : hi >> s;
+}
+
+// A block's sixteen bytes to a (any alignment) as the widest naturally aligned pieces the address
+// allows: one 16-byte store on a 16-byte boundary; otherwise 1, 2, 4 and 8 bytes, those that
+// 16 - (a mod 16) is made of, which end on the boundary, then from the boundary on 8, 4, 2 and 1
+// bytes, those that a mod 16 is made of -- five stores at the most.
+DEVI void store_block_any(uint8_t* a, const uint32_t d[4]) {
+  const uint32_t k = (uint32_t)((uintptr_t)a & 15u);
+  if (k == 0) {
+    __builtin_memcpy(__builtin_assume_aligned(a, 16), d, 16);
+    return;
+  }
+  uint32_t p = 0;
+  if (k & 1u) {
+    a[0] = (uint8_t)d[0];
+    p = 1;
+  }
+  if ((k + p) & 2u) {
+    const uint16_t v = (uint16_t)block_bytes_from(d, p);
+    __builtin_memcpy(__builtin_assume_aligned(a + p, 2), &v, 2);
+    p += 2;
+  }
+  if ((k + p) & 4u) {
+    const uint32_t v = (uint32_t)block_bytes_from(d, p);
+    __builtin_memcpy(__builtin_assume_aligned(a + p, 4), &v, 4);
+    p += 4;
+  }
+  if ((k + p) & 8u) {
+    const uint64_t v = block_bytes_from(d, p);
+    __builtin_memcpy(__builtin_assume_aligned(a + p, 8), &v, 8);
+    p += 8;
+  }
+  // a + p is the boundary and p = 16 - k: k bytes are left
+  if (k & 8u) {
+    const uint64_t v = block_bytes_from(d, p);
+    __builtin_memcpy(__builtin_assume_aligned(a + p, 8), &v, 8);
+    p += 8;
+  }
+  if (k & 4u) {
+    const uint32_t v = (uint32_t)block_bytes_from(d, p);
+    __builtin_memcpy(__builtin_assume_aligned(a + p, 4), &v, 4);
+    p += 4;
+  }
+  if (k & 2u) {
+    const uint16_t v = (uint16_t)block_bytes_from(d, p);
+    __builtin_memcpy(__builtin_assume_aligned(a + p, 2), &v, 2);
+    p += 2;
+  }
+  if (k & 1u) a[15] = (uint8_t)(d[3] >> 24);
+}
+
+// The ciphertext to a slot at any alignment (a packed slot at a byte offset, the payload column of
+// a report matrix): block b at ct + 16 b, a whole block as store_block_any's pieces, the partial
+// last block bytewise.  Only ct[16 b .. 16 b + n) is written.
+struct CtSink {
+  uint8_t* ct;
+  DEVI void put(uint64_t b, const uint32_t d[4], uint32_t n) {
+    uint8_t* a = ct + 16 * b;
+    if (n == 16) {
+      store_block_any(a, d);
+      return;
+    }
+#pragma unroll
+    for (uint32_t j = 0; j < 16; ++j)
+      if (j < n) a[j] = (uint8_t)(d[j >> 2] >> (8 * (j & 3)));
   }
 };
 

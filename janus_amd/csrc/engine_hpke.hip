@@ -2,8 +2,9 @@
 // (include/prio3gpu.h: prio3gpu_hpke_open_batch, prio3gpu_hpke_open_report_shares_gpu,
 // prio3gpu_helper_init_request), of the wave-per-report open of long ciphertexts
 // (prio3gpu_hpke_open_long_batch, prio3gpu_open_input_shares), of the GPU HPKE seal
-// (prio3gpu_hpke_seal_batch, prio3gpu_seal_input_shares) and the test hooks that launch only
-// their kernels.  No Prio3
+// (prio3gpu_hpke_seal_batch, prio3gpu_seal_input_shares), of its wave-per-report form for long
+// plaintexts (prio3gpu_hpke_seal_long_batch, prio3gpu_seal_input_shares_long) and the test hooks
+// that launch only their kernels.  No Prio3
 // kernel is in scope here: the request path hands over to the Prio3 side (engine.hip) through the
 // public prio3gpu_helper_init alone.
 #include <hip/hip_runtime.h>
@@ -23,6 +24,7 @@
 #include "helper_request.h"
 #include "hpke_seal_gpu.h"
 #include "hpke_open_team.h"
+#include "hpke_seal_team.h"
 
 using namespace p3g;
 using namespace p3g::eng;
@@ -685,7 +687,7 @@ int hpke_seal_batch_impl(prio3gpu_ctx* c, uint16_t kem_id, uint16_t kdf_id, uint
                          const uint8_t* pk, const uint8_t* info, size_t info_len, size_t n,
                          const uint8_t* sk_es, const uint8_t* aads, const uint64_t* aad_offsets,
                          const uint8_t* pts, const uint64_t* pt_offsets, uint8_t* encs,
-                         uint8_t* cts, const uint64_t* ct_offsets, uint8_t* status) {
+                         uint8_t* cts, const uint64_t* ct_offsets, uint8_t* status, bool team) {
   HpkeBatchConsts bc;
   if (!hpke_batch_consts(kem_id, kdf_id, aead_id, pk, info, info_len, &bc)) {
     set_err("HPKE primitives unavailable");
@@ -716,14 +718,23 @@ int hpke_seal_batch_impl(prio3gpu_ctx* c, uint16_t kem_id, uint16_t kdf_id, uint
     s.pt_bytes = pt_total;
     CHK(stage_in(c, c->seal[2], pts, pt_total, &s.d_pt, kHpkeMinStage));
     CHK(seal_ladders(c, pk, n, sk_es, &s));
-    {
+    // a lane per report, or (prio3gpu_hpke_seal_long_batch) a wave per report
+    auto launch = [&](auto kernel, size_t per_block) {
+      hipLaunchKernelGGL(kernel, dim3((unsigned)((n + per_block - 1) / per_block)), dim3(256), 0,
+                         c->stream, (uint32_t)n, bc, s.d_eph, d_aad,
+                         reinterpret_cast<const uint64_t*>(d_aoff), aad_total, s.d_pt,
+                         reinterpret_cast<const uint64_t*>(d_poff), pt_total, d_enc, d_ct,
+                         reinterpret_cast<const uint64_t*>(d_coff), ct_total, d_st);
+    };
+    if (team) {
+      PROF(KID_HPKE_SEAL_TEAM);
+      hpke_team_dispatch(bc, [&](auto kdf, auto aead) {
+        launch(k_hpke_seal_team<decltype(kdf)::value, decltype(aead)::value>, kTeamsPerBlock);
+      });
+    } else {
       PROF(KID_HPKE_SEAL);
       hpke_suite_dispatch(bc, [&](auto kdf, auto aead) {
-        hipLaunchKernelGGL((k_hpke_seal<decltype(kdf)::value, decltype(aead)::value>),
-                           dim3((unsigned)((n + 255) / 256)), dim3(256), 0, c->stream, (uint32_t)n,
-                           bc, s.d_eph, d_aad, reinterpret_cast<const uint64_t*>(d_aoff),
-                           aad_total, s.d_pt, reinterpret_cast<const uint64_t*>(d_poff), pt_total,
-                           d_enc, d_ct, reinterpret_cast<const uint64_t*>(d_coff), ct_total, d_st);
+        launch(k_hpke_seal<decltype(kdf)::value, decltype(aead)::value>, 256);
       });
     }
     HIPCHK(hipGetLastError());
@@ -753,24 +764,28 @@ int seal_rows_to_host(prio3gpu_ctx* c, uint8_t* dst, size_t pitch, const uint8_t
   return 0;
 }
 
-}  // namespace
+// The suite check of a seal entry point: a lane per report (hpke_seal_gpu.h), or with `team` a wave
+// per report (hpke_seal_team.h: the suites of the wave-per-report open).
+int seal_suite_check(uint16_t kem_id, uint16_t kdf_id, uint16_t aead_id, bool team) {
+  if (team ? hpke_team_suite(kem_id, kdf_id, aead_id) : hpke_seal_suite(kem_id, kdf_id, aead_id))
+    return 0;
+  set_err("HPKE suite 0x%04x/%u/%u is not sealed %s", kem_id, kdf_id, aead_id,
+          team ? "a wave per report" : "on the GPU");
+  return PRIO3GPU_E_UNSUPPORTED;
+}
 
-extern "C" {
-
-int prio3gpu_hpke_seal_batch(prio3gpu_ctx* c, uint16_t kem_id, uint16_t kdf_id, uint16_t aead_id,
-                             const uint8_t* pk, size_t pk_len, const uint8_t* info,
-                             size_t info_len, size_t n, const uint8_t* sk_es, const uint8_t* aads,
-                             const uint64_t* aad_offsets, const uint8_t* pts,
-                             const uint64_t* pt_offsets, uint8_t* encs, uint8_t* cts,
-                             const uint64_t* ct_offsets, uint8_t* status) {
+// prio3gpu_hpke_seal_batch and, with `team`, prio3gpu_hpke_seal_long_batch.
+int hpke_seal_batch_entry(prio3gpu_ctx* c, uint16_t kem_id, uint16_t kdf_id, uint16_t aead_id,
+                          const uint8_t* pk, size_t pk_len, const uint8_t* info, size_t info_len,
+                          size_t n, const uint8_t* sk_es, const uint8_t* aads,
+                          const uint64_t* aad_offsets, const uint8_t* pts,
+                          const uint64_t* pt_offsets, uint8_t* encs, uint8_t* cts,
+                          const uint64_t* ct_offsets, uint8_t* status, bool team) {
   if (!c) {
     set_err("null context");
     return PRIO3GPU_E_ARG;
   }
-  if (!hpke_seal_suite(kem_id, kdf_id, aead_id)) {
-    set_err("HPKE suite 0x%04x/%u/%u is not sealed on the GPU", kem_id, kdf_id, aead_id);
-    return PRIO3GPU_E_UNSUPPORTED;
-  }
+  CHK(seal_suite_check(kem_id, kdf_id, aead_id, team));
   if (!pk || pk_len != 32 || (info_len && !info)) {
     set_err("HPKE seal: the public key is 32 bytes");
     return PRIO3GPU_E_ARG;
@@ -782,26 +797,24 @@ int prio3gpu_hpke_seal_batch(prio3gpu_ctx* c, uint16_t kem_id, uint16_t kdf_id, 
     return PRIO3GPU_E_ARG;
   }
   return hpke_seal_batch_impl(c, kem_id, kdf_id, aead_id, pk, info, info_len, n, sk_es, aads,
-                              aad_offsets, pts, pt_offsets, encs, cts, ct_offsets, status);
+                              aad_offsets, pts, pt_offsets, encs, cts, ct_offsets, status, team);
 }
 
-int prio3gpu_seal_input_shares(prio3gpu_ctx* c, const uint8_t* task_id, uint16_t kem_id,
-                               uint16_t kdf_id, uint16_t aead_id, const uint8_t* pk,
-                               size_t pk_len, uint8_t recipient_role, size_t n,
-                               const uint8_t* report_ids, const uint64_t* times,
-                               const uint8_t* public_shares, uint32_t public_share_len,
-                               const uint8_t* input_shares, uint32_t input_share_len,
-                               size_t input_share_pitch, const uint8_t* sk_es, uint8_t* out_encs,
-                               size_t enc_pitch, uint8_t* out_payloads, size_t payload_pitch,
-                               uint8_t* status) {
+// prio3gpu_seal_input_shares and, with `team`, prio3gpu_seal_input_shares_long.
+int seal_input_shares_entry(prio3gpu_ctx* c, const uint8_t* task_id, uint16_t kem_id,
+                            uint16_t kdf_id, uint16_t aead_id, const uint8_t* pk, size_t pk_len,
+                            uint8_t recipient_role, size_t n, const uint8_t* report_ids,
+                            const uint64_t* times, const uint8_t* public_shares,
+                            uint32_t public_share_len, const uint8_t* input_shares,
+                            uint32_t input_share_len, size_t input_share_pitch,
+                            const uint8_t* sk_es, uint8_t* out_encs, size_t enc_pitch,
+                            uint8_t* out_payloads, size_t payload_pitch, uint8_t* status,
+                            bool team) {
   if (!c) {
     set_err("null context");
     return PRIO3GPU_E_ARG;
   }
-  if (!hpke_seal_suite(kem_id, kdf_id, aead_id)) {
-    set_err("HPKE suite 0x%04x/%u/%u is not sealed on the GPU", kem_id, kdf_id, aead_id);
-    return PRIO3GPU_E_UNSUPPORTED;
-  }
+  CHK(seal_suite_check(kem_id, kdf_id, aead_id, team));
   if (!pk || pk_len != 32 || !task_id) {
     set_err("seal_input_shares: the public key and the task id are 32 bytes");
     return PRIO3GPU_E_ARG;
@@ -849,15 +862,25 @@ int prio3gpu_seal_input_shares(prio3gpu_ctx* c, const uint8_t* task_id, uint16_t
     s.pt_bytes = share_bytes;
     CHK(stage_in(c, c->seal[2], input_shares, share_bytes, &s.d_pt, kHpkeMinStage));
     CHK(seal_ladders(c, pk, n, sk_es, &s));
-    {
+    // a lane per report, or (prio3gpu_seal_input_shares_long) a wave per report
+    auto launch = [&](auto kernel, size_t per_block) {
+      hipLaunchKernelGGL(kernel, dim3((unsigned)((n + per_block - 1) / per_block)), dim3(256), 0,
+                         c->stream, (uint32_t)n, bc, tid, s.d_eph, d_rid,
+                         reinterpret_cast<const uint64_t*>(d_time), d_pub, public_share_len,
+                         s.d_pt, input_share_len, (uint64_t)spitch, d_enc,
+                         (uint64_t)(enc_host ? 32 : epitch), d_pay,
+                         (uint64_t)(pay_host ? plen : ppitch), d_st);
+    };
+    if (team) {
+      PROF(KID_HPKE_SEAL_TEAM_SHARES);
+      hpke_team_dispatch(bc, [&](auto kdf, auto aead) {
+        launch(k_hpke_seal_team_shares<decltype(kdf)::value, decltype(aead)::value>,
+               kTeamsPerBlock);
+      });
+    } else {
       PROF(KID_HPKE_SEAL_SHARES);
       hpke_suite_dispatch(bc, [&](auto kdf, auto aead) {
-        hipLaunchKernelGGL((k_hpke_seal_shares<decltype(kdf)::value, decltype(aead)::value>),
-                           dim3((unsigned)((n + 255) / 256)), dim3(256), 0, c->stream, (uint32_t)n,
-                           bc, tid, s.d_eph, d_rid, reinterpret_cast<const uint64_t*>(d_time),
-                           d_pub, public_share_len, s.d_pt, input_share_len, (uint64_t)spitch,
-                           d_enc, (uint64_t)(enc_host ? 32 : epitch), d_pay,
-                           (uint64_t)(pay_host ? plen : ppitch), d_st);
+        launch(k_hpke_seal_shares<decltype(kdf)::value, decltype(aead)::value>, 256);
       });
     }
     HIPCHK(hipGetLastError());
@@ -869,6 +892,63 @@ int prio3gpu_seal_input_shares(prio3gpu_ctx* c, const uint8_t* task_id, uint16_t
   CHK(copy_out(c, status, d_st, n));
   return finish_call(c, {report_ids, times, public_shares, input_shares, sk_es, out_encs,
                          out_payloads, status});
+}
+
+}  // namespace
+
+extern "C" {
+
+int prio3gpu_hpke_seal_batch(prio3gpu_ctx* c, uint16_t kem_id, uint16_t kdf_id, uint16_t aead_id,
+                             const uint8_t* pk, size_t pk_len, const uint8_t* info,
+                             size_t info_len, size_t n, const uint8_t* sk_es, const uint8_t* aads,
+                             const uint64_t* aad_offsets, const uint8_t* pts,
+                             const uint64_t* pt_offsets, uint8_t* encs, uint8_t* cts,
+                             const uint64_t* ct_offsets, uint8_t* status) {
+  return hpke_seal_batch_entry(c, kem_id, kdf_id, aead_id, pk, pk_len, info, info_len, n, sk_es,
+                               aads, aad_offsets, pts, pt_offsets, encs, cts, ct_offsets, status,
+                               /*team=*/false);
+}
+
+int prio3gpu_hpke_seal_long_batch(prio3gpu_ctx* c, uint16_t kem_id, uint16_t kdf_id,
+                                  uint16_t aead_id, const uint8_t* pk, size_t pk_len,
+                                  const uint8_t* info, size_t info_len, size_t n,
+                                  const uint8_t* sk_es, const uint8_t* aads,
+                                  const uint64_t* aad_offsets, const uint8_t* pts,
+                                  const uint64_t* pt_offsets, uint8_t* encs, uint8_t* cts,
+                                  const uint64_t* ct_offsets, uint8_t* status) {
+  return hpke_seal_batch_entry(c, kem_id, kdf_id, aead_id, pk, pk_len, info, info_len, n, sk_es,
+                               aads, aad_offsets, pts, pt_offsets, encs, cts, ct_offsets, status,
+                               /*team=*/true);
+}
+
+int prio3gpu_seal_input_shares(prio3gpu_ctx* c, const uint8_t* task_id, uint16_t kem_id,
+                               uint16_t kdf_id, uint16_t aead_id, const uint8_t* pk,
+                               size_t pk_len, uint8_t recipient_role, size_t n,
+                               const uint8_t* report_ids, const uint64_t* times,
+                               const uint8_t* public_shares, uint32_t public_share_len,
+                               const uint8_t* input_shares, uint32_t input_share_len,
+                               size_t input_share_pitch, const uint8_t* sk_es, uint8_t* out_encs,
+                               size_t enc_pitch, uint8_t* out_payloads, size_t payload_pitch,
+                               uint8_t* status) {
+  return seal_input_shares_entry(c, task_id, kem_id, kdf_id, aead_id, pk, pk_len, recipient_role,
+                                 n, report_ids, times, public_shares, public_share_len,
+                                 input_shares, input_share_len, input_share_pitch, sk_es, out_encs,
+                                 enc_pitch, out_payloads, payload_pitch, status, /*team=*/false);
+}
+
+int prio3gpu_seal_input_shares_long(prio3gpu_ctx* c, const uint8_t* task_id, uint16_t kem_id,
+                                    uint16_t kdf_id, uint16_t aead_id, const uint8_t* pk,
+                                    size_t pk_len, uint8_t recipient_role, size_t n,
+                                    const uint8_t* report_ids, const uint64_t* times,
+                                    const uint8_t* public_shares, uint32_t public_share_len,
+                                    const uint8_t* input_shares, uint32_t input_share_len,
+                                    size_t input_share_pitch, const uint8_t* sk_es,
+                                    uint8_t* out_encs, size_t enc_pitch, uint8_t* out_payloads,
+                                    size_t payload_pitch, uint8_t* status) {
+  return seal_input_shares_entry(c, task_id, kem_id, kdf_id, aead_id, pk, pk_len, recipient_role,
+                                 n, report_ids, times, public_shares, public_share_len,
+                                 input_shares, input_share_len, input_share_pitch, sk_es, out_encs,
+                                 enc_pitch, out_payloads, payload_pitch, status, /*team=*/true);
 }
 
 int prio3gpu_hpke_open_batch(prio3gpu_ctx* c, uint16_t kem_id, uint16_t kdf_id, uint16_t aead_id,

@@ -174,6 +174,23 @@ struct SharePlaintext {
       load_block(share + (o - 6), (uint64_t)slen - (o - 6), d);
     }
   }
+  // block(o, d) where all sixteen bytes exist (o + 16 <= len()): one 16-byte load of the row, or
+  // for block 0 the header from registers and the row's first ten bytes
+  DEVI void whole(uint64_t o, uint32_t d[4]) const {
+    if (o == 0) {
+      const uint32_t be = bswap32(slen);
+      uint64_t lo;
+      uint16_t hi;
+      __builtin_memcpy(&lo, share, 8);
+      __builtin_memcpy(&hi, share + 8, 2);
+      d[0] = be << 16;
+      d[1] = (be >> 16) | ((uint32_t)lo << 16);
+      d[2] = (uint32_t)(lo >> 16);
+      d[3] = (uint32_t)(lo >> 48) | ((uint32_t)hi << 16);
+    } else {
+      __builtin_memcpy(d, share + (o - 6), 16);
+    }
+  }
 };
 
 }  // namespace p3g

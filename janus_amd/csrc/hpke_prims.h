@@ -48,6 +48,8 @@ struct PackedBytes {
   uint64_t n;
   P3G_HP uint64_t len() const { return n; }
   P3G_HP void block(uint64_t o, uint32_t d[4]) const { load_block(p + o, n - o, d); }
+  // block(o, d) where all sixteen bytes exist (o + 16 <= n): one 16-byte load
+  P3G_HP void whole(uint64_t o, uint32_t d[4]) const { __builtin_memcpy(d, p + o, 16); }
 };
 
 // ------------------------------------------------------------------------------------------------

@@ -222,23 +222,9 @@ def _dev_ptr(x, dtype):
     return _ptr(x, dtype)
 
 
-def seal_batch_gpu(gpu, config: HpkeConfig, info: bytes, sk_es, aads, aad_offsets, pts,
-                   pt_offsets, status=None, encs=None, cts=None, ct_offsets=None,
-                   n: Optional[int] = None):
-    """n HPKE seals to ONE recipient config on the GPU (prio3gpu_hpke_seal_batch), each under its
-    own ephemeral private key: any DHKEM(X25519, HKDF-SHA256) suite (KDF HKDF-SHA256 / -SHA384 /
-    -SHA512 x AEAD AES-128-GCM / AES-256-GCM / ChaCha20-Poly1305), no option needed.  `ValueError`
-    for any other suite (P-256 seals stay on `seal`), nothing launched.
-
-    `gpu` is a `Prio3Gpu` or a context handle.  Report i: ephemeral key = sk_es[32 i : 32 i + 32],
-    aad = aads[aad_offsets[i] : aad_offsets[i+1]], plaintext = pts[pt_offsets[i] :
-    pt_offsets[i+1]].  Buffers are numpy arrays (host), torch tensors (host or device) or integer
-    device pointers (then `n`, `encs`, `cts`, `ct_offsets` and `status` must be given).  By
-    default ciphertext i has the plaintext's length + 16 and the ciphertexts are packed.
-    -> (encs, cts, ct_offsets, status): enc i = encs[32 i : 32 i + 32], ciphertext || tag i =
-    cts[ct_offsets[i] : ct_offsets[i+1]] -- the bytes `seal` gives with the same ephemeral key.  A
-    report that is not sealed (status non-zero on entry, a public key of small order, a slot that
-    is too short) has zeros in both and, unless it was skipped, status 4."""
+def _seal_batch_gpu(entry: str, gpu, config: HpkeConfig, info: bytes, sk_es, aads, aad_offsets,
+                    pts, pt_offsets, status, encs, cts, ct_offsets, n):
+    """`seal_batch_gpu` / `seal_long_batch_gpu` through the library's entry point `entry`."""
     if n is None:
         n = len(np.asarray(pt_offsets)) - 1
     if ct_offsets is None:
@@ -259,12 +245,44 @@ def seal_batch_gpu(gpu, config: HpkeConfig, info: bytes, sk_es, aads, aad_offset
         keep.append(k)
     for out, k in ((encs, keep[5]), (cts, keep[6]), (status, keep[8])):  # written in place
         assert k is None or k is out, "encs / cts / status must be contiguous uint8 arrays"
-    _rc(lib().prio3gpu_hpke_seal_batch(_ctx_handle(gpu), config.kem_id, config.kdf_id,
-                                       config.aead_id, _buf(config.public_key),
-                                       len(config.public_key), _buf(info), len(info), n, *args),
-        "HPKE GPU seal")
+    _rc(getattr(lib(), entry)(_ctx_handle(gpu), config.kem_id, config.kdf_id, config.aead_id,
+                              _buf(config.public_key), len(config.public_key), _buf(info),
+                              len(info), n, *args), "HPKE GPU seal")
     del keep
     return encs, cts, ct_offsets, status
+
+
+def seal_batch_gpu(gpu, config: HpkeConfig, info: bytes, sk_es, aads, aad_offsets, pts,
+                   pt_offsets, status=None, encs=None, cts=None, ct_offsets=None,
+                   n: Optional[int] = None):
+    """n HPKE seals to ONE recipient config on the GPU (prio3gpu_hpke_seal_batch), each under its
+    own ephemeral private key: any DHKEM(X25519, HKDF-SHA256) suite (KDF HKDF-SHA256 / -SHA384 /
+    -SHA512 x AEAD AES-128-GCM / AES-256-GCM / ChaCha20-Poly1305), no option needed.  `ValueError`
+    for any other suite (P-256 seals stay on `seal`), nothing launched.
+
+    `gpu` is a `Prio3Gpu` or a context handle.  Report i: ephemeral key = sk_es[32 i : 32 i + 32],
+    aad = aads[aad_offsets[i] : aad_offsets[i+1]], plaintext = pts[pt_offsets[i] :
+    pt_offsets[i+1]].  Buffers are numpy arrays (host), torch tensors (host or device) or integer
+    device pointers (then `n`, `encs`, `cts`, `ct_offsets` and `status` must be given).  By
+    default ciphertext i has the plaintext's length + 16 and the ciphertexts are packed.
+    -> (encs, cts, ct_offsets, status): enc i = encs[32 i : 32 i + 32], ciphertext || tag i =
+    cts[ct_offsets[i] : ct_offsets[i+1]] -- the bytes `seal` gives with the same ephemeral key.  A
+    report that is not sealed (status non-zero on entry, a public key of small order, a slot that
+    is too short) has zeros in both and, unless it was skipped, status 4."""
+    return _seal_batch_gpu("prio3gpu_hpke_seal_batch", gpu, config, info, sk_es, aads,
+                           aad_offsets, pts, pt_offsets, status, encs, cts, ct_offsets, n)
+
+
+def seal_long_batch_gpu(gpu, config: HpkeConfig, info: bytes, sk_es, aads, aad_offsets, pts,
+                        pt_offsets, status=None, encs=None, cts=None, ct_offsets=None,
+                        n: Optional[int] = None):
+    """`seal_batch_gpu` with one GPU wave per report instead of one lane
+    (prio3gpu_hpke_seal_long_batch): for plaintexts of many kilobytes, the leader's input shares.
+    DHKEM(X25519, HKDF-SHA256) with any KDF and AES-128-GCM / AES-256-GCM, no option needed;
+    `ValueError` for any other suite (P-256, ChaCha20-Poly1305), nothing launched.  Same arguments
+    and the same bytes, offsets and statuses.  -> (encs, cts, ct_offsets, status)."""
+    return _seal_batch_gpu("prio3gpu_hpke_seal_long_batch", gpu, config, info, sk_es, aads,
+                           aad_offsets, pts, pt_offsets, status, encs, cts, ct_offsets, n)
 
 
 def _rows(x, n: int, width: int, what: str):
@@ -283,20 +301,10 @@ def _rows(x, n: int, width: int, what: str):
     return a.ctypes.data, (a.strides[0] if n > 1 else width), a
 
 
-def seal_input_shares_gpu(gpu, task_id: bytes, config: HpkeConfig, recipient_role: int,
-                          report_ids, times, public_shares, input_shares, sk_es, out_encs=None,
-                          out_payloads=None, status=None):
-    """Seal n Prio3 input shares to one aggregator on the GPU (prio3gpu_seal_input_shares): for
-    report i, `seal(config, application_info(INPUT_SHARE, CLIENT, recipient_role),
-    PlaintextInputShare(no extensions, input_shares[i]), input_share_aad(task_id, report_ids[i],
-    times[i], public_shares[i]), sk_es[i])` -- neither frame is built in memory.
-
-    report_ids (n, 16), public_shares (n, public_share_len) or None, sk_es (n, 32): uint8 numpy
-    arrays or torch tensors, packed; times (n,) uint64; input_shares (n, len) uint8 whose rows may
-    be a column slice of a wider buffer, like out_encs (n, 32) and out_payloads (n, 6 + len + 16):
-    only those columns are written (host or device; e.g. the columns of a fixed-stride Report
-    buffer; allocated as numpy arrays by default).  -> (out_encs, out_payloads, status); a report
-    that is not sealed has zeros in both columns and, unless skipped on entry, status 4."""
+def _seal_input_shares_gpu(entry: str, gpu, task_id: bytes, config: HpkeConfig,
+                           recipient_role: int, report_ids, times, public_shares, input_shares,
+                           sk_es, out_encs, out_payloads, status):
+    """`seal_input_shares_gpu` / `seal_input_shares_long_gpu` through the entry point `entry`."""
     tid = np.frombuffer(bytes(task_id), np.uint8).copy()
     if tid.size != 32:
         raise ValueError("TaskId is 32 bytes")
@@ -319,14 +327,44 @@ def seal_input_shares_gpu(gpu, task_id: bytes, config: HpkeConfig, recipient_rol
     p_sk, k6 = _dev_ptr(sk_es, np.uint8)
     p_st, k7 = _dev_ptr(status, np.uint8)
     assert k7 is None or k7 is status, "status must be a contiguous uint8 array"
-    _rc(lib().prio3gpu_seal_input_shares(_ctx_handle(gpu), tid.ctypes.data, config.kem_id,
-                                         config.kdf_id, config.aead_id, _buf(config.public_key),
-                                         len(config.public_key), recipient_role, n, p_rid, p_tm,
-                                         p_pub, pslen, p_sh, slen, sh_pitch, p_sk, p_enc,
-                                         enc_pitch, p_pay, pay_pitch, p_st),
+    _rc(getattr(lib(), entry)(_ctx_handle(gpu), tid.ctypes.data, config.kem_id, config.kdf_id,
+                              config.aead_id, _buf(config.public_key), len(config.public_key),
+                              recipient_role, n, p_rid, p_tm, p_pub, pslen, p_sh, slen, sh_pitch,
+                              p_sk, p_enc, enc_pitch, p_pay, pay_pitch, p_st),
         "seal input shares (GPU)")
     del k0, k1, k2, k3, k4, k5, k6, k7
     return out_encs, out_payloads, status
+
+
+def seal_input_shares_gpu(gpu, task_id: bytes, config: HpkeConfig, recipient_role: int,
+                          report_ids, times, public_shares, input_shares, sk_es, out_encs=None,
+                          out_payloads=None, status=None):
+    """Seal n Prio3 input shares to one aggregator on the GPU (prio3gpu_seal_input_shares): for
+    report i, `seal(config, application_info(INPUT_SHARE, CLIENT, recipient_role),
+    PlaintextInputShare(no extensions, input_shares[i]), input_share_aad(task_id, report_ids[i],
+    times[i], public_shares[i]), sk_es[i])` -- neither frame is built in memory.
+
+    report_ids (n, 16), public_shares (n, public_share_len) or None, sk_es (n, 32): uint8 numpy
+    arrays or torch tensors, packed; times (n,) uint64; input_shares (n, len) uint8 whose rows may
+    be a column slice of a wider buffer, like out_encs (n, 32) and out_payloads (n, 6 + len + 16):
+    only those columns are written (host or device; e.g. the columns of a fixed-stride Report
+    buffer; allocated as numpy arrays by default).  -> (out_encs, out_payloads, status); a report
+    that is not sealed has zeros in both columns and, unless skipped on entry, status 4."""
+    return _seal_input_shares_gpu("prio3gpu_seal_input_shares", gpu, task_id, config,
+                                  recipient_role, report_ids, times, public_shares, input_shares,
+                                  sk_es, out_encs, out_payloads, status)
+
+
+def seal_input_shares_long_gpu(gpu, task_id: bytes, config: HpkeConfig, recipient_role: int,
+                               report_ids, times, public_shares, input_shares, sk_es,
+                               out_encs=None, out_payloads=None, status=None):
+    """`seal_input_shares_gpu` with one GPU wave per report instead of one lane
+    (prio3gpu_seal_input_shares_long): for the leader's input shares of many kilobytes.  Suites as
+    `seal_long_batch_gpu`, `ValueError` otherwise; the same arguments, the same bytes in the same
+    columns (at any alignment) and the same statuses.  -> (out_encs, out_payloads, status)."""
+    return _seal_input_shares_gpu("prio3gpu_seal_input_shares_long", gpu, task_id, config,
+                                  recipient_role, report_ids, times, public_shares, input_shares,
+                                  sk_es, out_encs, out_payloads, status)
 
 
 def open_long_batch_gpu(gpu, keypair: HpkeKeypair, info: bytes, encs, aads, aad_offsets, cts,

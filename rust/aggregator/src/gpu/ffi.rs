@@ -345,6 +345,25 @@ extern "C" {
                                       out_shares: *mut u8, share_pitch: usize,
                                       status: *mut u8) -> c_int;
 
+    // -- HPKE seal of long plaintexts on the GPU (X25519 x AES-GCM; one wave per report) --------
+    pub fn prio3gpu_hpke_seal_long_batch(ctx: *mut prio3gpu_ctx, kem_id: u16, kdf_id: u16,
+                                         aead_id: u16, pk: *const u8, pk_len: usize,
+                                         info: *const u8, info_len: usize, n: usize,
+                                         sk_es: *const u8, aads: *const u8,
+                                         aad_offsets: *const u64, pts: *const u8,
+                                         pt_offsets: *const u64, encs: *mut u8, cts: *mut u8,
+                                         ct_offsets: *const u64, status: *mut u8) -> c_int;
+    pub fn prio3gpu_seal_input_shares_long(ctx: *mut prio3gpu_ctx, task_id: *const u8,
+                                           kem_id: u16, kdf_id: u16, aead_id: u16, pk: *const u8,
+                                           pk_len: usize, recipient_role: u8, n: usize,
+                                           report_ids: *const u8, times: *const u64,
+                                           public_shares: *const u8, public_share_len: u32,
+                                           input_shares: *const u8, input_share_len: u32,
+                                           input_share_pitch: usize, sk_es: *const u8,
+                                           out_encs: *mut u8, enc_pitch: usize,
+                                           out_payloads: *mut u8, payload_pitch: usize,
+                                           status: *mut u8) -> c_int;
+
     // -- helper aggregate-init from the request's bytes (one call per job, one context) ---------
     pub fn prio3gpu_helper_init_request(ctx: *mut prio3gpu_ctx, st: *mut prio3gpu_state,
                                         task_id: *const u8,

@@ -10,6 +10,13 @@ Prio3SumVec(8, 1000, 89) shard.  Times are a host clock around a device synchron
 warm-up call; the per-kernel HIP-event times of one call are listed beside them.  One JSON line.
 
   python tools/bench_client_seal.py [--helper-n 65536] [--leader-n 4096] [--reps 3]
+
+With --long the run instead sets the wave-per-report seal (hpke.seal_input_shares_long_gpu) beside
+the lane-per-report seal over the same device rows, alternating, outputs asserted equal: the
+leader share, the helper share, a sweep of share lengths with the threshold it gives for
+ClientBatch.LONG_SEAL_MIN_SHARE, and prepare_reports under long_seal=False and auto.
+
+  python tools/bench_client_seal.py --long [--threshold-from-sweep] [--out FILE.jsonl]
 """
 import argparse
 import ctypes
@@ -102,6 +109,126 @@ def seal_case(v, kp, role, n, slen, pub_len, reps, host_n, rng, dev):
             "kernel_ms": stage_ms(v, gpu_call)}
 
 
+def spread(xs):
+    """{median, min, max} of a list of seconds, in milliseconds."""
+    return {"median_ms": round(1e3 * statistics.median(xs), 3), "min_ms": round(1e3 * min(xs), 3),
+            "max_ms": round(1e3 * max(xs), 3)}
+
+
+def wins(fast, slow):
+    """`fast` beats `slow` by more than the sum of the two min..max spreads."""
+    return (slow["median_ms"] - fast["median_ms"]
+            > (slow["max_ms"] - slow["min_ms"]) + (fast["max_ms"] - fast["min_ms"]))
+
+
+def long_case(v, kp, role, n, slen, pub_len, reps, rng, dev):
+    """seal_input_shares_long_gpu (a wave per report) and seal_input_shares_gpu (a lane per
+    report) over the same n device rows of slen bytes, rep by rep in turn after one warm-up of
+    each; the outputs must be equal."""
+    ids = rng.integers(0, 256, (n, 16), dtype=np.uint8)
+    times = np.full(n, 1_700_000_000, np.uint64)
+    pub = rng.integers(0, 256, (n, pub_len), dtype=np.uint8)
+    sk = rng.integers(0, 256, (n, 32), dtype=np.uint8)
+    d_shares = torch.randint(0, 256, (n, slen), dtype=torch.uint8, device=dev)
+    d_ids, d_pub, d_sk = (torch.from_numpy(a).to(dev) for a in (ids, pub, sk))
+    d_times = torch.from_numpy(times.view(np.int64)).to(dev)
+    plen = 6 + slen + 16
+    outs = {k: (torch.empty((n, 32), dtype=torch.uint8, device=dev),
+                torch.empty((n, plen), dtype=torch.uint8, device=dev)) for k in ("wave", "lane")}
+    fns = {"wave": H.seal_input_shares_long_gpu, "lane": H.seal_input_shares_gpu}
+
+    def call(k):
+        d_st = torch.zeros(n, dtype=torch.uint8, device=dev)
+        torch.cuda.synchronize()
+        fns[k](v, TASK_ID, kp.config, role, d_ids, d_times, d_pub, d_shares, d_sk, *outs[k],
+               status=d_st)
+        torch.cuda.synchronize()
+        return d_st
+
+    for k in fns:                                               # warm-up
+        assert not call(k).any().item()
+    assert torch.equal(outs["wave"][0], outs["lane"][0])
+    assert torch.equal(outs["wave"][1], outs["lane"][1])
+    secs = {"wave": [], "lane": []}
+    for _ in range(reps):
+        for k in fns:
+            t = time.perf_counter()
+            call(k)
+            secs[k].append(time.perf_counter() - t)
+    res = {"n": n, "share_bytes": slen, "sealed_bytes": n * (6 + slen)}
+    for k in fns:
+        res[k] = dict(spread(secs[k]), kernel_ms=stage_ms(v, lambda: call(k)))
+    res["wave_over_lane"] = round(res["lane"]["median_ms"] / res["wave"]["median_ms"], 2)
+    res["wave_wins_by_more_than_the_spreads"] = wins(res["wave"], res["lane"])
+    return res
+
+
+SWEEP = ((256, 16384), (1024, 8192), (2576, 4096), (16384, 4096), (65536, 4096))   # (share, n)
+
+
+def long_main(args, v, lkp, hkp, rng, dev):
+    """The wave-per-report seal beside the lane-per-report seal (--long): (a) the leader share,
+    (b) the helper share, (c) a length sweep and the threshold it gives, (d) prepare_reports with
+    long_seal=False and auto."""
+    s = v.sizes
+    out = {"what": "client seal on one GPU, a wave per report beside a lane per report: X25519 / "
+                   "HKDF-SHA256 / AES-128-GCM seals of Prio3 input shares from device rows, the "
+                   "two paths alternating over the same inputs (outputs asserted equal), host "
+                   "clock around a synchronise, median of reps with min..max; and whole "
+                   "Prio3SumVec(8, 1000, 89) reports under long_seal=False and auto",
+           "reps": args.reps}
+    out["a_leader_share"] = long_case(v, lkp, H.ROLE_LEADER, args.leader_n, s.leader_input_share,
+                                      s.public_share, args.reps, rng, dev)
+    out["b_helper_share"] = long_case(v, hkp, H.ROLE_HELPER, args.helper_n, s.helper_input_share,
+                                      s.public_share, args.reps, rng, dev)
+    sweep = [long_case(v, lkp, H.ROLE_LEADER, n, slen, s.public_share, args.reps, rng, dev)
+             for slen, n in SWEEP]
+    out["c_sweep"] = sweep
+    # the smallest swept length from which the wave path wins at every longer length too
+    threshold = None
+    for case in reversed(sweep + [out["a_leader_share"]]):
+        if not case["wave_wins_by_more_than_the_spreads"]:
+            break
+        threshold = case["share_bytes"]
+    out["c_threshold"] = threshold
+    out["configured_long_seal_min_share"] = ClientBatch.LONG_SEAL_MIN_SHARE
+    if args.threshold_from_sweep:
+        ClientBatch.LONG_SEAL_MIN_SHARE = threshold
+    n = args.reports_n
+    meas = rng.integers(0, 256, (n, 1000), dtype=np.int64)
+    ids = rng.integers(0, 256, (n, 16), dtype=np.uint8)
+    rand = rng.integers(0, 256, (n, v.random_size()), dtype=np.uint8)
+    sk = rng.integers(0, 256, (2, n, 32), dtype=np.uint8)
+    times = np.full(n, 1_700_000_000, np.uint64)
+    cbs = {"lane": ClientBatch(v, TASK_ID, lkp.config, hkp.config, 3600, long_seal=False),
+           "auto": ClientBatch(v, TASK_ID, lkp.config, hkp.config, 3600)}
+
+    def prepare(k):
+        r = cbs[k].prepare_reports(meas, report_ids=ids, times=times, rand=rand, sk_es=sk,
+                                   device_out=True)
+        torch.cuda.synchronize()
+        return r
+
+    got = {k: prepare(k) for k in cbs}                          # warm-up, and the byte check
+    assert torch.equal(got["lane"], got["auto"])
+    del got
+    secs = {"lane": [], "auto": []}
+    for _ in range(args.reps):
+        for k in cbs:
+            t = time.perf_counter()
+            prepare(k)
+            secs[k].append(time.perf_counter() - t)
+    d = {"n": n, "report_bytes": cbs["lane"].report_len,
+         "auto_min_share": ClientBatch.LONG_SEAL_MIN_SHARE,
+         "auto_wave_routes": dict(zip(("leader", "helper"), cbs["auto"]._wave))}
+    for k in cbs:
+        d[k] = dict(spread(secs[k]), reports_per_s=round(n / statistics.median(secs[k])),
+                    kernel_ms=stage_ms(v, lambda: prepare(k)))
+        cbs[k].close()
+    out["d_prepare_reports"] = d
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--helper-n", type=int, default=65536)
@@ -109,7 +236,26 @@ def main():
     ap.add_argument("--reports-n", type=int, default=4096)
     ap.add_argument("--host-n", type=int, default=2048, help="reports of the host seal loop")
     ap.add_argument("--reps", type=int, default=3)
+    ap.add_argument("--long", action="store_true",
+                    help="the wave-per-report seal beside the lane-per-report seal instead")
+    ap.add_argument("--threshold-from-sweep", action="store_true",
+                    help="with --long: auto in prepare_reports routes by the threshold this run's "
+                         "sweep gives, not by ClientBatch.LONG_SEAL_MIN_SHARE")
+    ap.add_argument("--out", help="append the JSON line to this file as well")
     args = ap.parse_args()
+    if args.long:
+        rng = np.random.default_rng(2026)
+        vk = hashlib.shake_128(b"verify-key client seal").digest(16)
+        v = Prio3Gpu.new_sum_vec(8, 1000, 89, vk, device=0)
+        line = json.dumps(long_main(args, v, H.generate_hpke_config_and_private_key(1),
+                                    H.generate_hpke_config_and_private_key(2), rng,
+                                    torch.device("cuda", 0)))
+        v.close()
+        print(line, flush=True)
+        if args.out:
+            with open(args.out, "a") as f:
+                f.write(line + "\n")
+        return
     dev = torch.device("cuda", 0)
     rng = np.random.default_rng(2025)
     vk = hashlib.shake_128(b"verify-key client seal").digest(16)
