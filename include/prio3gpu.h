@@ -175,6 +175,12 @@ int prio3gpu_ctx_set_async(prio3gpu_ctx* ctx, int on);
  *                   host.  1: the GPU opens them too (k_p256_dh): 0x0010 / 1 / 1 with this option
  *                   alone, all nine 0x0010 / KDF 1-3 / AEAD 1-3 with "hpke_gpu_suites" = 1 as
  *                   well.  Independent of "hpke_gpu_suites".  Any other value is PRIO3GPU_E_ARG
+ *   "hpke_team_chacha"  0 (default): the wave-per-report entry points (prio3gpu_hpke_open_long_batch,
+ *                   prio3gpu_open_input_shares, prio3gpu_hpke_seal_long_batch,
+ *                   prio3gpu_seal_input_shares_long) take AES-GCM only and answer
+ *                   PRIO3GPU_E_UNSUPPORTED for ChaCha20-Poly1305 (AEAD 3).  1: they take 0x0020 /
+ *                   KDF 1-3 / AEAD 3 as well (chacha_poly_team.h).  It changes no other entry
+ *                   point.  Any other value is PRIO3GPU_E_ARG
  * The engine reads no environment variables.  PRIO3GPU_E_ARG for an unknown name. */
 int prio3gpu_ctx_set_option(prio3gpu_ctx* ctx, const char* name, int64_t value);
 /* Work queued on `ctx` from now on starts only after all work queued on `other` so far. */
@@ -629,9 +635,10 @@ int prio3gpu_seal_input_shares(prio3gpu_ctx* ctx, const uint8_t* task_id, uint16
  * n opens under ONE keypair, one GPU WAVE per report: what the leader does once per upload with an
  * input share of a hundred kilobytes (aggregator.rs:1325-1497), where a lane per report would walk
  * each ciphertext alone.  Suites: DHKEM(X25519, HKDF-SHA256) (KEM 0x0020) with KDF 1-3 and
- * AES-128-GCM / AES-256-GCM (AEAD 1, 2), no context option needed.  KEM 0x0010 (P-256), AEAD 3
- * (ChaCha20-Poly1305) or an unknown id is PRIO3GPU_E_UNSUPPORTED with nothing launched; n == 0
- * returns 0 and launches nothing.
+ * AES-128-GCM / AES-256-GCM (AEAD 1, 2), no context option needed, and with the context option
+ * "hpke_team_chacha" = 1 ChaCha20-Poly1305 (AEAD 3) too.  KEM 0x0010 (P-256), AEAD 3 while that
+ * option is 0, or an unknown id is PRIO3GPU_E_UNSUPPORTED with nothing launched; n == 0 returns 0
+ * and launches nothing.
  * prio3gpu_hpke_open_long_batch has the arguments and contracts of prio3gpu_hpke_open_batch --
  * host or device pointers, status in/out, zero-filled slots, zeros and status 4 for a failed
  * open, the handling of secrets -- and the same plaintexts, for every ciphertext length from 16
@@ -644,7 +651,9 @@ int prio3gpu_hpke_open_long_batch(prio3gpu_ctx* ctx, uint16_t kem_id, uint16_t k
                                   const uint8_t* cts, const uint64_t* ct_offsets, uint8_t* pts,
                                   const uint64_t* pt_offsets, uint8_t* status);
 /* Upload: open n Prio3 input shares sealed to this aggregator (handle_upload_generic's decrypt and
- * decode, aggregator.rs:1325-1497), the mirror of prio3gpu_seal_input_shares.  Report i's
+ * decode, aggregator.rs:1325-1497), the mirror of prio3gpu_seal_input_shares, a wave per report
+ * and for the suites above (AEAD 3 with "hpke_team_chacha" = 1, PRIO3GPU_E_UNSUPPORTED without
+ * it).  Report i's
  * encapsulated key (32 bytes) is read from encs + i enc_pitch and its payload, exactly
  * 6 + input_share_len + 16 bytes, from payloads + i payload_pitch, so both may be columns of one
  * fixed-stride Report buffer; its AAD is the InputShareAad of task_id, report_ids[16 i ..],
@@ -677,7 +686,8 @@ int prio3gpu_open_input_shares(prio3gpu_ctx* ctx, const uint8_t* task_id, uint16
  * client does with the leader's input share of a hundred kilobytes, where a lane per report would
  * walk each plaintext alone; the mirror of prio3gpu_hpke_open_long_batch.  Suites:
  * DHKEM(X25519, HKDF-SHA256) (KEM 0x0020) with KDF 1-3 and AES-128-GCM / AES-256-GCM (AEAD 1, 2),
- * no context option needed.  KEM 0x0010 (P-256), AEAD 3 (ChaCha20-Poly1305: it stays on
+ * no context option needed, and with the context option "hpke_team_chacha" = 1
+ * ChaCha20-Poly1305 (AEAD 3) too.  KEM 0x0010 (P-256), AEAD 3 while that option is 0 (it stays on
  * prio3gpu_hpke_seal_batch) or an unknown id is PRIO3GPU_E_UNSUPPORTED with nothing launched;
  * n == 0 returns 0 and launches nothing.
  * prio3gpu_hpke_seal_long_batch has the arguments and contracts of prio3gpu_hpke_seal_batch --
@@ -692,7 +702,8 @@ int prio3gpu_hpke_seal_long_batch(prio3gpu_ctx* ctx, uint16_t kem_id, uint16_t k
                                   const uint64_t* aad_offsets, const uint8_t* pts,
                                   const uint64_t* pt_offsets, uint8_t* encs, uint8_t* cts,
                                   const uint64_t* ct_offsets, uint8_t* status);
-/* Client: prio3gpu_seal_input_shares with a wave per report, for the suites above: the same
+/* Client: prio3gpu_seal_input_shares with a wave per report, for the suites above (AEAD 3 with
+ * "hpke_team_chacha" = 1, PRIO3GPU_E_UNSUPPORTED without it): the same
  * arguments, pitches (0 = packed; shorter than the row = PRIO3GPU_E_ARG), statuses, handling of
  * secrets and bytes.  The enc and payload columns may sit at any alignment (a whole 16-byte block
  * leaves as the widest naturally aligned pieces its address allows); no byte outside the two

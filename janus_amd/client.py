@@ -169,17 +169,29 @@ class ClientBatch:
     False: a GPU lane per report (`hpke.seal_input_shares_gpu`).  True: a wave per report
     (`hpke.seal_input_shares_long_gpu`) for both aggregators; `ValueError` here unless both AEADs
     are AES-GCM.  None: the wave per report where the AEAD is AES-GCM and the input share has at
-    least `LONG_SEAL_MIN_SHARE` bytes, else the lane."""
+    least `LONG_SEAL_MIN_SHARE` bytes, else the lane.
+
+    `team_chacha` sets the option "hpke_team_chacha" on `vdaf`'s context, with which the wave per
+    report takes ChaCha20-Poly1305 too: `long_seal=True` is then allowed for such configs, and
+    under `long_seal=None` such a config takes the wave from `LONG_SEAL_MIN_SHARE_CHACHA` bytes
+    on.  Without it a ChaCha20-Poly1305 config is sealed a lane per report, as before."""
 
     # The shortest input share from which the wave-per-report seal is measured to win at every
     # longer length too: the Sum32 leader share, 1.7x at 4,096 reports; at 1,024 bytes the lane per
     # report is still ahead (DESIGN.md §8b "Seal at the client, a wave per report").  None would
     # keep the lane per report everywhere under long_seal=None.
     LONG_SEAL_MIN_SHARE: Optional[int] = 2576
+    # The same rule for a ChaCha20-Poly1305 config under team_chacha=True: the smallest measured
+    # length from which the wave per report wins, by more than the two spreads, at every longer
+    # measured length.  4,096 shares: 1,024 bytes 1.05 ms against the lane's 1.06 (inside the
+    # spreads), 2,576 bytes 1.05 against 1.42, 65,536 bytes 1.45 against 15.12, 134,944 bytes
+    # 1.63 against 33.58; 65,536 shares of 48 bytes 5.36 against 1.58 (DESIGN.md §8b
+    # "ChaCha20-Poly1305, a wave per report").  None would keep the lane per report.
+    LONG_SEAL_MIN_SHARE_CHACHA: Optional[int] = 2576
 
     def __init__(self, vdaf, task_id: bytes, leader_config: H.HpkeConfig,
                  helper_config: H.HpkeConfig, time_precision: int,
-                 long_seal: Optional[bool] = None):
+                 long_seal: Optional[bool] = None, team_chacha: bool = False):
         if len(task_id) != 32:
             raise ValueError("TaskId is 32 bytes")
         if time_precision <= 0:
@@ -187,17 +199,24 @@ class ClientBatch:
         for c in (leader_config, helper_config):
             if c.kem_id != H.KEM_X25519_HKDF_SHA256:
                 raise ValueError("the GPU seals to DHKEM(X25519, HKDF-SHA256) configs only")
-        gcm = [c.aead_id in (H.AEAD_AES128GCM, H.AEAD_AES256GCM)
-               for c in (leader_config, helper_config)]
-        if long_seal and not all(gcm):
-            raise ValueError("long_seal=True needs AES-128-GCM or AES-256-GCM configs")
+        # per aggregator, the shortest share a wave per report seals under long_seal=None (None:
+        # never), or False where the wave does not take the AEAD at all
+        floors = [self.LONG_SEAL_MIN_SHARE
+                  if c.aead_id in (H.AEAD_AES128GCM, H.AEAD_AES256GCM) else
+                  self.LONG_SEAL_MIN_SHARE_CHACHA
+                  if team_chacha and c.aead_id == H.AEAD_CHACHA20POLY1305 else False
+                  for c in (leader_config, helper_config)]
+        if long_seal and any(f is False for f in floors):
+            raise ValueError("long_seal=True needs AES-128-GCM or AES-256-GCM configs, or "
+                             "ChaCha20-Poly1305 ones with team_chacha=True")
+        if team_chacha:
+            vdaf.set_option("hpke_team_chacha", 1)
         s = vdaf.sizes
-        floor = self.LONG_SEAL_MIN_SHARE
         # (leader, helper): whether a wave per report seals that aggregator's shares
         self._wave = tuple(
             bool(long_seal) if long_seal is not None else
-            (g and floor is not None and share >= floor)
-            for g, share in zip(gcm, (s.leader_input_share, s.helper_input_share)))
+            (f is not None and f is not False and share >= f)
+            for f, share in zip(floors, (s.leader_input_share, s.helper_input_share)))
         self.vdaf, self.task_id = vdaf, bytes(task_id)
         self.leader_config, self.helper_config = leader_config, helper_config
         self.time_precision = int(time_precision)

@@ -1445,6 +1445,12 @@ int prio3gpu_ctx_set_option(prio3gpu_ctx* c, const char* name, int64_t value) {
       return PRIO3GPU_E_ARG;
     }
     c->hpke_gpu_p256 = on;
+  } else if (k == "hpke_team_chacha") {
+    if (value < 0 || value > 1) {
+      set_err("option hpke_team_chacha: %lld is not 0 or 1", (long long)value);
+      return PRIO3GPU_E_ARG;
+    }
+    c->hpke_team_chacha = on;
   } else if (k == "expand_lds" || k == "jr_lds") {
     if (value < 0 || value > 160 * 1024) {
       set_err("option %s: %lld bytes is outside [0, 163840]", name, (long long)value);

@@ -191,18 +191,22 @@ void hpke_suite_dispatch(const HpkeBatchConsts& bc, F&& f) {
   else with_aead(std::integral_constant<int, 3>{});
 }
 
-// The suites the wave-per-report open takes (hpke_open_team.h; no option: it has entry points of
-// its own): DHKEM(X25519, HKDF-SHA256) with KDF 1-3 and AES-128-GCM / AES-256-GCM.
-bool hpke_team_suite(uint16_t kem, uint16_t kdf, uint16_t aead) {
-  return kem == 0x0020 && kdf >= 1 && kdf <= 3 && (aead == 1 || aead == 2);
+// The suites the wave-per-report opens and seals take (hpke_open_team.h, hpke_seal_team.h; they
+// have entry points of their own): DHKEM(X25519, HKDF-SHA256) with KDF 1-3 and AES-128-GCM /
+// AES-256-GCM, and with the context's "hpke_team_chacha" option ChaCha20-Poly1305 too.
+bool hpke_team_suite(const prio3gpu_ctx* c, uint16_t kem, uint16_t kdf, uint16_t aead) {
+  return kem == 0x0020 && kdf >= 1 && kdf <= 3 &&
+         (aead == 1 || aead == 2 || (aead == 3 && c->hpke_team_chacha));
 }
 
-// f(KDF, AEAD) for such a suite.
+// f(KDF, AEAD) for such a suite (the entry points have checked it with hpke_team_suite); the
+// ChaCha20-Poly1305 instantiations are reached with the context's option only.
 template <class F>
-void hpke_team_dispatch(const HpkeBatchConsts& bc, F&& f) {
+void hpke_team_dispatch(const prio3gpu_ctx* c, const HpkeBatchConsts& bc, F&& f) {
   auto with_aead = [&](auto kdf) {
     if (bc.aead_id == 1) f(kdf, std::integral_constant<int, 1>{});
-    else f(kdf, std::integral_constant<int, 2>{});
+    else if (bc.aead_id == 2) f(kdf, std::integral_constant<int, 2>{});
+    else if (c->hpke_team_chacha) f(kdf, std::integral_constant<int, 3>{});
   };
   if (bc.kdf_id == 1) with_aead(std::integral_constant<int, 1>{});
   else if (bc.kdf_id == 2) with_aead(std::integral_constant<int, 2>{});
@@ -217,7 +221,7 @@ int launch_hpke_open_team(prio3gpu_ctx* c, const HpkeBatchConsts& bc, size_t n,
                           const uint64_t* d_poff, uint64_t pt_total, uint8_t* d_st) {
   {
     PROF(KID_HPKE_OPEN_TEAM);
-    hpke_team_dispatch(bc, [&](auto kdf, auto aead) {
+    hpke_team_dispatch(c, bc, [&](auto kdf, auto aead) {
       hipLaunchKernelGGL((k_hpke_open_team<decltype(kdf)::value, decltype(aead)::value>),
                          dim3((unsigned)((n + kTeamsPerBlock - 1) / kTeamsPerBlock)), dim3(256), 0,
                          c->stream, (uint32_t)n, bc, d_dh, d_enc, d_aad, d_aoff, aad_total, d_ct,
@@ -728,7 +732,7 @@ int hpke_seal_batch_impl(prio3gpu_ctx* c, uint16_t kem_id, uint16_t kdf_id, uint
     };
     if (team) {
       PROF(KID_HPKE_SEAL_TEAM);
-      hpke_team_dispatch(bc, [&](auto kdf, auto aead) {
+      hpke_team_dispatch(c, bc, [&](auto kdf, auto aead) {
         launch(k_hpke_seal_team<decltype(kdf)::value, decltype(aead)::value>, kTeamsPerBlock);
       });
     } else {
@@ -765,9 +769,10 @@ int seal_rows_to_host(prio3gpu_ctx* c, uint8_t* dst, size_t pitch, const uint8_t
 }
 
 // The suite check of a seal entry point: a lane per report (hpke_seal_gpu.h), or with `team` a wave
-// per report (hpke_seal_team.h: the suites of the wave-per-report open).
-int seal_suite_check(uint16_t kem_id, uint16_t kdf_id, uint16_t aead_id, bool team) {
-  if (team ? hpke_team_suite(kem_id, kdf_id, aead_id) : hpke_seal_suite(kem_id, kdf_id, aead_id))
+// per report (hpke_seal_team.h: the suites of the wave-per-report open on this context).
+int seal_suite_check(const prio3gpu_ctx* c, uint16_t kem_id, uint16_t kdf_id, uint16_t aead_id,
+                     bool team) {
+  if (team ? hpke_team_suite(c, kem_id, kdf_id, aead_id) : hpke_seal_suite(kem_id, kdf_id, aead_id))
     return 0;
   set_err("HPKE suite 0x%04x/%u/%u is not sealed %s", kem_id, kdf_id, aead_id,
           team ? "a wave per report" : "on the GPU");
@@ -785,7 +790,7 @@ int hpke_seal_batch_entry(prio3gpu_ctx* c, uint16_t kem_id, uint16_t kdf_id, uin
     set_err("null context");
     return PRIO3GPU_E_ARG;
   }
-  CHK(seal_suite_check(kem_id, kdf_id, aead_id, team));
+  CHK(seal_suite_check(c, kem_id, kdf_id, aead_id, team));
   if (!pk || pk_len != 32 || (info_len && !info)) {
     set_err("HPKE seal: the public key is 32 bytes");
     return PRIO3GPU_E_ARG;
@@ -814,7 +819,7 @@ int seal_input_shares_entry(prio3gpu_ctx* c, const uint8_t* task_id, uint16_t ke
     set_err("null context");
     return PRIO3GPU_E_ARG;
   }
-  CHK(seal_suite_check(kem_id, kdf_id, aead_id, team));
+  CHK(seal_suite_check(c, kem_id, kdf_id, aead_id, team));
   if (!pk || pk_len != 32 || !task_id) {
     set_err("seal_input_shares: the public key and the task id are 32 bytes");
     return PRIO3GPU_E_ARG;
@@ -873,7 +878,7 @@ int seal_input_shares_entry(prio3gpu_ctx* c, const uint8_t* task_id, uint16_t ke
     };
     if (team) {
       PROF(KID_HPKE_SEAL_TEAM_SHARES);
-      hpke_team_dispatch(bc, [&](auto kdf, auto aead) {
+      hpke_team_dispatch(c, bc, [&](auto kdf, auto aead) {
         launch(k_hpke_seal_team_shares<decltype(kdf)::value, decltype(aead)::value>,
                kTeamsPerBlock);
       });
@@ -996,7 +1001,7 @@ int prio3gpu_hpke_open_long_batch(prio3gpu_ctx* c, uint16_t kem_id, uint16_t kdf
     set_err("null context");
     return PRIO3GPU_E_ARG;
   }
-  if (!hpke_team_suite(kem_id, kdf_id, aead_id)) {
+  if (!hpke_team_suite(c, kem_id, kdf_id, aead_id)) {
     set_err("HPKE suite 0x%04x/%u/%u is not opened a wave per report", kem_id, kdf_id, aead_id);
     return PRIO3GPU_E_UNSUPPORTED;
   }
@@ -1026,7 +1031,7 @@ int prio3gpu_open_input_shares(prio3gpu_ctx* c, const uint8_t* task_id, uint16_t
     set_err("null context");
     return PRIO3GPU_E_ARG;
   }
-  if (!hpke_team_suite(kem_id, kdf_id, aead_id)) {
+  if (!hpke_team_suite(c, kem_id, kdf_id, aead_id)) {
     set_err("HPKE suite 0x%04x/%u/%u is not opened a wave per report", kem_id, kdf_id, aead_id);
     return PRIO3GPU_E_UNSUPPORTED;
   }
@@ -1090,7 +1095,7 @@ int prio3gpu_open_input_shares(prio3gpu_ctx* c, const uint8_t* task_id, uint16_t
   if (!rc) {
     {
       PROF(KID_HPKE_OPEN_TEAM_SHARES);
-      hpke_team_dispatch(bc, [&](auto kdf, auto aead) {
+      hpke_team_dispatch(c, bc, [&](auto kdf, auto aead) {
         hipLaunchKernelGGL((k_hpke_open_team_shares<decltype(kdf)::value, decltype(aead)::value>),
                            dim3((unsigned)((n + kTeamsPerBlock - 1) / kTeamsPerBlock)), dim3(256),
                            0, c->stream, (uint32_t)n, bc, tid, d_dh, d_rid,

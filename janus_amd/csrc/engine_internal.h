@@ -179,6 +179,9 @@ struct prio3gpu_ctx {
   // "hpke_gpu_p256": 1 lets the GPU open DHKEM(P-256, HKDF-SHA256) too (k_p256_dh): with
   // HKDF-SHA256 / AES-128-GCM, and with every KDF and AEAD when "hpke_gpu_suites" is on as well
   bool hpke_gpu_p256 = false;
+  // "hpke_team_chacha": 1 lets the wave-per-report opens and seals (hpke_team_suite) take
+  // ChaCha20-Poly1305 (AEAD 3) beside AES-GCM; 0 leaves it PRIO3GPU_E_UNSUPPORTED there
+  bool hpke_team_chacha = false;
   size_t expand_lds = 0;     // "expand_lds": dynamic LDS per k_expand block (occupancy cap)
   size_t jr_lds = 0;         // "jr_lds": dynamic LDS per k_jr block (occupancy cap)
   uint32_t cus = 0;          // compute units of the device

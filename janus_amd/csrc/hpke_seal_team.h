@@ -1,7 +1,8 @@
 // Batched HPKE seal of long plaintexts on the GPU, one WAVE per report: DHKEM(X25519, HKDF-SHA256)
-// with HKDF-SHA256 / -SHA384 / -SHA512 and AES-128-GCM / AES-256-GCM, RFC 9180 base mode, single
-// shot.  What a DAP client does for the leader's input share of a hundred kilobytes, where
-// hpke_seal_gpu.h's lane per report would walk it alone; the mirror of hpke_open_team.h:
+// with HKDF-SHA256 / -SHA384 / -SHA512 and AES-128-GCM / AES-256-GCM / ChaCha20-Poly1305, RFC 9180
+// base mode, single shot.  What a DAP client does for the leader's input share of a hundred
+// kilobytes, where hpke_seal_gpu.h's lane per report would walk it alone; the mirror of
+// hpke_open_team.h:
 //   k_hpke_seal_team<KDF, AEAD>          packed inputs with offsets, as k_hpke_seal takes them
 //   k_hpke_seal_team_shares<KDF, AEAD>   Prio3 input-share rows in, enc and payload columns out: the
 //                                        PlaintextInputShare and the InputShareAad are byte sources
@@ -12,8 +13,11 @@
 // (registers only); the lanes then share the plaintext by stripes (aes_gcm_team.h): a block is
 // encrypted, stored and absorbed by GHASH; the lanes' sums are XORed, every lane computes the tag
 // and one lane stores it.  The wave's table of H^1 .. H^64 (LDS, key-derived) is zeroed before the
-// wave ends.  Only the kernels and what crosses lanes are here; a lane's arithmetic is
-// aes_gcm_team.h's, free of HIP and run by a CPU test too.  The wave's place in its block
+// wave ends.  With ChaCha20-Poly1305 (AEAD 3) the lanes share the plaintext by 64-byte chunks
+// (chacha_poly_team.h): a block is encrypted, stored and absorbed by Poly1305, and the lanes' sums
+// are added by hpke_open_team.h's poly_team_sum; no S-box, no block barrier, no LDS.  Only the
+// kernels and what crosses lanes are here; a lane's arithmetic is aes_gcm_team.h's and
+// chacha_poly_team.h's, free of HIP and run by CPU tests too.  The wave's place in its block
 // (team_wave_setup, team_lds_sync, kTeam, kTeamsPerBlock) is hpke_open_team.h's.  Included by
 // engine_hpke.hip.
 #pragma once
@@ -35,7 +39,8 @@ __device__ __forceinline__ void hpke_seal_team_reject(uint8_t* enc_out, uint8_t*
 // the report's 8 little-endian words each as k_x25519_eph wrote them; enc_out gets the 32 bytes of
 // enc, ct gets pt.len() + 16 bytes (ciphertext || tag) and zeros up to ct_cap -- or everything
 // zeros and status 4 when the DH value is all zero, before any key is derived.  tbl: 4 kTeam words
-// of LDS of this wave's own, zero when the call returns.
+// of LDS of this wave's own, zero when the call returns; sbox and tbl are not read (null) for
+// ChaCha20-Poly1305.
 template <int KDF, int AEAD, class Pt, class Aad>
 __device__ __forceinline__ void hpke_seal_team_wave(const uint8_t* sbox, uint32_t* tbl,
                                                     const HpkeBatchConsts& bc, const uint32_t* enc,
@@ -57,29 +62,45 @@ __device__ __forceinline__ void hpke_seal_team_wave(const uint8_t* sbox, uint32_
     return;
   }
   constexpr int NKW = hpke_aead_nk(AEAD) / 4;
-  uint32_t key[NKW], nonce[3], rk[4 * (NKW + 7)], h[4], y0[4], ctr[4], t[4];
+  uint32_t key[NKW], nonce[3], t[4];
   hpke_key_nonce<KDF, AEAD>(bc, dhw, encw, key, nonce);
-  aes_gcm_start<NKW>(sbox, key, nonce, aad, rk, h, y0, ctr);
-  if (lane == 0) {
-#pragma unroll
-    for (int i = 0; i < 4; ++i) tbl[i] = h[i];
-  }
-  for (uint32_t half = 1; half < kTeam; half *= 2) {
-    team_lds_sync();
-    gf128_powers_step(tbl, lane, half);
-  }
-  team_lds_sync();
   const uint64_t plen = pt.len();
-  uint32_t acc[4] = {0, 0, 0, 0}, y[4];
   CtSink sink{ct};
-  gcm_team_seal_stripe<NKW>(sbox, rk, ctr, tbl, y0, pt, lane, kTeam, acc, sink);
+  if constexpr (AEAD == 3) {  // chacha_poly_team.h: no S-box and no table
+    uint32_t sum[5];
 #pragma unroll
-  for (int i = 0; i < 4; ++i) {  // the XOR of the 64 sums, on every lane
+    for (int i = 0; i < NKW; ++i) key[i] = bswap32(key[i]);
 #pragma unroll
-    for (int m = 1; m < (int)kTeam; m *= 2) acc[i] ^= (uint32_t)__shfl_xor((int)acc[i], m);
+    for (int i = 0; i < 3; ++i) nonce[i] = bswap32(nonce[i]);
+    PolyTeam mac;
+    chacha_team_start(mac, key, nonce, aad, plen, lane, kTeam);
+    chacha_team_stripe<true>(mac, key, nonce, pt, lane, kTeam, sink);
+#pragma unroll
+    for (int i = 0; i < 5; ++i) sum[i] = mac.mac.h[i];
+    poly_team_sum(sum);
+    poly_team_tag(mac, sum, aad.len(), plen, t);
+  } else {
+    uint32_t rk[4 * (NKW + 7)], h[4], y0[4], ctr[4];
+    aes_gcm_start<NKW>(sbox, key, nonce, aad, rk, h, y0, ctr);
+    if (lane == 0) {
+#pragma unroll
+      for (int i = 0; i < 4; ++i) tbl[i] = h[i];
+    }
+    for (uint32_t half = 1; half < kTeam; half *= 2) {
+      team_lds_sync();
+      gf128_powers_step(tbl, lane, half);
+    }
+    team_lds_sync();
+    uint32_t acc[4] = {0, 0, 0, 0}, y[4];
+    gcm_team_seal_stripe<NKW>(sbox, rk, ctr, tbl, y0, pt, lane, kTeam, acc, sink);
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {  // the XOR of the 64 sums, on every lane
+#pragma unroll
+      for (int m = 1; m < (int)kTeam; m *= 2) acc[i] ^= (uint32_t)__shfl_xor((int)acc[i], m);
+    }
+    gcm_team_join(y, acc, y0, plen);
+    aes_gcm_tag<NKW>(sbox, rk, h, y, ctr, aad.len(), plen, t);
   }
-  gcm_team_join(y, acc, y0, plen);
-  aes_gcm_tag<NKW>(sbox, rk, h, y, ctr, aad.len(), plen, t);
   if (lane == 0) store_block_any(ct + plen, t);
   if (lane < 2) {  // enc: sixteen bytes from each of two lanes
     uint32_t e[4];
@@ -88,8 +109,10 @@ __device__ __forceinline__ void hpke_seal_team_wave(const uint8_t* sbox, uint32_
     store_block_any(enc_out + 16 * lane, e);
   }
   team_zero(ct + plen + 16, ct_cap - plen - 16, lane, kTeam);
+  if constexpr (AEAD != 3) {
 #pragma unroll
-  for (int i = 0; i < 4; ++i) tbl[4 * lane + i] = 0;
+    for (int i = 0; i < 4; ++i) tbl[4 * lane + i] = 0;
+  }
 }
 
 // One wave per report over packed inputs, with k_hpke_seal's arguments and contracts: report r's
@@ -103,7 +126,7 @@ __global__ void __launch_bounds__(256) k_hpke_seal_team(
     const uint64_t* aad_off, uint64_t aad_total, const uint8_t* pts, const uint64_t* pt_off,
     uint64_t pt_total, uint8_t* encs, uint8_t* cts, const uint64_t* ct_off, uint64_t ct_total,
     uint8_t* status) {
-  const TeamWave w = team_wave_setup();
+  const TeamWave w = team_wave_setup<AEAD>();
   const uint32_t r = w.r, lane = w.lane;
   if (r >= n) return;
   const uint64_t a0 = aad_off[r], a1 = aad_off[r + 1], p0 = pt_off[r], p1 = pt_off[r + 1];
@@ -137,7 +160,7 @@ __global__ void __launch_bounds__(256) k_hpke_seal_team_shares(
     const uint64_t* times, const uint8_t* pubs, uint32_t pslen, const uint8_t* shares,
     uint32_t slen, uint64_t spitch, uint8_t* encs, uint64_t enc_pitch, uint8_t* payloads,
     uint64_t ppitch, uint8_t* status) {
-  const TeamWave w = team_wave_setup();
+  const TeamWave w = team_wave_setup<AEAD>();
   const uint32_t r = w.r, lane = w.lane;
   if (r >= n) return;
   uint8_t* enc_out = encs + (uint64_t)r * enc_pitch;

@@ -278,8 +278,9 @@ def seal_long_batch_gpu(gpu, config: HpkeConfig, info: bytes, sk_es, aads, aad_o
                         n: Optional[int] = None):
     """`seal_batch_gpu` with one GPU wave per report instead of one lane
     (prio3gpu_hpke_seal_long_batch): for plaintexts of many kilobytes, the leader's input shares.
-    DHKEM(X25519, HKDF-SHA256) with any KDF and AES-128-GCM / AES-256-GCM, no option needed;
-    `ValueError` for any other suite (P-256, ChaCha20-Poly1305), nothing launched.  Same arguments
+    DHKEM(X25519, HKDF-SHA256) with any KDF and AES-128-GCM / AES-256-GCM, no option needed, and
+    after `gpu.set_option("hpke_team_chacha", 1)` ChaCha20-Poly1305 too; `ValueError` for any
+    other suite (P-256; ChaCha20-Poly1305 without the option), nothing launched.  Same arguments
     and the same bytes, offsets and statuses.  -> (encs, cts, ct_offsets, status)."""
     return _seal_batch_gpu("prio3gpu_hpke_seal_long_batch", gpu, config, info, sk_es, aads,
                            aad_offsets, pts, pt_offsets, status, encs, cts, ct_offsets, n)
@@ -360,7 +361,7 @@ def seal_input_shares_long_gpu(gpu, task_id: bytes, config: HpkeConfig, recipien
                                out_encs=None, out_payloads=None, status=None):
     """`seal_input_shares_gpu` with one GPU wave per report instead of one lane
     (prio3gpu_seal_input_shares_long): for the leader's input shares of many kilobytes.  Suites as
-    `seal_long_batch_gpu`, `ValueError` otherwise; the same arguments, the same bytes in the same
+    `seal_long_batch_gpu` (ChaCha20-Poly1305 with "hpke_team_chacha"), `ValueError` otherwise; the same arguments, the same bytes in the same
     columns (at any alignment) and the same statuses.  -> (out_encs, out_payloads, status)."""
     return _seal_input_shares_gpu("prio3gpu_seal_input_shares_long", gpu, task_id, config,
                                   recipient_role, report_ids, times, public_shares, input_shares,
@@ -373,7 +374,8 @@ def open_long_batch_gpu(gpu, keypair: HpkeKeypair, info: bytes, encs, aads, aad_
     """`open_batch_gpu` with one GPU wave per report instead of one lane
     (prio3gpu_hpke_open_long_batch): for ciphertexts of many kilobytes, the leader's input shares
     at upload.  DHKEM(X25519, HKDF-SHA256) with any KDF and AES-128-GCM / AES-256-GCM, no option
-    needed; `ValueError` for any other suite (P-256, ChaCha20-Poly1305), nothing launched.  Same
+    needed, and after `gpu.set_option("hpke_team_chacha", 1)` ChaCha20-Poly1305 too; `ValueError`
+    for any other suite (P-256; ChaCha20-Poly1305 without the option), nothing launched.  Same
     arguments, plaintexts and statuses; buffers are numpy arrays (host), torch tensors (host or
     device) or integer device pointers (then `n`, `pts`, `pt_offsets` and `status` must be given).
     -> (plaintexts, pt_offsets, status); a failed open has status 4 and zeros."""
@@ -419,7 +421,8 @@ def open_input_shares_gpu(gpu, task_id: bytes, keypair: HpkeKeypair, recipient_r
     fixed-stride Report matrix), like out_shares (n, len): only those columns are written (a numpy
     array by default).  -> (out_shares, status); status 4 and a zero row for a failed open, 8 and
     a zero row for an authentic plaintext that is not an extension-free share of this length.
-    Suites as `open_long_batch_gpu`; `ValueError` otherwise."""
+    Suites as `open_long_batch_gpu` (ChaCha20-Poly1305 with "hpke_team_chacha"); `ValueError`
+    otherwise."""
     tid = np.frombuffer(bytes(task_id), np.uint8).copy()
     if tid.size != 32:
         raise ValueError("TaskId is 32 bytes")

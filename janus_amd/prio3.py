@@ -315,7 +315,8 @@ class Prio3Gpu:
     def set_option(self, name: str, value: int):
         """Engine option of this context (prio3gpu_ctx_set_option: "speculate", "wires_mfma",
         "wires_cols", "fused_helper", "helper_snap", "snap_chunk", "jr_ring", "spread",
-        "expand_lds", "jr_lds", "exact_squeeze", "hpke_gpu_suites", "hpke_gpu_p256")."""
+        "expand_lds", "jr_lds", "exact_squeeze", "hpke_gpu_suites", "hpke_gpu_p256",
+        "hpke_team_chacha")."""
         check(lib().prio3gpu_ctx_set_option(self._ctx, name.encode(), int(value)),
               f"ctx_set_option({name})")
 

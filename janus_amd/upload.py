@@ -27,23 +27,32 @@ ST_UNKNOWN_CONFIG, ST_DECRYPT, ST_INVALID_MESSAGE = 3, 4, 8
 ROW_ALIGN = 128
 
 
-def _gpu_suite(c: H.HpkeConfig) -> bool:
-    """The suites prio3gpu_open_input_shares takes."""
+def _gpu_suite(c: H.HpkeConfig, team_chacha: bool = False) -> bool:
+    """The suites prio3gpu_open_input_shares takes: X25519 with AES-GCM, and with the context's
+    "hpke_team_chacha" option (`team_chacha`) ChaCha20-Poly1305 too."""
+    aeads = (H.AEAD_AES128GCM, H.AEAD_AES256GCM) + \
+        ((H.AEAD_CHACHA20POLY1305,) if team_chacha else ())
     return (c.kem_id == H.KEM_X25519_HKDF_SHA256 and c.kdf_id in (1, 2, 3)
-            and c.aead_id in (H.AEAD_AES128GCM, H.AEAD_AES256GCM))
+            and c.aead_id in aeads)
 
 
 class UploadBatch:
     """The batched upload open of one task: `vdaf` a `Prio3Gpu`, the task's and the global
     `HpkeKeypair`s, and the role this aggregator plays (the leader by default: it is whom clients
-    upload to)."""
+    upload to).  `team_chacha` sets the option "hpke_team_chacha" on `vdaf`'s context: key groups
+    under ChaCha20-Poly1305 are then opened a GPU wave per report like the AES-GCM ones, not one
+    by one on the host."""
 
     def __init__(self, vdaf, task_id: bytes, task_keys: Sequence[H.HpkeKeypair],
-                 global_keys: Sequence[H.HpkeKeypair] = (), role: int = H.ROLE_LEADER):
+                 global_keys: Sequence[H.HpkeKeypair] = (), role: int = H.ROLE_LEADER,
+                 team_chacha: bool = False):
         if len(task_id) != 32:
             raise ValueError("TaskId is 32 bytes")
         if role not in (H.ROLE_LEADER, H.ROLE_HELPER):
             raise ValueError("an input share is sealed to the leader or to the helper")
+        self.team_chacha = bool(team_chacha)
+        if self.team_chacha:
+            vdaf.set_option("hpke_team_chacha", 1)
         self.vdaf, self.task_id, self.role = vdaf, bytes(task_id), role
         self.task_keys, self.global_keys = {}, {}
         for table, kps in ((self.task_keys, task_keys), (self.global_keys, global_keys)):
@@ -170,7 +179,7 @@ class UploadBatch:
             first[int(cid)] = kp
             if kp is None:
                 status[idx] = ST_UNKNOWN_CONFIG
-            elif _gpu_suite(kp.config):
+            elif _gpu_suite(kp.config, self.team_chacha):
                 self._open_group(kp, reports, idx, ids, times, rows, status)
             else:
                 self._host_rows(lambda i, kp=kp: kp, reports, idx, times, rows, status)

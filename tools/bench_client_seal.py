@@ -16,7 +16,11 @@ the lane-per-report seal over the same device rows, alternating, outputs asserte
 leader share, the helper share, a sweep of share lengths with the threshold it gives for
 ClientBatch.LONG_SEAL_MIN_SHARE, and prepare_reports under long_seal=False and auto.
 
-  python tools/bench_client_seal.py --long [--threshold-from-sweep] [--out FILE.jsonl]
+  python tools/bench_client_seal.py --long [--aead {1,2,3}] [--threshold-from-sweep] [--out FILE.jsonl]
+
+--aead picks both aggregators' AEAD under --long (1 AES-128-GCM, the default; 2 AES-256-GCM; 3
+ChaCha20-Poly1305, which sets the context option "hpke_team_chacha" and has its own threshold,
+ClientBatch.LONG_SEAL_MIN_SHARE_CHACHA).
 """
 import argparse
 import ctypes
@@ -171,8 +175,10 @@ def long_main(args, v, lkp, hkp, rng, dev):
     (b) the helper share, (c) a length sweep and the threshold it gives, (d) prepare_reports with
     long_seal=False and auto."""
     s = v.sizes
+    aead = {1: "AES-128-GCM", 2: "AES-256-GCM", 3: "ChaCha20-Poly1305"}[args.aead]
+    attr = "LONG_SEAL_MIN_SHARE_CHACHA" if args.aead == 3 else "LONG_SEAL_MIN_SHARE"
     out = {"what": "client seal on one GPU, a wave per report beside a lane per report: X25519 / "
-                   "HKDF-SHA256 / AES-128-GCM seals of Prio3 input shares from device rows, the "
+                   f"HKDF-SHA256 / {aead} seals of Prio3 input shares from device rows, the "
                    "two paths alternating over the same inputs (outputs asserted equal), host "
                    "clock around a synchronise, median of reps with min..max; and whole "
                    "Prio3SumVec(8, 1000, 89) reports under long_seal=False and auto",
@@ -191,17 +197,18 @@ def long_main(args, v, lkp, hkp, rng, dev):
             break
         threshold = case["share_bytes"]
     out["c_threshold"] = threshold
-    out["configured_long_seal_min_share"] = ClientBatch.LONG_SEAL_MIN_SHARE
+    out["configured_long_seal_min_share"] = getattr(ClientBatch, attr)
     if args.threshold_from_sweep:
-        ClientBatch.LONG_SEAL_MIN_SHARE = threshold
+        setattr(ClientBatch, attr, threshold)
     n = args.reports_n
     meas = rng.integers(0, 256, (n, 1000), dtype=np.int64)
     ids = rng.integers(0, 256, (n, 16), dtype=np.uint8)
     rand = rng.integers(0, 256, (n, v.random_size()), dtype=np.uint8)
     sk = rng.integers(0, 256, (2, n, 32), dtype=np.uint8)
     times = np.full(n, 1_700_000_000, np.uint64)
+    chacha = args.aead == 3
     cbs = {"lane": ClientBatch(v, TASK_ID, lkp.config, hkp.config, 3600, long_seal=False),
-           "auto": ClientBatch(v, TASK_ID, lkp.config, hkp.config, 3600)}
+           "auto": ClientBatch(v, TASK_ID, lkp.config, hkp.config, 3600, team_chacha=chacha)}
 
     def prepare(k):
         r = cbs[k].prepare_reports(meas, report_ids=ids, times=times, rand=rand, sk_es=sk,
@@ -219,7 +226,7 @@ def long_main(args, v, lkp, hkp, rng, dev):
             prepare(k)
             secs[k].append(time.perf_counter() - t)
     d = {"n": n, "report_bytes": cbs["lane"].report_len,
-         "auto_min_share": ClientBatch.LONG_SEAL_MIN_SHARE,
+         "auto_min_share": getattr(ClientBatch, attr),
          "auto_wave_routes": dict(zip(("leader", "helper"), cbs["auto"]._wave))}
     for k in cbs:
         d[k] = dict(spread(secs[k]), reports_per_s=round(n / statistics.median(secs[k])),
@@ -241,15 +248,22 @@ def main():
     ap.add_argument("--threshold-from-sweep", action="store_true",
                     help="with --long: auto in prepare_reports routes by the threshold this run's "
                          "sweep gives, not by ClientBatch.LONG_SEAL_MIN_SHARE")
+    ap.add_argument("--aead", type=int, choices=(1, 2, 3), default=1,
+                    help="with --long: both aggregators' AEAD; 3 (ChaCha20-Poly1305) sets the "
+                         'context option "hpke_team_chacha"')
     ap.add_argument("--out", help="append the JSON line to this file as well")
     args = ap.parse_args()
     if args.long:
         rng = np.random.default_rng(2026)
         vk = hashlib.shake_128(b"verify-key client seal").digest(16)
         v = Prio3Gpu.new_sum_vec(8, 1000, 89, vk, device=0)
-        line = json.dumps(long_main(args, v, H.generate_hpke_config_and_private_key(1),
-                                    H.generate_hpke_config_and_private_key(2), rng,
-                                    torch.device("cuda", 0)))
+        if args.aead == 3:
+            v.set_option("hpke_team_chacha", 1)
+        X = H.KEM_X25519_HKDF_SHA256
+        line = json.dumps(long_main(args, v,
+                                    H.generate_hpke_config_and_private_key(1, X, 1, args.aead),
+                                    H.generate_hpke_config_and_private_key(2, X, 1, args.aead),
+                                    rng, torch.device("cuda", 0)))
         v.close()
         print(line, flush=True)
         if args.out:

@@ -2,7 +2,8 @@
 (hpke.open_input_shares_gpu, k_hpke_open_team_shares) and, alternating in the same run, the same
 ciphertexts through the lane-per-report prio3gpu_hpke_open_batch (k_hpke_open), the baseline.
 
-Two cases under X25519 / HKDF-SHA256 / AES-128-GCM, rows in device memory:
+Two cases under X25519 / HKDF-SHA256 / AES-128-GCM (--aead 2: AES-256-GCM; --aead 3:
+ChaCha20-Poly1305, with the context options the two GPU paths need for it), rows in device memory:
   leader   --leader-n payloads of a SumVec(8, 1000) leader share (134,966 bytes each)
   helper   --helper-n payloads of a helper share with joint randomness (70 bytes each)
 Shares are random bytes sealed on the GPU (hpke.seal_input_shares_gpu); both paths must give them
@@ -10,7 +11,10 @@ back.  Times are a host clock around a device synchronise, after one warm-up cal
 the median of --reps with min..max, and the per-kernel HIP-event times of one call.  One JSON line
 per case, printed and appended to --out.
 
-  python tools/bench_upload_open.py [--leader-n 4096] [--helper-n 65536] [--reps 3]
+The first --host-n reports are also opened once by the host's hpke.open_ loop, the route
+UploadBatch takes for a suite it does not give to the GPU.
+
+  python tools/bench_upload_open.py [--leader-n 4096] [--helper-n 65536] [--reps 3] [--aead 3]
 """
 import argparse
 import ctypes
@@ -55,7 +59,7 @@ def spread(xs):
             "max": round(max(xs), 3)}
 
 
-def open_case(v, kp, case, n, slen, reps, rng, dev):
+def open_case(v, kp, case, n, slen, reps, rng, dev, host_n=0):
     role = H.ROLE_LEADER
     plen = 6 + slen + 16
     ids = rng.integers(0, 256, (n, 16), dtype=np.uint8)
@@ -116,8 +120,19 @@ def open_case(v, kp, case, n, slen, reps, rng, dev):
         lane_call()
         lane_ms.append(1e3 * (time.perf_counter() - t))
     tm, lm = statistics.median(team_ms), statistics.median(lane_ms)
-    return {"case": case, "suite": "X25519 / HKDF-SHA256 / AES-128-GCM", "n": n,
-            "payload_bytes": plen, "reps": reps,
+    # UploadBatch's host route for a suite the wave does not take: hpke.open_ report by report
+    host_n = min(host_n, n)
+    h_enc, h_pay = d_encs[:host_n].cpu().numpy(), d_pay[:host_n].cpu().numpy()
+    h_shares = d_shares[:host_n].cpu().numpy()
+    t = time.perf_counter()
+    for i in range(host_n):
+        pt = H.open_(kp, info, h_enc[i].tobytes(), h_pay[i].tobytes(), aad[i].tobytes())
+        assert pt[6:] == h_shares[i].tobytes()
+    host_ms = 1e3 * (time.perf_counter() - t)
+    aead = {1: "AES-128-GCM", 2: "AES-256-GCM", 3: "ChaCha20-Poly1305"}[kp.config.aead_id]
+    return {"case": case, "suite": "X25519 / HKDF-SHA256 / " + aead, "n": n,
+            "payload_bytes": plen, "reps": reps, "host_loop_n": host_n,
+            "host_loop_opens_per_s": round(host_n / host_ms * 1e3) if host_n else None,
             "wave_per_report_ms": spread(team_ms), "lane_per_report_ms": spread(lane_ms),
             "wave_opens_per_s": round(n / tm * 1e3), "lane_opens_per_s": round(n / lm * 1e3),
             "wave_gb_per_s": round(n * plen / tm / 1e6, 2),
@@ -131,18 +146,27 @@ def main():
     ap.add_argument("--leader-n", type=int, default=4096)
     ap.add_argument("--helper-n", type=int, default=65536)
     ap.add_argument("--reps", type=int, default=3)
+    ap.add_argument("--aead", type=int, choices=(1, 2, 3), default=1,
+                    help="the key's AEAD; 2 and 3 set \"hpke_gpu_suites\" for the lane path, 3 "
+                         "(ChaCha20-Poly1305) also \"hpke_team_chacha\" for the wave path")
+    ap.add_argument("--host-n", type=int, default=256,
+                    help="reports of the host's open loop, once (0: none)")
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "upload_open",
                                                   "bench_upload_open.jsonl"))
     args = ap.parse_args()
     dev = torch.device("cuda", 0)
     rng = np.random.default_rng(2026)
     v = Prio3Gpu.new_count(bytes(16), device=0)
-    kp = H.generate_hpke_config_and_private_key(1)
+    if args.aead != 1:
+        v.set_option("hpke_gpu_suites", 1)
+    if args.aead == 3:
+        v.set_option("hpke_team_chacha", 1)
+    kp = H.generate_hpke_config_and_private_key(1, H.KEM_X25519_HKDF_SHA256, 1, args.aead)
     os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
     for case, n, slen in (("leader", args.leader_n, 134_944), ("helper", args.helper_n, 48)):
         if n <= 0:
             continue
-        line = json.dumps(open_case(v, kp, case, n, slen, args.reps, rng, dev))
+        line = json.dumps(open_case(v, kp, case, n, slen, args.reps, rng, dev, args.host_n))
         print(line, flush=True)
         with open(args.out, "a") as f:
             f.write(line + "\n")
