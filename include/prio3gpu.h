@@ -174,7 +174,12 @@ int prio3gpu_ctx_set_async(prio3gpu_ctx* ctx, int on);
  *   "hpke_gpu_p256"  0 (default): DHKEM(P-256, HKDF-SHA256) (KEM 0x0010) keys are opened on the
  *                   host.  1: the GPU opens them too (k_p256_dh): 0x0010 / 1 / 1 with this option
  *                   alone, all nine 0x0010 / KDF 1-3 / AEAD 1-3 with "hpke_gpu_suites" = 1 as
- *                   well.  Independent of "hpke_gpu_suites".  Any other value is PRIO3GPU_E_ARG
+ *                   well.  Independent of "hpke_gpu_suites".  1 also lets the seal entry points
+ *                   (prio3gpu_hpke_seal_batch, prio3gpu_seal_input_shares and their _long forms)
+ *                   and the wave-per-report opens (prio3gpu_hpke_open_long_batch,
+ *                   prio3gpu_open_input_shares) take KEM 0x0010 with the KDFs and AEADs they take
+ *                   under X25519 (k_p256_eph, k_p256_eph_kem; k_p256_dh); at 0 they answer
+ *                   PRIO3GPU_E_UNSUPPORTED for it.  Any other value is PRIO3GPU_E_ARG
  *   "hpke_team_chacha"  0 (default): the wave-per-report entry points (prio3gpu_hpke_open_long_batch,
  *                   prio3gpu_open_input_shares, prio3gpu_hpke_seal_long_batch,
  *                   prio3gpu_seal_input_shares_long) take AES-GCM only and answer
@@ -584,22 +589,27 @@ int prio3gpu_hpke_open_report_shares_gpu(prio3gpu_ctx* ctx, const uint8_t* task_
 /* ---- HPKE seal on the GPU (janus_amd/csrc/hpke_seal_gpu.h) -------------------------------------
  * n seals to ONE recipient key, one GPU lane per report, each under its own ephemeral key: the
  * batched hpke::seal (core/src/hpke.rs:158-182).  Suites: DHKEM(X25519, HKDF-SHA256) (KEM 0x0020)
- * with KDF 1-3 and AEAD 1-3, no context option needed.  KEM 0x0010 (P-256) or an unknown KDF or
- * AEAD is PRIO3GPU_E_UNSUPPORTED with nothing launched: P-256 seals stay on the host's
- * prio3gpu_hpke_seal.  pk_len other than 32 is PRIO3GPU_E_ARG; n == 0 returns 0 and launches
- * nothing.  pk and info are host memory; every other pointer may be host or device (detected).
- * Report i is sealed under the ephemeral private key sk_es[32 i .. 32 i + 32) with
+ * with KDF 1-3 and AEAD 1-3, no context option needed, and with the context option
+ * "hpke_gpu_p256" = 1 DHKEM(P-256, HKDF-SHA256) (KEM 0x0010) with the same KDFs and AEADs.  KEM
+ * 0x0010 while that option is 0 (such seals stay on the host's prio3gpu_hpke_seal) or an unknown
+ * KDF or AEAD is PRIO3GPU_E_UNSUPPORTED with nothing launched.  pk_len other than Nenc -- 32 for
+ * X25519, 65 for P-256 (an uncompressed point) -- is PRIO3GPU_E_ARG; a P-256 pk that
+ * DeserializePublicKey refuses (not 0x04 || x || y, a coordinate >= p, off the curve) is
+ * PRIO3GPU_E_HPKE with nothing launched; n == 0 returns 0 and launches nothing.  pk and info are
+ * host memory; every other pointer may be host or device (detected).
+ * Report i is sealed under the ephemeral private key sk_es[32 i .. 32 i + 32) (X25519: clamped
+ * inside; P-256: a big-endian scalar, which must lie in [1, n)) with
  * aad = aads[aad_offsets[i] .. aad_offsets[i+1]) and plaintext = pts[pt_offsets[i] ..
- * pt_offsets[i+1]); its encapsulated key goes to encs[32 i .. 32 i + 32) and its ciphertext || tag
- * to cts[ct_offsets[i] .. ct_offsets[i+1]) (room for the plaintext length + 16; a longer slot is
+ * pt_offsets[i+1]); its encapsulated key goes to encs[Nenc i .. Nenc i + Nenc) and its
+ * ciphertext || tag to cts[ct_offsets[i] .. ct_offsets[i+1]) (room for the plaintext length + 16; a longer slot is
  * zero-filled).  The bytes are those of prio3gpu_hpke_seal with the same sk_e.
  * status in/out: non-zero on entry = skipped; a report that is not sealed -- skipped, an all-zero
  * DH value (pk of small order, RFC 9180 §7.1.4; prio3gpu_hpke_seal returns PRIO3GPU_E_HPKE
- * there), a slot shorter than the plaintext + 16, offsets that do not fit -- gets zeros in its
+ * there), a P-256 ephemeral scalar outside [1, n) (PRIO3GPU_E_HPKE there too), a slot shorter than the plaintext + 16, offsets that do not fit -- gets zeros in its
  * enc and ciphertext slots and, unless it was skipped, status 4 (PRIO3GPU_HPKE_DECRYPT_ERROR, the
  * ABI's one per-report HPKE failure).
  * Secrets: the engine's device copies of the ephemeral keys and of the plaintexts, and the buffer
- * of the per-report DH values, are zeroed before the call returns, on the error paths too; keys
+ * of the per-report DH values (P-256: shared secrets and validity bytes), are zeroed before the call returns, on the error paths too; keys
  * and nonces never leave registers.  Scratch belongs to the context (see prio3gpu_state_create). */
 int prio3gpu_hpke_seal_batch(prio3gpu_ctx* ctx, uint16_t kem_id, uint16_t kdf_id, uint16_t aead_id,
                              const uint8_t* pk, size_t pk_len, const uint8_t* info,
@@ -614,7 +624,8 @@ int prio3gpu_hpke_seal_batch(prio3gpu_ctx* ctx, uint16_t kem_id, uint16_t kdf_id
  * report_ids[16 i ..], times[i] (u64, seconds; encoded big-endian) and public_shares[i
  * public_share_len ..] with its u32 length prefix; both are read from the caller's rows lane by
  * lane and never written to memory.  info = "dap-07 input share" || Client || recipient_role.
- * Report i's encapsulated key (32 bytes) goes to out_encs + i enc_pitch and its payload, exactly
+ * Report i's encapsulated key (Nenc bytes: 32, or 65 for KEM 0x0010, at any alignment) goes to
+ * out_encs + i enc_pitch and its payload, exactly
  * 6 + input_share_len + 16 bytes, to out_payloads + i payload_pitch; no other byte of either
  * buffer is written, so both may be columns of one fixed-stride Report buffer.  A pitch of 0 is
  * the packed one (the row's own length); a pitch shorter than its row is PRIO3GPU_E_ARG.
@@ -636,9 +647,12 @@ int prio3gpu_seal_input_shares(prio3gpu_ctx* ctx, const uint8_t* task_id, uint16
  * input share of a hundred kilobytes (aggregator.rs:1325-1497), where a lane per report would walk
  * each ciphertext alone.  Suites: DHKEM(X25519, HKDF-SHA256) (KEM 0x0020) with KDF 1-3 and
  * AES-128-GCM / AES-256-GCM (AEAD 1, 2), no context option needed, and with the context option
- * "hpke_team_chacha" = 1 ChaCha20-Poly1305 (AEAD 3) too.  KEM 0x0010 (P-256), AEAD 3 while that
- * option is 0, or an unknown id is PRIO3GPU_E_UNSUPPORTED with nothing launched; n == 0 returns 0
- * and launches nothing.
+ * "hpke_team_chacha" = 1 ChaCha20-Poly1305 (AEAD 3) too; with "hpke_gpu_p256" = 1 the same under
+ * DHKEM(P-256, HKDF-SHA256) (KEM 0x0010: k_p256_dh, then the same wave per report).  KEM 0x0010 or
+ * AEAD 3 while its option is 0, or an unknown id, is PRIO3GPU_E_UNSUPPORTED with nothing launched;
+ * n == 0 returns 0 and launches nothing.  sk is 32 bytes; pk and every enc are Nenc bytes, 32 for
+ * X25519 and 65 for KEM 0x0010; another length is PRIO3GPU_E_ARG, and a P-256 keypair whose scalar
+ * is not in [1, n) or whose public key is no point is PRIO3GPU_E_HPKE before any launch.
  * prio3gpu_hpke_open_long_batch has the arguments and contracts of prio3gpu_hpke_open_batch --
  * host or device pointers, status in/out, zero-filled slots, zeros and status 4 for a failed
  * open, the handling of secrets -- and the same plaintexts, for every ciphertext length from 16
@@ -654,7 +668,8 @@ int prio3gpu_hpke_open_long_batch(prio3gpu_ctx* ctx, uint16_t kem_id, uint16_t k
  * decode, aggregator.rs:1325-1497), the mirror of prio3gpu_seal_input_shares, a wave per report
  * and for the suites above (AEAD 3 with "hpke_team_chacha" = 1, PRIO3GPU_E_UNSUPPORTED without
  * it).  Report i's
- * encapsulated key (32 bytes) is read from encs + i enc_pitch and its payload, exactly
+ * encapsulated key (Nenc bytes: 32, or 65 for KEM 0x0010) is read from encs + i enc_pitch and
+ * its payload, exactly
  * 6 + input_share_len + 16 bytes, from payloads + i payload_pitch, so both may be columns of one
  * fixed-stride Report buffer; its AAD is the InputShareAad of task_id, report_ids[16 i ..],
  * times[i] and public_shares[i public_share_len ..], never written to memory;
@@ -665,7 +680,7 @@ int prio3gpu_hpke_open_long_batch(prio3gpu_ctx* ctx, uint16_t kem_id, uint16_t k
  * prio3gpu_state_set_input_pitch, prio3gpu_prepare_init reads the rows in place.  A pitch of 0 is
  * the packed one (the row's own length); a pitch shorter than its row is PRIO3GPU_E_ARG.
  * status in/out: non-zero on entry = skipped (the row is zeroed); a failed open (bad tag, an
- * all-zero DH value) sets 4 and writes zeros; an authentic plaintext with any other six leading
+ * all-zero X25519 DH value, a P-256 enc that is no valid point) sets 4 and writes zeros; an authentic plaintext with any other six leading
  * bytes -- extensions, another length: at this payload length either means a share of the wrong
  * size -- sets 8 (InvalidMessage, "Leader input share decoding failed") and writes zeros.
  * task_id, sk and pk are host memory; every other pointer may be host or device (detected).
@@ -687,9 +702,10 @@ int prio3gpu_open_input_shares(prio3gpu_ctx* ctx, const uint8_t* task_id, uint16
  * walk each plaintext alone; the mirror of prio3gpu_hpke_open_long_batch.  Suites:
  * DHKEM(X25519, HKDF-SHA256) (KEM 0x0020) with KDF 1-3 and AES-128-GCM / AES-256-GCM (AEAD 1, 2),
  * no context option needed, and with the context option "hpke_team_chacha" = 1
- * ChaCha20-Poly1305 (AEAD 3) too.  KEM 0x0010 (P-256), AEAD 3 while that option is 0 (it stays on
- * prio3gpu_hpke_seal_batch) or an unknown id is PRIO3GPU_E_UNSUPPORTED with nothing launched;
- * n == 0 returns 0 and launches nothing.
+ * ChaCha20-Poly1305 (AEAD 3) too; with "hpke_gpu_p256" = 1 the same under DHKEM(P-256,
+ * HKDF-SHA256) (KEM 0x0010), pk and encs as prio3gpu_hpke_seal_batch takes them.  AEAD 3 while its
+ * option is 0 (it stays on prio3gpu_hpke_seal_batch), KEM 0x0010 while its option is 0, or an
+ * unknown id is PRIO3GPU_E_UNSUPPORTED with nothing launched; n == 0 returns 0 and launches nothing.
  * prio3gpu_hpke_seal_long_batch has the arguments and contracts of prio3gpu_hpke_seal_batch --
  * host or device pointers, status in/out, zero-filled slots, zeros and status 4 for a report that
  * is not sealed, the handling of secrets (round keys too never leave registers; the wave's table

@@ -58,6 +58,17 @@ int prio3gpu_test_x25519_gpu(prio3gpu_ctx* ctx, const uint8_t* sk, const uint8_t
 int prio3gpu_test_p256_gpu(prio3gpu_ctx* ctx, const uint8_t* sk, const uint8_t* points, size_t n,
                            uint8_t* out_x, uint8_t* ok);
 
+/* TEST ONLY.  The GPU seal's P-256 ladders alone (k_p256_eph without the KEM half that follows it,
+ * two lanes per report), the counterpart of prio3gpu_test_p256_gpu for the sender: for n 32-byte
+ * big-endian ephemeral scalars sk_es under one recipient key pk65 (0x04 || x || y),
+ * out_enc[65 i .. 65 i + 65) is enc = 0x04 || x || y of [sk_e_i] G, out_dh_x[32 i .. 32 i + 32)
+ * the big-endian x coordinate of [sk_e_i] pk, and ok[i] = 1 -- or zeros in both and ok[i] = 0 for
+ * a scalar outside [1, n).  An all-zero x with ok[i] = 1 is a result, not a failure.  A pk65 that
+ * DeserializePublicKey refuses returns PRIO3GPU_E_HPKE and launches nothing.  All host memory;
+ * n == 0 returns 0 and launches nothing. */
+int prio3gpu_test_p256_eph_gpu(prio3gpu_ctx* ctx, const uint8_t* pk65, const uint8_t* sk_es,
+                               size_t n, uint8_t* out_enc, uint8_t* out_dh_x, uint8_t* ok);
+
 /* TEST ONLY.  The device Poly1305 (janus_amd/csrc/hpke_prims.h: poly1305_mac, RFC 8439 §2.5) alone,
  * one lane per message: tags[16 i .. 16 i + 16) is the MAC of msgs[msg_offsets[i] ..
  * msg_offsets[i + 1]) under keys[32 i .. 32 i + 32) (r || s; r is clamped inside).  The HPKE-level

@@ -234,6 +234,7 @@ def _declare(lib):
                                                    c.c_size_t, P, u8p, u8p, u8p, P, c.c_int]),
         "prio3gpu_test_x25519_gpu": (c.c_int, [P, u8p, u8p, c.c_size_t, u8p]),
         "prio3gpu_test_p256_gpu": (c.c_int, [P, u8p, u8p, c.c_size_t, u8p, u8p]),
+        "prio3gpu_test_p256_eph_gpu": (c.c_int, [P, u8p, u8p, c.c_size_t, u8p, u8p, u8p]),
         "prio3gpu_test_poly1305_gpu": (c.c_int, [P, u8p, u8p, P, c.c_size_t, u8p]),
         "prio3gpu_test_req_gather": (c.c_int, [P, u8p, c.c_size_t, P, c.c_size_t, u8p, u8p, u8p,
                                                u8p]),
@@ -279,7 +280,7 @@ TEST_EXPORTED = [
     "prio3gpu_test_squeeze", "prio3gpu_test_flp_query", "prio3gpu_dev_alloc", "prio3gpu_dev_free",
     "prio3gpu_memcpy", "prio3gpu_test_hpke_set_ifma", "prio3gpu_test_x25519_gpu",
     "prio3gpu_test_field_op", "prio3gpu_test_req_gather", "prio3gpu_test_poly1305_gpu",
-    "prio3gpu_test_p256_gpu",
+    "prio3gpu_test_p256_gpu", "prio3gpu_test_p256_eph_gpu",
 ]
 
 

@@ -10,7 +10,7 @@ are the fields of messages/src/lib.rs's `Report`:
 
   ReportMetadata   report_id[16] | time u64
   public_share     u32 length | bytes
-  HpkeCiphertext   config_id u8 | u16 length (32) | enc[32] | u32 length | payload     (leader)
+  HpkeCiphertext   config_id u8 | u16 length | enc[32 or 65] | u32 length | payload    (leader)
   HpkeCiphertext   the same                                                            (helper)
   payload = AEAD(PlaintextInputShare = 00 00 | u32 length | input share) || tag[16]
 
@@ -27,7 +27,9 @@ import numpy as np
 
 from . import hpke as H
 
-ENC_LEN = 32        # Nenc of DHKEM(X25519, HKDF-SHA256), the KEM the GPU seals to
+ENC_LEN = 32        # Nenc of DHKEM(X25519, HKDF-SHA256), the KEM the GPU seals to by default
+# The order n of P-256's group: an ephemeral private key is a scalar in [1, n) (RFC 9180 §7.1.3)
+P256_ORDER = 0xffffffff00000000ffffffffffffffffbce6faada7179e84f3b9cac2fc632551
 TAG_LEN = 16
 PLAINTEXT_OVERHEAD = 6   # empty extension list (u16) + payload length (u32)
 
@@ -103,11 +105,14 @@ def _like(dst, a: np.ndarray):
 
 class ReportLayout:
     """Column offsets of the fixed-stride Report matrix for given public-share and input-share
-    lengths (X25519 encapsulated keys)."""
+    lengths; `leader_enc` / `helper_enc` are the lengths of the two encapsulated keys, 32
+    (X25519, the default) or 65 (P-256)."""
 
-    def __init__(self, public_share: int, leader_share: int, helper_share: int):
+    def __init__(self, public_share: int, leader_share: int, helper_share: int,
+                 leader_enc: int = ENC_LEN, helper_enc: int = ENC_LEN):
         self.public_share, self.leader_share, self.helper_share = (public_share, leader_share,
                                                                    helper_share)
+        self.leader_enc, self.helper_enc = int(leader_enc), int(helper_enc)
         self.leader_payload = PLAINTEXT_OVERHEAD + leader_share + TAG_LEN
         self.helper_payload = PLAINTEXT_OVERHEAD + helper_share + TAG_LEN
         o = 0
@@ -115,22 +120,24 @@ class ReportLayout:
         self.o_time, o = o, o + 8
         self.o_public_len, o = o, o + 4
         self.o_public, o = o, o + public_share
-        self.o_leader = o                          # config id, 00 20, enc, u32 length, payload
+        self.o_leader = o                  # config id, 00 20 / 00 41, enc, u32 length, payload
         self.o_leader_enc = o + 3
-        self.o_leader_payload = o + 3 + ENC_LEN + 4
+        self.o_leader_payload = o + 3 + self.leader_enc + 4
         o = self.o_leader_payload + self.leader_payload
         self.o_helper = o
         self.o_helper_enc = o + 3
-        self.o_helper_payload = o + 3 + ENC_LEN + 4
+        self.o_helper_payload = o + 3 + self.helper_enc + 4
         self.report_len = self.o_helper_payload + self.helper_payload
-        assert self.report_len == (16 + 8 + 4 + public_share + 2 * (1 + 2 + 32 + 4 + 6 + 16)
-                                   + leader_share + helper_share)
+        assert self.report_len == (16 + 8 + 4 + public_share + 2 * (1 + 2 + 4 + 6 + 16)
+                                   + self.leader_enc + self.helper_enc + leader_share
+                                   + helper_share)
 
     def write_fixed(self, reports, report_ids: np.ndarray, times: np.ndarray, public_shares,
                     leader_config_id: int, helper_config_id: int) -> None:
         """Everything of `reports` (an (n, report_len) uint8 numpy array or torch tensor) except
         the enc and payload columns: metadata, the public share with its length prefix, the
-        config ids and the `00 20` / u32 length prefixes of both ciphertexts.  `public_shares`:
+        config ids and the `00 20` (`00 41` for a 65-byte enc) / u32 length prefixes of both
+        ciphertexts.  `public_shares`:
         (n, public_share) rows of the same kind as `reports`, or None when there are none."""
         n = reports.shape[0]
         head = np.empty((n, 28), np.uint8)
@@ -140,19 +147,39 @@ class ReportLayout:
         reports[:, :28] = _like(reports, head)
         if self.public_share:
             reports[:, self.o_public:self.o_public + self.public_share] = public_shares
-        for o, cfg, plen in ((self.o_leader, leader_config_id, self.leader_payload),
-                             (self.o_helper, helper_config_id, self.helper_payload)):
-            pre = np.frombuffer(bytes([cfg]) + struct.pack(">H", ENC_LEN), np.uint8)
+        for o, cfg, plen, ne in (
+                (self.o_leader, leader_config_id, self.leader_payload, self.leader_enc),
+                (self.o_helper, helper_config_id, self.helper_payload, self.helper_enc)):
+            pre = np.frombuffer(bytes([cfg]) + struct.pack(">H", ne), np.uint8)
             reports[:, o:o + 3] = _like(reports, pre)
             ln = np.frombuffer(struct.pack(">I", plen), np.uint8)
-            reports[:, o + 3 + ENC_LEN:o + 3 + ENC_LEN + 4] = _like(reports, ln)
+            reports[:, o + 3 + ne:o + 3 + ne + 4] = _like(reports, ln)
 
     def columns(self, reports, which: str):
         """(enc column, payload column) views of `reports` for "leader" or "helper"."""
-        oe, op, pl = ((self.o_leader_enc, self.o_leader_payload, self.leader_payload)
-                      if which == "leader" else
-                      (self.o_helper_enc, self.o_helper_payload, self.helper_payload))
-        return reports[:, oe:oe + ENC_LEN], reports[:, op:op + pl]
+        oe, op, pl, ne = ((self.o_leader_enc, self.o_leader_payload, self.leader_payload,
+                           self.leader_enc) if which == "leader" else
+                          (self.o_helper_enc, self.o_helper_payload, self.helper_payload,
+                           self.helper_enc))
+        return reports[:, oe:oe + ne], reports[:, op:op + pl]
+
+
+def draw_p256_scalars(n: int, rand=os.urandom) -> np.ndarray:
+    """n ephemeral P-256 private keys as (n, 32) big-endian bytes, each in [1, n): a draw of 0 or
+    >= the group order is drawn again (RFC 9180 §7.1.3's rejection sampling; about one draw in
+    2^32 is refused).  `rand(k)` gives k random bytes."""
+    out = np.frombuffer(rand(32 * n), np.uint8).reshape(n, 32).copy()
+    # k < n word by word from the top, for all rows at once; the rare refused row is redrawn alone
+    words = out.view(">u8").reshape(n, 4)
+    order = np.frombuffer(P256_ORDER.to_bytes(32, "big"), ">u8")
+    below, equal = np.zeros(n, bool), np.ones(n, bool)
+    for j in range(4):
+        below |= equal & (words[:, j] < order[j])
+        equal &= words[:, j] == order[j]
+    for i in np.flatnonzero(~(below & out.any(axis=1))):
+        while not 1 <= int.from_bytes(out[i].tobytes(), "big") < P256_ORDER:
+            out[i] = np.frombuffer(rand(32), np.uint8)
+    return out
 
 
 def round_times(times, time_precision: int) -> np.ndarray:
@@ -163,7 +190,8 @@ def round_times(times, time_precision: int) -> np.ndarray:
 
 class ClientBatch:
     """The batched `Client` of one task: `vdaf` a `Prio3Gpu`, the two aggregators' `HpkeConfig`s
-    (DHKEM(X25519, HKDF-SHA256) with any KDF and AEAD) and the task's time precision in seconds.
+    (DHKEM(X25519, HKDF-SHA256), or with `p256` DHKEM(P-256, HKDF-SHA256) too, with any KDF and
+    AEAD) and the task's time precision in seconds.
 
     `long_seal` picks the seal's kernels per aggregator; the report bytes never depend on it.
     False: a GPU lane per report (`hpke.seal_input_shares_gpu`).  True: a wave per report
@@ -174,7 +202,13 @@ class ClientBatch:
     `team_chacha` sets the option "hpke_team_chacha" on `vdaf`'s context, with which the wave per
     report takes ChaCha20-Poly1305 too: `long_seal=True` is then allowed for such configs, and
     under `long_seal=None` such a config takes the wave from `LONG_SEAL_MIN_SHARE_CHACHA` bytes
-    on.  Without it a ChaCha20-Poly1305 config is sealed a lane per report, as before."""
+    on.  Without it a ChaCha20-Poly1305 config is sealed a lane per report, as before.
+
+    `p256` sets the option "hpke_gpu_p256" on `vdaf`'s context and admits P-256 configs: such an
+    aggregator's encapsulated keys are 65 bytes (`layout`), its ephemeral private keys are drawn
+    in [1, n) (`draw_p256_scalars`), and a caller's `sk_es` outside that range raise `HpkeError`.
+    The `long_seal` rules do not change: the AEAD decides, the ladders cost the same on both
+    paths.  Without it a P-256 config is a `ValueError`, as before."""
 
     # The shortest input share from which the wave-per-report seal is measured to win at every
     # longer length too: the Sum32 leader share, 1.7x at 4,096 reports; at 1,024 bytes the lane per
@@ -191,14 +225,17 @@ class ClientBatch:
 
     def __init__(self, vdaf, task_id: bytes, leader_config: H.HpkeConfig,
                  helper_config: H.HpkeConfig, time_precision: int,
-                 long_seal: Optional[bool] = None, team_chacha: bool = False):
+                 long_seal: Optional[bool] = None, team_chacha: bool = False,
+                 p256: bool = False):
         if len(task_id) != 32:
             raise ValueError("TaskId is 32 bytes")
         if time_precision <= 0:
             raise ValueError("time precision must be positive")
         for c in (leader_config, helper_config):
-            if c.kem_id != H.KEM_X25519_HKDF_SHA256:
-                raise ValueError("the GPU seals to DHKEM(X25519, HKDF-SHA256) configs only")
+            if c.kem_id != H.KEM_X25519_HKDF_SHA256 and \
+                    not (p256 and c.kem_id == H.KEM_P256_HKDF_SHA256):
+                raise ValueError("the GPU seals to DHKEM(X25519, HKDF-SHA256) configs only"
+                                 + ("" if p256 else ", or with p256=True to P-256 ones"))
         # per aggregator, the shortest share a wave per report seals under long_seal=None (None:
         # never), or False where the wave does not take the AEAD at all
         floors = [self.LONG_SEAL_MIN_SHARE
@@ -211,6 +248,8 @@ class ClientBatch:
                              "ChaCha20-Poly1305 ones with team_chacha=True")
         if team_chacha:
             vdaf.set_option("hpke_team_chacha", 1)
+        if p256:
+            vdaf.set_option("hpke_gpu_p256", 1)
         s = vdaf.sizes
         # (leader, helper): whether a wave per report seals that aggregator's shares
         self._wave = tuple(
@@ -220,7 +259,8 @@ class ClientBatch:
         self.vdaf, self.task_id = vdaf, bytes(task_id)
         self.leader_config, self.helper_config = leader_config, helper_config
         self.time_precision = int(time_precision)
-        self.layout = ReportLayout(s.public_share, s.leader_input_share, s.helper_input_share)
+        self.layout = ReportLayout(s.public_share, s.leader_input_share, s.helper_input_share,
+                                   H.enc_len(leader_config.kem_id), H.enc_len(helper_config.kem_id))
         self.report_len = self.layout.report_len
         self._state = None
 
@@ -241,7 +281,8 @@ class ClientBatch:
         `Prio3Gpu.shard` takes them) -> the (n, report_len) uint8 matrix of their encoded
         Reports (a numpy array; with `device_out` the torch tensor on the GPU it was built in).
         report_ids (n, 16), rand (n, vdaf.random_size()) and sk_es (2, n, 32: the leader's and the
-        helper's ephemeral private keys) default to os.urandom, times (n,) seconds to now; times
+        helper's ephemeral private keys; for a P-256 config big-endian scalars in [1, n)) default
+        to os.urandom (`draw_p256_scalars` for a P-256 config), times (n,) seconds to now; times
         are rounded down to the time precision.  Shares, frames and ciphertexts never leave the
         GPU; only the report matrix is copied back."""
         import torch
@@ -258,8 +299,11 @@ class ClientBatch:
         tm = round_times(np.full(n, int(_time.time())) if times is None else times,
                          self.time_precision)
         rand = rnd((n, v.random_size())) if rand is None else np.asarray(rand, np.uint8)
-        sk = rnd((2, n, 32)) if sk_es is None else \
-            np.ascontiguousarray(sk_es, np.uint8).reshape(2, n, 32)
+        if sk_es is None:
+            sk = np.stack([draw_p256_scalars(n) if c.kem_id == H.KEM_P256_HKDF_SHA256
+                           else rnd((n, 32)) for c in (self.leader_config, self.helper_config)])
+        else:
+            sk = np.ascontiguousarray(sk_es, np.uint8).reshape(2, n, 32)
         reports = torch.zeros((n, L.report_len), dtype=torch.uint8, device=dev)
         if n == 0:
             return reports if device_out else reports.cpu().numpy()
@@ -284,6 +328,7 @@ class ClientBatch:
                             payloads)
             if st[:n].any():
                 raise H.HpkeError(f"sealing to the {which} failed for {int((st[:n] != 0).sum())} "
-                                  "reports (a public key of small order)")
+                                  "reports (a public key of small order, or an ephemeral "
+                                  "P-256 scalar outside [1, n))")
         d_sk.zero_()
         return reports if device_out else reports.cpu().numpy()

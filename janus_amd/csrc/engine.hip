@@ -69,7 +69,7 @@ const char* const kKernelNames[KID_COUNT] = {
     // not a kernel: the request's one host-to-device copy in prio3gpu_helper_init_request
     "copy_request", "k_p256_dh", "k_p256_dh_idx", "k_x25519_eph", "k_hpke_seal",
     "k_hpke_seal_shares", "k_hpke_open_team", "k_hpke_open_team_shares", "k_hpke_seal_team",
-    "k_hpke_seal_team_shares"};
+    "k_hpke_seal_team_shares", "k_p256_eph", "k_p256_eph_kem"};
 
 }  // namespace
 

@@ -193,9 +193,10 @@ void hpke_suite_dispatch(const HpkeBatchConsts& bc, F&& f) {
 
 // The suites the wave-per-report opens and seals take (hpke_open_team.h, hpke_seal_team.h; they
 // have entry points of their own): DHKEM(X25519, HKDF-SHA256) with KDF 1-3 and AES-128-GCM /
-// AES-256-GCM, and with the context's "hpke_team_chacha" option ChaCha20-Poly1305 too.
+// AES-256-GCM, and with the context's "hpke_team_chacha" option ChaCha20-Poly1305 too; with its
+// "hpke_gpu_p256" option the same under DHKEM(P-256, HKDF-SHA256).
 bool hpke_team_suite(const prio3gpu_ctx* c, uint16_t kem, uint16_t kdf, uint16_t aead) {
-  return kem == 0x0020 && kdf >= 1 && kdf <= 3 &&
+  return (kem == 0x0020 || (kem == 0x0010 && c->hpke_gpu_p256)) && kdf >= 1 && kdf <= 3 &&
          (aead == 1 || aead == 2 || (aead == 3 && c->hpke_team_chacha));
 }
 
@@ -622,9 +623,29 @@ int req_clear_secrets(ReqCall& q, int rc) {
 
 // ---- batched HPKE seal on the GPU (hpke_seal_gpu.h) ---------------------------------------------
 // The suites the GPU seals: DHKEM(X25519, HKDF-SHA256) with KDF 1-3 and AEAD 1-3 (no option: the
-// seal has entry points of its own).
-bool hpke_seal_suite(uint16_t kem, uint16_t kdf, uint16_t aead) {
-  return kem == 0x0020 && kdf >= 1 && kdf <= 3 && aead >= 1 && aead <= 3;
+// seal has entry points of its own), and with the context's "hpke_gpu_p256" option the same under
+// DHKEM(P-256, HKDF-SHA256).
+bool hpke_seal_suite(const prio3gpu_ctx* c, uint16_t kem, uint16_t kdf, uint16_t aead) {
+  return (kem == 0x0020 || (kem == 0x0010 && c->hpke_gpu_p256)) && kdf >= 1 && kdf <= 3 &&
+         aead >= 1 && aead <= 3;
+}
+
+// The recipient's public key of a seal entry point: 32 bytes for X25519; for P-256 the 65 bytes
+// of a point DeserializePublicKey takes (p256.h's decoder), checked before anything is launched.
+int seal_pk_check(uint16_t kem_id, const uint8_t* pk, size_t pk_len) {
+  if (!pk || pk_len != hpke_kem_nenc(kem_id)) {
+    set_err("HPKE seal: the public key is %u bytes", hpke_kem_nenc(kem_id));
+    return PRIO3GPU_E_ARG;
+  }
+  if (kem_id == 0x0010) {
+    uint32_t x[8], y[8];
+    Fp256 X, Y;
+    if (!p256_decode(pk, x, y, X, Y)) {
+      set_err("HPKE seal: the public key is not a P-256 point");
+      return PRIO3GPU_E_HPKE;
+    }
+  }
+  return 0;
 }
 
 // The per-report secrets of one seal call on the device: the engine's copies of the ephemeral
@@ -639,14 +660,63 @@ struct SealSecrets {
   size_t eph_bytes = 0;
 };
 
-// Stage the n ephemeral keys and run both ladders of every report: s->d_eph.
-int seal_ladders(prio3gpu_ctx* c, const uint8_t* pk, size_t n, const uint8_t* sk_es,
-                 SealSecrets* s) {
-  CHK(c->seal[1].ensure(n * 64));
+// The generator, as SerializePublicKey writes it
+const uint8_t kP256G[65] = {
+    0x04, 0x6b, 0x17, 0xd1, 0xf2, 0xe1, 0x2c, 0x42, 0x47, 0xf8, 0xbc, 0xe6, 0xe5, 0x63, 0xa4,
+    0x40, 0xf2, 0x77, 0x03, 0x7d, 0x81, 0x2d, 0xeb, 0x33, 0xa0, 0xf4, 0xa1, 0x39, 0x45, 0xd8,
+    0x98, 0xc2, 0x96, 0x4f, 0xe3, 0x42, 0xe2, 0xfe, 0x1a, 0x7f, 0x9b, 0x8e, 0xe7, 0xeb, 0x4a,
+    0x7c, 0x0f, 0x9e, 0x16, 0x2b, 0xce, 0x33, 0x57, 0x6b, 0x31, 0x5e, 0xce, 0xcb, 0xb6, 0x40,
+    0x68, 0x37, 0xbf, 0x51, 0xf5};
+
+// k_p256_eph over n staged ephemeral scalars to the recipient pk (a point: seal_pk_check): the
+// points, the raw DH values and the validity bytes, in hpke_seal_gpu.h's layout at d_eph.
+int launch_p256_eph(prio3gpu_ctx* c, const uint8_t* pk, size_t n, const uint8_t* d_sk,
+                    uint32_t* d_eph) {
+  P256EphPoints pts;
+  uint32_t x[8], y[8];
+  if (!p256_decode(kP256G, x, y, pts.X[0], pts.Y[0]) ||
+      !p256_decode(pk, x, y, pts.X[1], pts.Y[1])) {
+    set_err("HPKE seal: the public key is not a P-256 point");
+    return PRIO3GPU_E_HPKE;
+  }
+  {
+    PROF(KID_P256_EPH);
+    hipLaunchKernelGGL(k_p256_eph, dim3((unsigned)((n + 63) / 64), 2), dim3(64), 0, c->stream,
+                       (uint32_t)n, d_sk, pts, d_eph,
+                       reinterpret_cast<uint8_t*>(d_eph) + n * 96);
+  }
+  HIPCHK(hipGetLastError());
+  return 0;
+}
+
+// Stage the n ephemeral keys and run both ladders of every report: s->d_eph.  Under P-256 the KEM
+// half follows (k_p256_eph_kem) and bc.dh_ok is set to the validity bytes.
+int seal_ladders(prio3gpu_ctx* c, HpkeBatchConsts& bc, const uint8_t* pk, size_t n,
+                 const uint8_t* sk_es, SealSecrets* s) {
+  const bool p256 = bc.kem_lo == 0x10;
+  const size_t eph_bytes = n * (p256 ? kP256EphBytes : 64);
+  CHK(c->seal[1].ensure(eph_bytes));
   s->d_eph = static_cast<uint32_t*>(c->seal[1].p);
-  s->eph_bytes = n * 64;
+  s->eph_bytes = eph_bytes;
   s->sk_bytes = n * 32;
   CHK(stage_in(c, c->seal[0], sk_es, n * 32, &s->d_sk, kHpkeMinStage));
+  if (p256) {
+    uint8_t* d_ok = c->seal[1].u8() + n * 96;
+    bc.dh_ok = d_ok;
+    CHK(launch_p256_eph(c, pk, n, s->d_sk, s->d_eph));
+    P256DhConsts dc;
+    p256_load_be_words8(pk + 1, dc.pk.x);
+    p256_load_be_words8(pk + 33, dc.pk.y);
+    memcpy(dc.salt0_i, bc.salt0_i, sizeof dc.salt0_i);
+    memcpy(dc.salt0_o, bc.salt0_o, sizeof dc.salt0_o);
+    {
+      PROF(KID_P256_EPH_KEM);
+      hipLaunchKernelGGL(k_p256_eph_kem, dim3((unsigned)((n + 255) / 256)), dim3(256), 0,
+                         c->stream, (uint32_t)n, dc, s->d_eph, d_ok);
+    }
+    HIPCHK(hipGetLastError());
+    return 0;
+  }
   X25519Point pkw;
   memcpy(pkw.w, pk, 32);  // little-endian host
   {
@@ -717,11 +787,11 @@ int hpke_seal_batch_impl(prio3gpu_ctx* c, uint16_t kem_id, uint16_t kdf_id, uint
     CHK(stage_in(c, c->hpke[4], ct_offsets, (n + 1) * 8, &d_coff, kHpkeMinStage));
     CHK(stage_in(c, c->hpke[7], status, n, &d_st_in, kHpkeMinStage));
     d_st = const_cast<uint8_t*>(d_st_in);
-    CHK(seal_out(c, c->seal[7], encs, n * 32, &d_enc));
+    CHK(seal_out(c, c->seal[7], encs, n * bc.nenc, &d_enc));
     CHK(seal_out(c, c->seal[8], cts, ct_total, &d_ct));
     s.pt_bytes = pt_total;
     CHK(stage_in(c, c->seal[2], pts, pt_total, &s.d_pt, kHpkeMinStage));
-    CHK(seal_ladders(c, pk, n, sk_es, &s));
+    CHK(seal_ladders(c, bc, pk, n, sk_es, &s));
     // a lane per report, or (prio3gpu_hpke_seal_long_batch) a wave per report
     auto launch = [&](auto kernel, size_t per_block) {
       hipLaunchKernelGGL(kernel, dim3((unsigned)((n + per_block - 1) / per_block)), dim3(256), 0,
@@ -745,7 +815,7 @@ int hpke_seal_batch_impl(prio3gpu_ctx* c, uint16_t kem_id, uint16_t kdf_id, uint
     return 0;
   }();
   CHK(seal_clear_secrets(c, s, rc));
-  CHK(copy_out(c, encs, d_enc, n * 32));
+  CHK(copy_out(c, encs, d_enc, n * bc.nenc));
   if (d_ct != cts && ct_total > ct_first)
     HIPCHK(hipMemcpyAsync(cts + ct_first, d_ct + ct_first, ct_total - ct_first,
                           hipMemcpyDeviceToHost, c->stream));
@@ -772,7 +842,8 @@ int seal_rows_to_host(prio3gpu_ctx* c, uint8_t* dst, size_t pitch, const uint8_t
 // per report (hpke_seal_team.h: the suites of the wave-per-report open on this context).
 int seal_suite_check(const prio3gpu_ctx* c, uint16_t kem_id, uint16_t kdf_id, uint16_t aead_id,
                      bool team) {
-  if (team ? hpke_team_suite(c, kem_id, kdf_id, aead_id) : hpke_seal_suite(kem_id, kdf_id, aead_id))
+  if (team ? hpke_team_suite(c, kem_id, kdf_id, aead_id)
+           : hpke_seal_suite(c, kem_id, kdf_id, aead_id))
     return 0;
   set_err("HPKE suite 0x%04x/%u/%u is not sealed %s", kem_id, kdf_id, aead_id,
           team ? "a wave per report" : "on the GPU");
@@ -791,8 +862,9 @@ int hpke_seal_batch_entry(prio3gpu_ctx* c, uint16_t kem_id, uint16_t kdf_id, uin
     return PRIO3GPU_E_ARG;
   }
   CHK(seal_suite_check(c, kem_id, kdf_id, aead_id, team));
-  if (!pk || pk_len != 32 || (info_len && !info)) {
-    set_err("HPKE seal: the public key is 32 bytes");
+  CHK(seal_pk_check(kem_id, pk, pk_len));
+  if (info_len && !info) {
+    set_err("HPKE seal: null info");
     return PRIO3GPU_E_ARG;
   }
   if (n == 0) return 0;
@@ -820,14 +892,16 @@ int seal_input_shares_entry(prio3gpu_ctx* c, const uint8_t* task_id, uint16_t ke
     return PRIO3GPU_E_ARG;
   }
   CHK(seal_suite_check(c, kem_id, kdf_id, aead_id, team));
-  if (!pk || pk_len != 32 || !task_id) {
-    set_err("seal_input_shares: the public key and the task id are 32 bytes");
+  CHK(seal_pk_check(kem_id, pk, pk_len));
+  if (!task_id) {
+    set_err("seal_input_shares: null task id");
     return PRIO3GPU_E_ARG;
   }
   if (n == 0) return 0;
+  const size_t nenc = hpke_kem_nenc(kem_id);
   const size_t plen = 6 + (size_t)input_share_len + 16;
   const size_t spitch = input_share_pitch ? input_share_pitch : input_share_len;
-  const size_t epitch = enc_pitch ? enc_pitch : 32;
+  const size_t epitch = enc_pitch ? enc_pitch : nenc;
   const size_t ppitch = payload_pitch ? payload_pitch : plen;
   if (!report_ids || !times || (public_share_len && !public_shares) ||
       (input_share_len && !input_shares) || !sk_es || !out_encs || !out_payloads || !status ||
@@ -835,7 +909,7 @@ int seal_input_shares_entry(prio3gpu_ctx* c, const uint8_t* task_id, uint16_t ke
     set_err("seal_input_shares: null argument");
     return PRIO3GPU_E_ARG;
   }
-  if (spitch < input_share_len || epitch < 32 || ppitch < plen) {
+  if (spitch < input_share_len || epitch < nenc || ppitch < plen) {
     set_err("seal_input_shares: a pitch is shorter than its row");
     return PRIO3GPU_E_ARG;
   }
@@ -862,18 +936,18 @@ int seal_input_shares_entry(prio3gpu_ctx* c, const uint8_t* task_id, uint16_t ke
                  kHpkeMinStage));
     CHK(stage_in(c, c->hpke[7], status, n, &d_st_in, kHpkeMinStage));
     d_st = const_cast<uint8_t*>(d_st_in);
-    CHK(seal_out(c, c->seal[7], enc_host ? nullptr : out_encs, n * 32, &d_enc));
+    CHK(seal_out(c, c->seal[7], enc_host ? nullptr : out_encs, n * nenc, &d_enc));
     CHK(seal_out(c, c->seal[8], pay_host ? nullptr : out_payloads, n * plen, &d_pay));
     s.pt_bytes = share_bytes;
     CHK(stage_in(c, c->seal[2], input_shares, share_bytes, &s.d_pt, kHpkeMinStage));
-    CHK(seal_ladders(c, pk, n, sk_es, &s));
+    CHK(seal_ladders(c, bc, pk, n, sk_es, &s));
     // a lane per report, or (prio3gpu_seal_input_shares_long) a wave per report
     auto launch = [&](auto kernel, size_t per_block) {
       hipLaunchKernelGGL(kernel, dim3((unsigned)((n + per_block - 1) / per_block)), dim3(256), 0,
                          c->stream, (uint32_t)n, bc, tid, s.d_eph, d_rid,
                          reinterpret_cast<const uint64_t*>(d_time), d_pub, public_share_len,
                          s.d_pt, input_share_len, (uint64_t)spitch, d_enc,
-                         (uint64_t)(enc_host ? 32 : epitch), d_pay,
+                         (uint64_t)(enc_host ? nenc : epitch), d_pay,
                          (uint64_t)(pay_host ? plen : ppitch), d_st);
     };
     if (team) {
@@ -892,7 +966,7 @@ int seal_input_shares_entry(prio3gpu_ctx* c, const uint8_t* task_id, uint16_t ke
     return 0;
   }();
   CHK(seal_clear_secrets(c, s, rc));
-  if (enc_host) CHK(seal_rows_to_host(c, out_encs, epitch, d_enc, 32, n));
+  if (enc_host) CHK(seal_rows_to_host(c, out_encs, epitch, d_enc, nenc, n));
   if (pay_host) CHK(seal_rows_to_host(c, out_payloads, ppitch, d_pay, plen, n));
   CHK(copy_out(c, status, d_st, n));
   return finish_call(c, {report_ids, times, public_shares, input_shares, sk_es, out_encs,
@@ -1005,9 +1079,14 @@ int prio3gpu_hpke_open_long_batch(prio3gpu_ctx* c, uint16_t kem_id, uint16_t kdf
     set_err("HPKE suite 0x%04x/%u/%u is not opened a wave per report", kem_id, kdf_id, aead_id);
     return PRIO3GPU_E_UNSUPPORTED;
   }
-  if (!sk || sk_len != 32 || !pk || pk_len != 32 || (info_len && !info)) {
-    set_err("HPKE open: the private key and the public key are 32 bytes");
+  const size_t npk = hpke_kem_nenc(kem_id);
+  if (!sk || sk_len != 32 || !pk || pk_len != npk || (info_len && !info)) {
+    set_err("HPKE open: the private key is 32 bytes, the public key %zu", npk);
     return PRIO3GPU_E_ARG;
+  }
+  if (kem_id == 0x0010 && !p256_keypair_valid(sk, sk_len, pk, pk_len)) {
+    set_err("HPKE open: not a P-256 keypair");
+    return PRIO3GPU_E_HPKE;
   }
   if (n == 0) return 0;
   if (!encs || !aad_offsets || !ct_offsets || !pt_offsets || !status || n > 0x7FFFFFFFu) {
@@ -1035,13 +1114,20 @@ int prio3gpu_open_input_shares(prio3gpu_ctx* c, const uint8_t* task_id, uint16_t
     set_err("HPKE suite 0x%04x/%u/%u is not opened a wave per report", kem_id, kdf_id, aead_id);
     return PRIO3GPU_E_UNSUPPORTED;
   }
-  if (!sk || sk_len != 32 || !pk || pk_len != 32 || !task_id) {
-    set_err("open_input_shares: the keys and the task id are 32 bytes");
+  const bool p256 = kem_id == 0x0010;
+  const size_t nenc = hpke_kem_nenc(kem_id);
+  if (!sk || sk_len != 32 || !pk || pk_len != nenc || !task_id) {
+    set_err("open_input_shares: the private key and the task id are 32 bytes, the public key %zu",
+            nenc);
     return PRIO3GPU_E_ARG;
+  }
+  if (p256 && !p256_keypair_valid(sk, sk_len, pk, pk_len)) {
+    set_err("open_input_shares: not a P-256 keypair");
+    return PRIO3GPU_E_HPKE;
   }
   if (n == 0) return 0;
   const size_t plen = 6 + (size_t)input_share_len + 16;
-  const size_t epitch = enc_pitch ? enc_pitch : 32;
+  const size_t epitch = enc_pitch ? enc_pitch : nenc;
   const size_t ppitch = payload_pitch ? payload_pitch : plen;
   const size_t spitch = share_pitch ? share_pitch : input_share_len;
   if (!report_ids || !times || (public_share_len && !public_shares) || !encs || !payloads ||
@@ -1049,7 +1135,7 @@ int prio3gpu_open_input_shares(prio3gpu_ctx* c, const uint8_t* task_id, uint16_t
     set_err("open_input_shares: null argument");
     return PRIO3GPU_E_ARG;
   }
-  if (epitch < 32 || ppitch < plen || spitch < input_share_len) {
+  if (epitch < nenc || ppitch < plen || spitch < input_share_len) {
     set_err("open_input_shares: a pitch is shorter than its row");
     return PRIO3GPU_E_ARG;
   }
@@ -1066,13 +1152,14 @@ int prio3gpu_open_input_shares(prio3gpu_ctx* c, const uint8_t* task_id, uint16_t
   // host rows are staged with their gaps, one span per column; a host output is opened into
   // packed staging rows (zeroed after the copy: they are input shares), a device one in place
   const bool out_host = !(out_shares && is_device_ptr(out_shares));
-  const size_t out_bytes = n * (size_t)input_share_len, dh_bytes = n * 32;
+  // per report 32 bytes of DH value (P-256: shared secret) and, for P-256, one validity byte
+  const size_t out_bytes = n * (size_t)input_share_len, dh_bytes = n * (p256 ? 33 : 32);
   const uint8_t *d_rid, *d_time, *d_pub, *d_enc, *d_pay, *d_st_in;
   CHK(stage_in(c, c->seal[4], report_ids, n * 16, &d_rid, kHpkeMinStage));
   CHK(stage_in(c, c->seal[5], times, n * 8, &d_time, kHpkeMinStage));
   CHK(stage_in(c, c->seal[6], public_shares, n * (size_t)public_share_len, &d_pub,
                kHpkeMinStage));
-  CHK(stage_in(c, c->hpke[0], encs, (n - 1) * epitch + 32, &d_enc, kHpkeMinStage));
+  CHK(stage_in(c, c->hpke[0], encs, (n - 1) * epitch + nenc, &d_enc, kHpkeMinStage));
   CHK(stage_in(c, c->hpke[3], payloads, (n - 1) * ppitch + plen, &d_pay, kHpkeMinStage));
   CHK(stage_in(c, c->hpke[7], status, n, &d_st_in, kHpkeMinStage));
   uint8_t* d_st = const_cast<uint8_t*>(d_st_in);
@@ -1085,13 +1172,20 @@ int prio3gpu_open_input_shares(prio3gpu_ctx* c, const uint8_t* task_id, uint16_t
   uint32_t* d_dh = static_cast<uint32_t*>(c->hpke[8].p);
   // the ladder reads packed encapsulated keys: a pitched column is gathered first
   const uint8_t* d_enc_packed = d_enc;
-  if (epitch != 32) {
-    CHK(c->seal[7].ensure(n * 32));
-    HIPCHK(hipMemcpy2DAsync(c->seal[7].p, 32, d_enc, epitch, 32, n, hipMemcpyDeviceToDevice,
+  if (epitch != nenc) {
+    CHK(c->seal[7].ensure(n * nenc));
+    HIPCHK(hipMemcpy2DAsync(c->seal[7].p, nenc, d_enc, epitch, nenc, n, hipMemcpyDeviceToDevice,
                             c->stream));
     d_enc_packed = c->seal[7].u8();
   }
-  int rc = launch_x25519(c, sk, n, d_enc_packed, d_dh);
+  int rc;
+  if (p256) {
+    uint8_t* d_ok = c->hpke[8].u8() + n * 32;
+    bc.dh_ok = d_ok;
+    rc = launch_p256_dh(c, sk, pk, bc, /*raw=*/false, n, d_enc_packed, d_dh, d_ok);
+  } else {
+    rc = launch_x25519(c, sk, n, d_enc_packed, d_dh);
+  }
   if (!rc) {
     {
       PROF(KID_HPKE_OPEN_TEAM_SHARES);
@@ -1300,19 +1394,13 @@ int prio3gpu_test_p256_gpu(prio3gpu_ctx* c, const uint8_t* sk, const uint8_t* po
   }
   if (n == 0) return 0;
   // the generator stands in for pkRm: a refused encoding's lane runs over it
-  static const uint8_t kG[65] = {
-      0x04, 0x6b, 0x17, 0xd1, 0xf2, 0xe1, 0x2c, 0x42, 0x47, 0xf8, 0xbc, 0xe6, 0xe5, 0x63, 0xa4,
-      0x40, 0xf2, 0x77, 0x03, 0x7d, 0x81, 0x2d, 0xeb, 0x33, 0xa0, 0xf4, 0xa1, 0x39, 0x45, 0xd8,
-      0x98, 0xc2, 0x96, 0x4f, 0xe3, 0x42, 0xe2, 0xfe, 0x1a, 0x7f, 0x9b, 0x8e, 0xe7, 0xeb, 0x4a,
-      0x7c, 0x0f, 0x9e, 0x16, 0x2b, 0xce, 0x33, 0x57, 0x6b, 0x31, 0x5e, 0xce, 0xcb, 0xb6, 0x40,
-      0x68, 0x37, 0xbf, 0x51, 0xf5};
   HpkeBatchConsts bc{};  // raw mode hashes nothing: the pad states are not read
   HIPCHK(hipSetDevice(c->device));
   const uint8_t* d_pts;
   CHK(stage_in(c, c->hpke[0], points, n * 65, &d_pts, kHpkeMinStage));
   CHK(c->hpke[8].ensure(n * 33));
   uint8_t* d_out = c->hpke[8].u8();
-  int rc = launch_p256_dh(c, sk, kG, bc, /*raw=*/true, n, d_pts,
+  int rc = launch_p256_dh(c, sk, kP256G, bc, /*raw=*/true, n, d_pts,
                           reinterpret_cast<uint32_t*>(d_out), d_out + n * 32);
   if (!rc && hipMemcpyAsync(out_x, d_out, n * 32, hipMemcpyDeviceToHost, c->stream) != hipSuccess)
     rc = PRIO3GPU_E_HIP;
@@ -1321,6 +1409,39 @@ int prio3gpu_test_p256_gpu(prio3gpu_ctx* c, const uint8_t* sk, const uint8_t* po
   (void)hipMemsetAsync(d_out, 0, n * 33, c->stream);
   HIPCHK(hipStreamSynchronize(c->stream));
   return rc;
+}
+
+int prio3gpu_test_p256_eph_gpu(prio3gpu_ctx* c, const uint8_t* pk, const uint8_t* sk_es, size_t n,
+                               uint8_t* out_enc, uint8_t* out_dh_x, uint8_t* ok) {
+  if (!c || !pk || (n && (!sk_es || !out_enc || !out_dh_x || !ok)) || n > 0x7FFFFFFFu) {
+    set_err("null argument");
+    return PRIO3GPU_E_ARG;
+  }
+  CHK(seal_pk_check(0x0010, pk, 65));
+  if (n == 0) return 0;
+  HIPCHK(hipSetDevice(c->device));
+  const uint8_t* d_sk;
+  const size_t eph_bytes = n * kP256EphBytes;
+  CHK(stage_in(c, c->seal[0], sk_es, n * 32, &d_sk, kHpkeMinStage));
+  CHK(c->seal[1].ensure(eph_bytes));
+  uint8_t* d_eph = c->seal[1].u8();
+  std::vector<uint8_t> h(eph_bytes);
+  int rc = launch_p256_eph(c, pk, n, d_sk, reinterpret_cast<uint32_t*>(d_eph));
+  if (!rc && hipMemcpyAsync(h.data(), d_eph, eph_bytes, hipMemcpyDeviceToHost, c->stream) !=
+                 hipSuccess)
+    rc = PRIO3GPU_E_HIP;
+  (void)hipMemsetAsync(d_eph, 0, eph_bytes, c->stream);
+  if (d_sk == c->seal[0].u8()) (void)hipMemsetAsync(c->seal[0].p, 0, n * 32, c->stream);
+  HIPCHK(hipStreamSynchronize(c->stream));
+  if (rc) return rc;
+  for (size_t i = 0; i < n; ++i) {  // enc = 0x04 || x || y; all zeros for a refused scalar
+    ok[i] = h[n * 96 + i];
+    out_enc[i * 65] = ok[i] ? 0x04 : 0x00;
+    memcpy(out_enc + i * 65 + 1, &h[i * 64], 64);
+    memcpy(out_dh_x + i * 32, &h[n * 64 + i * 32], 32);
+  }
+  wipe(h.data(), h.size());
+  return 0;
 }
 
 int prio3gpu_test_poly1305_gpu(prio3gpu_ctx* c, const uint8_t* keys, const uint8_t* msgs,

@@ -88,7 +88,7 @@ enum KernelId {
   KID_FPV_REGEN, KID_X25519, KID_HPKE_OPEN, KID_REQ_GATHER, KID_X25519_IDX, KID_HPKE_OPEN_REQ,
   KID_DECODE_PT, KID_REQ_SCATTER, KID_REQ_COPY, KID_P256_DH, KID_P256_DH_IDX, KID_X25519_EPH,
   KID_HPKE_SEAL, KID_HPKE_SEAL_SHARES, KID_HPKE_OPEN_TEAM, KID_HPKE_OPEN_TEAM_SHARES,
-  KID_HPKE_SEAL_TEAM, KID_HPKE_SEAL_TEAM_SHARES, KID_COUNT
+  KID_HPKE_SEAL_TEAM, KID_HPKE_SEAL_TEAM_SHARES, KID_P256_EPH, KID_P256_EPH_KEM, KID_COUNT
 };
 
 // Per-kernel HIP-event timing on the context's stream (opt-in; used by bench.py).

@@ -72,10 +72,10 @@ DEVI void hpke_open_lane(const uint8_t* sbox, const HpkeBatchConsts& bc, const u
 }
 
 // A report that is not sealed: zeros in its enc and ciphertext slots; status 4 unless it was
-// skipped on entry.
+// skipped on entry.  nenc: the enc slot's bytes (HpkeBatchConsts::nenc).
 DEVI void hpke_seal_reject(uint8_t* enc_out, uint8_t* ct, uint64_t ct_cap, uint8_t* status,
-                           bool skip) {
-  for (int j = 0; j < 32; ++j) enc_out[j] = 0;
+                           bool skip, uint32_t nenc = 32) {
+  for (uint32_t j = 0; j < nenc; ++j) enc_out[j] = 0;
   for (uint64_t j = 0; j < ct_cap; ++j) ct[j] = 0;
   if (!skip) *status = ST_HPKE_DECRYPT;
 }
@@ -84,30 +84,49 @@ DEVI void hpke_seal_reject(uint8_t* enc_out, uint8_t* ct, uint64_t ct_cap, uint8
 // each, as k_x25519_eph wrote them), then AEAD-encrypt pt under aad with sequence number 0: enc_out
 // gets the 32 bytes of enc, ct gets pt.len() + 16 bytes (ciphertext || tag) and zeros up to
 // ct_cap -- or everything zeros and status 4 when the DH value is all zero (pkR of small order,
-// RFC 9180 §7.1.4).  pt and aad are byte sources (len(), block(o, d)).  sbox is unused (null) for
-// ChaCha20-Poly1305.
+// RFC 9180 §7.1.4).  With bc.dh_ok set (P-256: k_p256_eph and k_p256_eph_kem have run) dh is the
+// finished shared_secret, the report's flag dh_flag says whether its ephemeral scalar was valid
+// (zero: everything zeros and status 4; an all-zero value is no marker there), and enc is the 64
+// bytes x || y of the ephemeral point: enc_out gets the bc.nenc = 65 bytes 0x04 || x || y, at any
+// alignment.  The KEM is a wave-uniform branch.  pt and aad are byte sources (len(), block(o, d)).
+// sbox is unused (null) for ChaCha20-Poly1305.
 template <int KDF, int AEAD, class Pt, class Aad>
 DEVI void hpke_seal_lane(const uint8_t* sbox, const HpkeBatchConsts& bc, const uint32_t* enc,
                          const uint32_t* dh, const Pt& pt, const Aad& aad, uint8_t* enc_out,
-                         uint8_t* ct, uint64_t ct_cap, uint8_t* status) {
+                         uint8_t* ct, uint64_t ct_cap, uint8_t* status, uint32_t dh_flag = 1u) {
   uint32_t dhw[8], encw[8], ence[8], nz = 0;
 #pragma unroll
   for (int i = 0; i < 8; ++i) {
     const uint32_t d = dh[i];
     nz |= d;
     dhw[i] = bswap32(d);
-    ence[i] = enc[i];
-    encw[i] = bswap32(ence[i]);
+    ence[i] = encw[i] = 0;
+  }
+  if (bc.dh_ok) {
+    nz = dh_flag;
+  } else {
+#pragma unroll
+    for (int i = 0; i < 8; ++i) {
+      ence[i] = enc[i];
+      encw[i] = bswap32(ence[i]);
+    }
   }
   if (nz == 0u) {
-    hpke_seal_reject(enc_out, ct, ct_cap, status, false);
+    hpke_seal_reject(enc_out, ct, ct_cap, status, false, bc.nenc);
     return;
+  }
+  if (bc.dh_ok) {  // before the key schedule: nothing of enc stays live across it
+    const uint8_t* xy = reinterpret_cast<const uint8_t*>(enc);
+    enc_out[0] = 0x04;
+    for (int j = 0; j < 64; ++j) enc_out[1 + j] = xy[j];
   }
   constexpr int NKW = hpke_aead_nk(AEAD) / 4;
   uint32_t key[NKW], nonce[3];
   hpke_key_nonce<KDF, AEAD>(bc, dhw, encw, key, nonce);
-  store_block(enc_out, 16, ence);
-  store_block(enc_out + 16, 16, ence + 4);
+  if (!bc.dh_ok) {
+    store_block(enc_out, 16, ence);
+    store_block(enc_out + 16, 16, ence + 4);
+  }
   const uint64_t plen = pt.len();
   if constexpr (AEAD == 3) {
 #pragma unroll

@@ -1,5 +1,6 @@
 // Batched HPKE open of long ciphertexts on the GPU, one WAVE per report: DHKEM(X25519,
-// HKDF-SHA256) with HKDF-SHA256 / -SHA384 / -SHA512 and AES-128-GCM / AES-256-GCM /
+// HKDF-SHA256) (and DHKEM(P-256, HKDF-SHA256) behind the context's "hpke_gpu_p256" option, after
+// hpke_gpu.h's k_p256_dh) with HKDF-SHA256 / -SHA384 / -SHA512 and AES-128-GCM / AES-256-GCM /
 // ChaCha20-Poly1305, RFC 9180 base mode, single shot.  What the leader does once per upload (aggregator.rs:1325-1497) with an input
 // share of a hundred kilobytes, where hpke_gpu.h's lane per report would walk it alone:
 //   k_hpke_open_team<KDF, AEAD>          packed inputs with offsets, as k_hpke_open takes them
@@ -126,21 +127,31 @@ __device__ __forceinline__ bool hpke_open_team_wave_gcm(const uint8_t* sbox, uin
 }
 
 // Either of them, from the report's dh (8 words as k_x25519 wrote them) and enc (32 bytes); sbox
-// and tbl are not read (null) for ChaCha20-Poly1305.
+// and tbl are not read (null) for ChaCha20-Poly1305.  With bc.dh_ok set (P-256) dh is the
+// shared_secret k_p256_dh left, dh_flag the report's validity byte in place of the all-zero test,
+// and enc is not read: what hpke_open_lane does, on a wave-uniform branch.
 template <int KDF, int AEAD, class Aad, class Sink>
 __device__ __forceinline__ bool hpke_open_team_wave(const uint8_t* sbox, uint32_t* tbl,
                                                     const HpkeBatchConsts& bc, const uint32_t* dh,
                                                     const uint8_t* enc, const Aad& aad,
                                                     const uint8_t* ct, uint64_t body,
-                                                    uint32_t lane, Sink& sink) {
+                                                    uint32_t lane, Sink& sink, uint32_t dh_flag) {
   uint32_t dhw[8], encw[8], nz = 0;
 #pragma unroll
   for (int i = 0; i < 8; ++i) {
     const uint32_t d = dh[i];
     nz |= d;
     dhw[i] = bswap32(d);
-    const uint8_t* e = enc + 4 * i;
-    encw[i] = ((uint32_t)e[0] << 24) | ((uint32_t)e[1] << 16) | ((uint32_t)e[2] << 8) | e[3];
+    encw[i] = 0;
+  }
+  if (bc.dh_ok) {
+    nz = dh_flag;
+  } else {
+#pragma unroll
+    for (int i = 0; i < 8; ++i) {
+      const uint8_t* e = enc + 4 * i;
+      encw[i] = ((uint32_t)e[0] << 24) | ((uint32_t)e[1] << 16) | ((uint32_t)e[2] << 8) | e[3];
+    }
   }
   if constexpr (AEAD == 3)
     return hpke_open_team_wave_chacha<KDF>(bc, dhw, nz, encw, aad, ct, body, lane, sink);
@@ -211,15 +222,15 @@ __global__ void __launch_bounds__(256) k_hpke_open_team(
   const uint64_t body = c1 - c0 - 16;
   PackedSink sink{pt};
   const bool ok = hpke_open_team_wave<KDF, AEAD>(w.sbox, w.tbl, bc, dh + (size_t)r * 8,
-                                                 encs + (size_t)r * 32,
+                                                 encs + (size_t)r * bc.nenc,
                                                  PackedBytes{aads + a0, a1 - a0}, cts + c0, body,
-                                                 lane, sink);
+                                                 lane, sink, bc.dh_ok ? bc.dh_ok[r] : 1u);
   team_zero(pt + body, pt_cap - body, lane, kTeam);
   if (!ok && lane == 0) status[r] = ST_HPKE_DECRYPT;
 }
 
 // One wave per report over the columns of a batch of uploads to one aggregator: report r's enc is
-// encs[r enc_pitch ..] (32 bytes), its payload payloads[r ppitch ..], exactly 6 + slen + 16 bytes,
+// encs[r enc_pitch ..] (bc.nenc bytes; not read for P-256), its payload payloads[r ppitch ..], exactly 6 + slen + 16 bytes,
 // its AAD the InputShareAad of (tid, rids[16 r ..], times[r], pubs[r pslen ..]), never built in
 // memory.  The plaintext must be 00 00 | u32 BE slen | share: the share goes to
 // out[r spitch .. + slen) and nothing else of out is written.  Zeros in the row and status 4 for
@@ -245,7 +256,8 @@ __global__ void __launch_bounds__(256) k_hpke_open_team_shares(
   const bool ok = hpke_open_team_wave<KDF, AEAD>(w.sbox, w.tbl, bc, dh + (size_t)r * 8,
                                                  encs + (uint64_t)r * enc_pitch, aad,
                                                  payloads + (uint64_t)r * ppitch,
-                                                 6 + (uint64_t)slen, lane, sink);
+                                                 6 + (uint64_t)slen, lane, sink,
+                                                 bc.dh_ok ? bc.dh_ok[r] : 1u);
   if (!ok) {
     if (lane == 0) status[r] = ST_HPKE_DECRYPT;
     return;

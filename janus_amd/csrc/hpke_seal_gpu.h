@@ -1,9 +1,12 @@
-// Batched HPKE seal on the GPU for DHKEM(X25519, HKDF-SHA256) with every KDF and AEAD Janus accepts
+// Batched HPKE seal on the GPU for DHKEM(X25519, HKDF-SHA256) and, behind the context's
+// "hpke_gpu_p256" option, DHKEM(P-256, HKDF-SHA256) with every KDF and AEAD Janus accepts
 // (KDF 1-3 x AEAD 1-3), RFC 9180 base mode, single shot: what a DAP client does once per input
 // share (client/src/lib.rs:212-258, core/src/hpke.rs:158-182).  The mirror image of hpke_gpu.h's
 // open, one lane per report, every report of a launch to ONE recipient key, each under its own
 // ephemeral key:
 //   k_x25519_eph               enc = X25519(skE, 9), dh = X25519(skE, pkR)         RFC 9180 §4.1
+//   k_p256_eph                 enc = [skE] G, dh = x([skE] pkR), the scalar's validity   §7.1
+//   k_p256_eph_kem             dh -> shared_secret (ExtractAndExpand over enc || pkR)    §4.1
 //   k_hpke_seal<KDF, AEAD>     key schedule + AEAD encryption over packed plaintexts and AADs
 //   k_hpke_seal_shares<KDF, AEAD>   the same over Prio3 input shares: the PlaintextInputShare and
 //                              the InputShareAad are byte sources over the caller's rows and are
@@ -14,6 +17,7 @@
 // Only the kernels are here: the lane (hpke_seal_lane) and the two byte sources (SharePlaintext,
 // ReqAad) are hpke_lane.h's, free of HIP and run by CPU tests too.  Included by engine_hpke.hip.
 #pragma once
+#include "hpke_gpu.h"
 #include "hpke_lane.h"
 #include "x25519.h"
 
@@ -47,11 +51,80 @@ __global__ void __launch_bounds__(64) k_x25519_eph(uint32_t n, const uint8_t* sk
   }
 }
 
+// The ladders' output for n reports under P-256, as the seal kernels read it (bc.dh_ok set), in
+// bytes: [0, 64 n) the ephemeral points' x || y, 64 per report; [64 n, 96 n) the DH values' x, after
+// k_p256_eph_kem the shared secrets; [96 n, 97 n) one validity byte per report (bc.dh_ok).
+constexpr size_t kP256EphBytes = 97;
+
+struct P256EphPoints {  // G ([0]) and pkR ([1]) in Montgomery coordinates; a kernel argument
+  Fp256 X[2], Y[2];
+};
+
+// The P-256 counterpart of k_x25519_eph: blockIdx.y = 0 the encapsulated keys [sk_es[r]] G (both
+// coordinates, and the report's validity byte), 1 the DH values x([sk_es[r]] pkR).  ONE ladder:
+// the point comes from selects on blockIdx.y.  The scalar is the lane's own (p256_eph_lane): its
+// bits are select masks only, no branch and no address depends on it; a scalar outside [1, n)
+// runs the same instructions and leaves zeros and ok = 0.
+__global__ void __launch_bounds__(64) k_p256_eph(uint32_t n, const uint8_t* sk_es,
+                                                 P256EphPoints pts, uint32_t* out, uint8_t* ok) {
+  const uint32_t r = blockIdx.x * blockDim.x + threadIdx.x;
+  const uint32_t which = blockIdx.y;
+  const bool live = r < n;
+  Fp256 X, Y;
+#pragma unroll
+  for (int i = 0; i < 8; ++i) {
+    X.v[i] = which ? pts.X[1].v[i] : pts.X[0].v[i];
+    Y.v[i] = which ? pts.Y[1].v[i] : pts.Y[0].v[i];
+  }
+  uint32_t x[8], y[8];
+  const bool good = p256_eph_lane(sk_es + (size_t)(live ? r : n - 1) * 32, X, Y, x, y);
+  if (!live) return;
+  if (which == 0) {
+    uint32_t* o = out + (size_t)r * 16;
+#pragma unroll
+    for (int i = 0; i < 8; ++i) o[i] = bswap32(x[i]), o[8 + i] = bswap32(y[i]);
+    ok[r] = good ? 1 : 0;
+  } else {
+    uint32_t* o = out + (size_t)n * 16 + (size_t)r * 8;
+#pragma unroll
+    for (int i = 0; i < 8; ++i) o[i] = bswap32(x[i]);
+  }
+}
+
+// The KEM half after k_p256_eph, one lane per report: eph's DH value becomes the shared_secret in
+// place (zeros for a report whose ok byte is 0).
+__global__ void __launch_bounds__(256) k_p256_eph_kem(uint32_t n, P256DhConsts dc, uint32_t* eph,
+                                                      const uint8_t* ok) {
+  const uint32_t r = blockIdx.x * blockDim.x + threadIdx.x;
+  if (r >= n) return;
+  uint32_t ex[8], ey[8], dh[8], ss[8];
+  uint32_t* d = eph + (size_t)n * 16 + (size_t)r * 8;
+#pragma unroll
+  for (int i = 0; i < 8; ++i) {
+    ex[i] = bswap32(eph[(size_t)r * 16 + i]);
+    ey[i] = bswap32(eph[(size_t)r * 16 + 8 + i]);
+    dh[i] = bswap32(d[i]);
+  }
+  p256_eph_shared_secret(dc.salt0_i, dc.salt0_o, dh, ex, ey, dc.pk, ok[r] != 0, ss);
+#pragma unroll
+  for (int i = 0; i < 8; ++i) d[i] = bswap32(ss[i]);
+}
+
+// Where report r's enc and DH words lie in the ladders' output: k_x25519_eph's n encs of 8 words,
+// then n DH values; under P-256 (bc.dh_ok) n points of 16 words, then n shared secrets.
+DEVI const uint32_t* eph_enc(const HpkeBatchConsts& bc, const uint32_t* eph, uint32_t r) {
+  return eph + (size_t)r * (bc.dh_ok ? 16 : 8);
+}
+DEVI const uint32_t* eph_dh(const HpkeBatchConsts& bc, const uint32_t* eph, uint32_t n,
+                            uint32_t r) {
+  return eph + (size_t)n * (bc.dh_ok ? 16 : 8) + (size_t)r * 8;
+}
+
 // One lane per report: hpke_seal_lane over packed plaintexts and AADs; report r's ciphertext ||
-// tag goes to cts[ct_off[r] .. ct_off[r + 1]) and its enc to encs[32 r ..].  A slot shorter than
+// tag goes to cts[ct_off[r] .. ct_off[r + 1]) and its enc to encs[bc.nenc r ..].  A slot shorter than
 // the plaintext + 16 or offsets that do not fit: zeros and status 4.  A report whose status is
 // non-zero on entry keeps it and gets zeros.  `eph` is k_x25519_eph's output (n encs, then n DH
-// values).  Lanes have their own lengths; the only barrier is the one after the S-box is built,
+// values) or, with bc.dh_ok set, k_p256_eph's and k_p256_eph_kem's.  Lanes have their own lengths; the only barrier is the one after the S-box is built,
 // before any lane diverges (no S-box for ChaCha20-Poly1305).
 template <int KDF, int AEAD>
 __global__ void __launch_bounds__(256) k_hpke_seal(
@@ -73,23 +146,23 @@ __global__ void __launch_bounds__(256) k_hpke_seal(
   const bool ct_fits = c0 <= c1 && c1 <= ct_total;
   const uint64_t ct_cap = ct_fits ? c1 - c0 : 0;
   uint8_t* ct = cts + (ct_fits ? c0 : 0);
-  uint8_t* enc_out = encs + (size_t)r * 32;
+  uint8_t* enc_out = encs + (size_t)r * bc.nenc;
   const bool skip = status[r] != 0;
   const bool ok = !skip && ct_fits && a0 <= a1 && a1 <= aad_total && p0 <= p1 && p1 <= pt_total &&
                   ct_cap >= 16 && p1 - p0 <= ct_cap - 16;
   if (!ok) {  // nothing to read: skip the work, not just the result
-    hpke_seal_reject(enc_out, ct, ct_cap, status + r, skip);
+    hpke_seal_reject(enc_out, ct, ct_cap, status + r, skip, bc.nenc);
     return;
   }
-  hpke_seal_lane<KDF, AEAD>(sbox, bc, eph + (size_t)r * 8, eph + ((size_t)n + r) * 8,
+  hpke_seal_lane<KDF, AEAD>(sbox, bc, eph_enc(bc, eph, r), eph_dh(bc, eph, n, r),
                             PackedBytes{pts + p0, p1 - p0}, PackedBytes{aads + a0, a1 - a0},
-                            enc_out, ct, ct_cap, status + r);
+                            enc_out, ct, ct_cap, status + r, bc.dh_ok ? bc.dh_ok[r] : 1u);
 }
 
 // One lane per report: hpke_seal_lane over the rows of a batch of Prio3 input shares to one
 // aggregator.  Report r's plaintext is the PlaintextInputShare of shares[r spitch ..] (slen bytes),
 // its AAD the InputShareAad of (tid, rids[16 r ..], times[r], pubs[r pslen ..]); neither frame
-// exists in memory.  Its enc goes to encs[r enc_pitch ..] (32 bytes) and its payload, exactly
+// exists in memory.  Its enc goes to encs[r enc_pitch ..] (bc.nenc bytes) and its payload, exactly
 // 6 + slen + 16 bytes, to payloads[r ppitch ..]; nothing else of either buffer is written.
 template <int KDF, int AEAD>
 __global__ void __launch_bounds__(256) k_hpke_seal_shares(
@@ -110,13 +183,13 @@ __global__ void __launch_bounds__(256) k_hpke_seal_shares(
   uint8_t* ct = payloads + (uint64_t)r * ppitch;
   const uint64_t ct_cap = 6 + (uint64_t)slen + 16;
   if (status[r] != 0) {
-    hpke_seal_reject(enc_out, ct, ct_cap, status + r, true);
+    hpke_seal_reject(enc_out, ct, ct_cap, status + r, true, bc.nenc);
     return;
   }
   const ReqAad aad{tid, rids + (size_t)r * 16, times[r], pslen, pubs + (size_t)r * pslen};
-  hpke_seal_lane<KDF, AEAD>(sbox, bc, eph + (size_t)r * 8, eph + ((size_t)n + r) * 8,
+  hpke_seal_lane<KDF, AEAD>(sbox, bc, eph_enc(bc, eph, r), eph_dh(bc, eph, n, r),
                             SharePlaintext{shares + (uint64_t)r * spitch, slen}, aad, enc_out, ct,
-                            ct_cap, status + r);
+                            ct_cap, status + r, bc.dh_ok ? bc.dh_ok[r] : 1u);
 }
 
 }  // namespace p3g

@@ -1,5 +1,6 @@
 // Batched HPKE seal of long plaintexts on the GPU, one WAVE per report: DHKEM(X25519, HKDF-SHA256)
-// with HKDF-SHA256 / -SHA384 / -SHA512 and AES-128-GCM / AES-256-GCM / ChaCha20-Poly1305, RFC 9180
+// (and DHKEM(P-256, HKDF-SHA256) behind the context's "hpke_gpu_p256" option; its ladders are
+// hpke_seal_gpu.h's k_p256_eph) with HKDF-SHA256 / -SHA384 / -SHA512 and AES-128-GCM / AES-256-GCM / ChaCha20-Poly1305, RFC 9180
 // base mode, single shot.  What a DAP client does for the leader's input share of a hundred
 // kilobytes, where hpke_seal_gpu.h's lane per report would walk it alone; the mirror of
 // hpke_open_team.h:
@@ -22,6 +23,7 @@
 // engine_hpke.hip.
 #pragma once
 #include "hpke_open_team.h"
+#include "hpke_seal_gpu.h"
 
 namespace p3g {
 
@@ -29,8 +31,8 @@ namespace p3g {
 // unless it was skipped on entry.
 __device__ __forceinline__ void hpke_seal_team_reject(uint8_t* enc_out, uint8_t* ct,
                                                       uint64_t ct_cap, uint8_t* status, bool skip,
-                                                      uint32_t lane) {
-  team_zero(enc_out, 32, lane, kTeam);
+                                                      uint32_t lane, uint32_t nenc) {
+  team_zero(enc_out, nenc, lane, kTeam);
   team_zero(ct, ct_cap, lane, kTeam);
   if (!skip && lane == 0) *status = ST_HPKE_DECRYPT;
 }
@@ -38,27 +40,37 @@ __device__ __forceinline__ void hpke_seal_team_reject(uint8_t* enc_out, uint8_t*
 // The wave's seal of one report after the ladders, with hpke_seal_lane's contract: enc and dh are
 // the report's 8 little-endian words each as k_x25519_eph wrote them; enc_out gets the 32 bytes of
 // enc, ct gets pt.len() + 16 bytes (ciphertext || tag) and zeros up to ct_cap -- or everything
-// zeros and status 4 when the DH value is all zero, before any key is derived.  tbl: 4 kTeam words
-// of LDS of this wave's own, zero when the call returns; sbox and tbl are not read (null) for
-// ChaCha20-Poly1305.
+// zeros and status 4 when the DH value is all zero, before any key is derived.  With bc.dh_ok set
+// (P-256) dh is the finished shared_secret, dh_flag the report's validity byte in place of the
+// all-zero test, enc the 64 bytes x || y, and enc_out gets the 65 bytes 0x04 || x || y, a byte per
+// lane; the KEM is a wave-uniform branch.  tbl: 4 kTeam words of LDS of this wave's own, zero when
+// the call returns; sbox and tbl are not read (null) for ChaCha20-Poly1305.
 template <int KDF, int AEAD, class Pt, class Aad>
 __device__ __forceinline__ void hpke_seal_team_wave(const uint8_t* sbox, uint32_t* tbl,
                                                     const HpkeBatchConsts& bc, const uint32_t* enc,
                                                     const uint32_t* dh, const Pt& pt,
                                                     const Aad& aad, uint8_t* enc_out, uint8_t* ct,
                                                     uint64_t ct_cap, uint8_t* status,
-                                                    uint32_t lane) {
+                                                    uint32_t lane, uint32_t dh_flag) {
   uint32_t dhw[8], encw[8], ence[8], nz = 0;
 #pragma unroll
   for (int i = 0; i < 8; ++i) {
     const uint32_t d = dh[i];
     nz |= d;
     dhw[i] = bswap32(d);
-    ence[i] = enc[i];
-    encw[i] = bswap32(ence[i]);
+    ence[i] = encw[i] = 0;
+  }
+  if (bc.dh_ok) {
+    nz = dh_flag;
+  } else {
+#pragma unroll
+    for (int i = 0; i < 8; ++i) {
+      ence[i] = enc[i];
+      encw[i] = bswap32(ence[i]);
+    }
   }
   if (nz == 0u) {  // alike on every lane of the wave
-    hpke_seal_team_reject(enc_out, ct, ct_cap, status, false, lane);
+    hpke_seal_team_reject(enc_out, ct, ct_cap, status, false, lane, bc.nenc);
     return;
   }
   constexpr int NKW = hpke_aead_nk(AEAD) / 4;
@@ -102,7 +114,10 @@ __device__ __forceinline__ void hpke_seal_team_wave(const uint8_t* sbox, uint32_
     aes_gcm_tag<NKW>(sbox, rk, h, y, ctr, aad.len(), plen, t);
   }
   if (lane == 0) store_block_any(ct + plen, t);
-  if (lane < 2) {  // enc: sixteen bytes from each of two lanes
+  if (bc.dh_ok) {  // enc: 0x04, then a byte of x || y from each lane
+    if (lane == 0) enc_out[0] = 0x04;
+    enc_out[1 + lane] = reinterpret_cast<const uint8_t*>(enc)[lane];
+  } else if (lane < 2) {  // enc: sixteen bytes from each of two lanes
     uint32_t e[4];
 #pragma unroll
     for (int i = 0; i < 4; ++i) e[i] = lane ? ence[4 + i] : ence[i];
@@ -116,10 +131,10 @@ __device__ __forceinline__ void hpke_seal_team_wave(const uint8_t* sbox, uint32_
 }
 
 // One wave per report over packed inputs, with k_hpke_seal's arguments and contracts: report r's
-// ciphertext || tag goes to cts[ct_off[r] .. ct_off[r + 1]) and its enc to encs[32 r ..].  A slot
+// ciphertext || tag goes to cts[ct_off[r] .. ct_off[r + 1]) and its enc to encs[bc.nenc r ..].  A slot
 // shorter than the plaintext + 16 or offsets that do not fit: zeros and status 4.  A report whose
 // status is non-zero on entry keeps it and gets zeros.  `eph` is k_x25519_eph's output (n encs,
-// then n DH values).
+// then n DH values) or, with bc.dh_ok set, k_p256_eph's and k_p256_eph_kem's.
 template <int KDF, int AEAD>
 __global__ void __launch_bounds__(256) k_hpke_seal_team(
     uint32_t n, HpkeBatchConsts bc, const uint32_t* eph, const uint8_t* aads,
@@ -134,25 +149,25 @@ __global__ void __launch_bounds__(256) k_hpke_seal_team(
   const bool ct_fits = c0 <= c1 && c1 <= ct_total;
   const uint64_t ct_cap = ct_fits ? c1 - c0 : 0;
   uint8_t* ct = cts + (ct_fits ? c0 : 0);
-  uint8_t* enc_out = encs + (size_t)r * 32;
+  uint8_t* enc_out = encs + (size_t)r * bc.nenc;
   const bool skip = status[r] != 0;
   const bool ok = !skip && ct_fits && a0 <= a1 && a1 <= aad_total && p0 <= p1 && p1 <= pt_total &&
                   ct_cap >= 16 && p1 - p0 <= ct_cap - 16;
   if (!ok) {  // nothing to read: skip the work, not just the result
-    hpke_seal_team_reject(enc_out, ct, ct_cap, status + r, skip, lane);
+    hpke_seal_team_reject(enc_out, ct, ct_cap, status + r, skip, lane, bc.nenc);
     return;
   }
-  hpke_seal_team_wave<KDF, AEAD>(w.sbox, w.tbl, bc, eph + (size_t)r * 8,
-                                 eph + ((size_t)n + r) * 8, PackedBytes{pts + p0, p1 - p0},
-                                 PackedBytes{aads + a0, a1 - a0}, enc_out, ct, ct_cap, status + r,
-                                 lane);
+  hpke_seal_team_wave<KDF, AEAD>(w.sbox, w.tbl, bc, eph_enc(bc, eph, r), eph_dh(bc, eph, n, r),
+                                 PackedBytes{pts + p0, p1 - p0}, PackedBytes{aads + a0, a1 - a0},
+                                 enc_out, ct, ct_cap, status + r, lane,
+                                 bc.dh_ok ? bc.dh_ok[r] : 1u);
 }
 
 // One wave per report over the rows of a batch of Prio3 input shares to one aggregator, with
 // k_hpke_seal_shares' arguments and contracts.  Report r's plaintext is the PlaintextInputShare of
 // shares[r spitch ..] (slen bytes), its AAD the InputShareAad of (tid, rids[16 r ..], times[r],
 // pubs[r pslen ..]); neither frame exists in memory.  Its enc goes to encs[r enc_pitch ..]
-// (32 bytes) and its payload, exactly 6 + slen + 16 bytes, to payloads[r ppitch ..], at whatever
+// (bc.nenc bytes) and its payload, exactly 6 + slen + 16 bytes, to payloads[r ppitch ..], at whatever
 // alignment the columns have; nothing else of either buffer is written.
 template <int KDF, int AEAD>
 __global__ void __launch_bounds__(256) k_hpke_seal_team_shares(
@@ -167,14 +182,13 @@ __global__ void __launch_bounds__(256) k_hpke_seal_team_shares(
   uint8_t* ct = payloads + (uint64_t)r * ppitch;
   const uint64_t ct_cap = 6 + (uint64_t)slen + 16;
   if (status[r] != 0) {
-    hpke_seal_team_reject(enc_out, ct, ct_cap, status + r, true, lane);
+    hpke_seal_team_reject(enc_out, ct, ct_cap, status + r, true, lane, bc.nenc);
     return;
   }
   const ReqAad aad{tid, rids + (size_t)r * 16, times[r], pslen, pubs + (size_t)r * pslen};
-  hpke_seal_team_wave<KDF, AEAD>(w.sbox, w.tbl, bc, eph + (size_t)r * 8,
-                                 eph + ((size_t)n + r) * 8,
+  hpke_seal_team_wave<KDF, AEAD>(w.sbox, w.tbl, bc, eph_enc(bc, eph, r), eph_dh(bc, eph, n, r),
                                  SharePlaintext{shares + (uint64_t)r * spitch, slen}, aad, enc_out,
-                                 ct, ct_cap, status + r, lane);
+                                 ct, ct_cap, status + r, lane, bc.dh_ok ? bc.dh_ok[r] : 1u);
 }
 
 }  // namespace p3g

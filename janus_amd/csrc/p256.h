@@ -3,7 +3,9 @@
 // (tests/native/p256_host.cpp) run the same code:
 //   Fp256, fp_*            GF(p), p = 2^256 - 2^224 + 2^192 + 2^96 - 1            FIPS 186-4 D.1.2.3
 //   p256_decode            DeserializePublicKey with the on-curve check           RFC 9180 §7.1.1, §7.1.4
-//   p256_dh_x              x([k] P), one instruction sequence for every scalar
+//   p256_dh_x, p256_mul_xy x([k] P) and (x, y)([k] P), one instruction sequence for every scalar,
+//                          wave-uniform (the recipient's key) or the lane's own (the sender's
+//                          ephemeral key, hpke_seal_gpu.h: k_p256_eph)
 // The KEM half (ExtractAndExpand, RFC 9180 §4.1) and the kernels' lane are p256_kem.h's, which
 // hashes; this header has no dependency, so the host planning (plan_hpke.h) validates keypairs
 // with the kernels' own decoder.
@@ -18,9 +20,10 @@
 // below 2 p (nine words, the ninth 0 or 1): t' = (t + a_i b + m p) / 2^32 < (2 p + 2 (2^32 - 1) p)
 // / 2^32 < 2 p for b < p; one masked subtraction of p ends it.
 //
-// Nothing here branches or indexes memory by the scalar or by a field value: the scalar is
-// wave-uniform, its words are picked with uniform selects (as x25519_lane does), its bits are used
-// as select masks only; the inversion is a fixed addition chain for p - 2.
+// Nothing here branches or indexes memory by the scalar or by a field value: a wave-uniform
+// scalar's words are picked with selects on the loop counter (as x25519_lane does), a lane's own
+// scalar is shifted out of fixed registers, its bits are used as select masks only; the inversion
+// is a fixed addition chain for p - 2.
 #pragma once
 #include <stdint.h>
 
@@ -39,6 +42,9 @@ struct Fp256 {
   uint32_t v[8];
 };
 struct P256Scalar {  // k in [1, n), little-endian words; a kernel argument (SGPRs)
+  uint32_t w[8];
+};
+struct P256LaneScalar {  // the same, a lane's own (VGPRs): the sender's ephemeral key
   uint32_t w[8];
 };
 
@@ -360,35 +366,107 @@ P3G_P256 void p256_add_affine(P256Proj& r, const P256Proj& p, const Fp256& x2, c
   fp_add(r.Z, Z3, t1);
 }
 
-// x([k] P) as 8 big-endian words, for k in [1, n) and P = (X, Y) a valid point: double-and-add-
+// [k] P in projective coordinates, for k in [1, n) and P = (X, Y) a valid point: double-and-add-
 // always from the point at infinity over all 256 bits, the addition's result taken with a select.
 // [k] P is never O (the group has prime order n and 0 < k < n), so Z != 0 at the end.
-// 256 (8 M + 3 S + 2 m_b + 11 M + 2 m_b) = 6,656 field products of 64 v_mad_u64_u32, plus the
-// inversion's 267 and three more: 443 K products per DH.
-P3G_P256 void p256_dh_x(const P256Scalar& k, const Fp256& X, const Fp256& Y, uint32_t out_be[8]) {
-  P256Proj r, s;
+// 256 (8 M + 3 S + 2 m_b + 11 M + 2 m_b) = 6,656 field products of 64 v_mad_u64_u32.
+// Scalar is P256Scalar (wave-uniform: a kernel argument in SGPRs) or P256LaneScalar (the lane's
+// own, in VGPRs); the two differ only in how bit t is read (p256_next_bit), one text of the
+// formulas for both.  Either way the bit is a select mask and nothing is indexed by the scalar.
+// The uniform scalar's words are picked with selects on the loop counter.
+P3G_P256 uint32_t p256_next_bit(P256Scalar& k, int t) {
+  const int wi = t >> 5;
+  uint32_t kw = k.w[0];
+#pragma unroll
+  for (int i = 1; i < 8; ++i) kw = wi == i ? k.w[i] : kw;
+  return (kw >> (t & 31)) & 1u;
+}
+// The lane's own scalar is consumed from the top: its eight words shift left by one per step, so
+// every word keeps a fixed register and no word is ever chosen by an index (a choice among eight
+// per-lane words is what a compiler turns into an indexed array in memory).
+P3G_P256 uint32_t p256_next_bit(P256LaneScalar& k, int) {
+  const uint32_t kt = k.w[7] >> 31;
+#pragma unroll
+  for (int i = 7; i > 0; --i) k.w[i] = (k.w[i] << 1) | (k.w[i - 1] >> 31);
+  k.w[0] <<= 1;
+  return kt;
+}
+
+template <class Scalar>
+P3G_P256 void p256_ladder(const Scalar& k_in, const Fp256& X, const Fp256& Y, P256Proj& r) {
+  P256Proj s;
+  Scalar k = k_in;
 #pragma unroll
   for (int i = 0; i < 8; ++i) r.X.v[i] = r.Z.v[i] = 0u;
   fp_one(r.Y);
 #pragma unroll 1
   for (int t = 255; t >= 0; --t) {
-    const int wi = t >> 5;
-    uint32_t kw = k.w[0];
-#pragma unroll
-    for (int i = 1; i < 8; ++i) kw = wi == i ? k.w[i] : kw;
-    const uint32_t kt = (kw >> (t & 31)) & 1u;
+    const uint32_t kt = p256_next_bit(k, t);
     p256_double(r, r);
     p256_add_affine(s, r, X, Y);
     fp_select(r.X, r.X, s.X, kt);
     fp_select(r.Y, r.Y, s.Y, kt);
     fp_select(r.Z, r.Z, s.Z, kt);
   }
+}
+
+// x([k] P) as 8 big-endian words: the ladder, the inversion's 267 products and three more, 443 K
+// products per DH.
+template <class Scalar>
+P3G_P256 void p256_dh_x(const Scalar& k, const Fp256& X, const Fp256& Y, uint32_t out_be[8]) {
+  P256Proj r;
+  p256_ladder(k, X, Y, r);
   Fp256 zi, x;
   fp_inv(zi, r.Z);
   fp_mul(x, r.X, zi);
   fp_from_mont(x, x);
 #pragma unroll
   for (int i = 0; i < 8; ++i) out_be[i] = x.v[7 - i];
+}
+
+// Both affine coordinates of [k] P as 8 big-endian words each (one inversion, two products): what
+// SerializePublicKey writes behind the 0x04 of an encapsulated key.
+template <class Scalar>
+P3G_P256 void p256_mul_xy(const Scalar& k, const Fp256& X, const Fp256& Y, uint32_t x_be[8],
+                          uint32_t y_be[8]) {
+  P256Proj r;
+  p256_ladder(k, X, Y, r);
+  Fp256 zi, x, y;
+  fp_inv(zi, r.Z);
+  fp_mul(x, r.X, zi);
+  fp_mul(y, r.Y, zi);
+  fp_from_mont(x, x);
+  fp_from_mont(y, y);
+#pragma unroll
+  for (int i = 0; i < 8; ++i) x_be[i] = x.v[7 - i], y_be[i] = y.v[7 - i];
+}
+
+// The group order n's limbs, little-endian
+P3G_P256 constexpr uint32_t p256_order(int i) {
+  return i == 0 ? 0xfc632551u : i == 1 ? 0xf3b9cac2u : i == 2 ? 0xa7179e84u : i == 3 ? 0xbce6faadu
+         : i == 6 ? 0u : 0xffffffffu;
+}
+
+// A lane's own scalar from 32 big-endian bytes (any alignment); true iff 1 <= k < n.  A scalar
+// outside that range is replaced by 1, so the ladder's precondition holds and the lane runs the
+// same instructions; its caller zeroes what such a lane computes.  No branch on the value.
+P3G_P256 bool p256_lane_scalar(const uint8_t* be, P256LaneScalar& k) {
+  uint32_t w[8];
+  p256_load_be_words8(be, w);
+  uint32_t nz = 0;
+  int64_t c = 0;
+#pragma unroll
+  for (int i = 0; i < 8; ++i) {
+    k.w[i] = w[7 - i];
+    nz |= k.w[i];
+    c += (int64_t)k.w[i] - (int64_t)p256_order(i);
+    c >>= 32;
+  }
+  const bool ok = (c < 0) & (nz != 0u);  // k - n borrows, and k is not zero
+  const uint32_t m = ok ? 0xffffffffu : 0u;
+#pragma unroll
+  for (int i = 0; i < 8; ++i) k.w[i] = (k.w[i] & m) | (i == 0 ? (~m & 1u) : 0u);
+  return ok;
 }
 
 }  // namespace p3g

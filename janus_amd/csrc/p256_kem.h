@@ -1,7 +1,8 @@
-// The KEM half of DHKEM(P-256, HKDF-SHA256) (RFC 9180 §4.1) over p256.h, and one lane of the DH
-// kernels (hpke_gpu.h: k_p256_dh, helper_request.h: k_p256_dh_idx).  Free of HIP like p256.h; it
-// hashes with sha256.h, device code in a HIP unit and host code in a plain C++ build
-// (tests/native/p256_host.cpp).
+// The KEM half of DHKEM(P-256, HKDF-SHA256) (RFC 9180 §4.1) over p256.h, one lane of the DH
+// kernels (hpke_gpu.h: k_p256_dh, helper_request.h: k_p256_dh_idx) and one lane of the sender's
+// (hpke_seal_gpu.h: k_p256_eph, k_p256_eph_kem).  Free of HIP like p256.h; it hashes with
+// sha256.h, device code in a HIP unit and host code in a plain C++ build
+// (tests/native/p256_host.cpp, tests/native/p256_eph_host.cpp).
 #pragma once
 #include "p256.h"
 #include "sha256.h"
@@ -150,6 +151,34 @@ P3G_P256_DEV bool p256_dh_lane(const P256Scalar& k, const P256PublicKey& pk,
 #pragma unroll
   for (int i = 0; i < 8; ++i) ss[i] &= m;
   return ok;
+}
+
+// One lane of the sender's ladders (hpke_seal_gpu.h: k_p256_eph): (x, y)([sk_e] P) as big-endian
+// words for the report's own ephemeral scalar sk_e (32 big-endian bytes, any alignment) and a valid
+// point P = (X, Y), the generator (the encapsulated key) or the recipient's key (the DH value).
+// Returns whether sk_e is in [1, n); a scalar outside runs the same instructions over 1 and both
+// coordinates are zeroed, as p256_dh_lane does for a refused enc.
+P3G_P256_DEV bool p256_eph_lane(const uint8_t* sk_e, const Fp256& X, const Fp256& Y,
+                                uint32_t x_be[8], uint32_t y_be[8]) {
+  P256LaneScalar k;
+  const bool ok = p256_lane_scalar(sk_e, k);
+  p256_mul_xy(k, X, Y, x_be, y_be);
+  const uint32_t m = ok ? 0xffffffffu : 0u;
+#pragma unroll
+  for (int i = 0; i < 8; ++i) x_be[i] &= m, y_be[i] &= m;
+  return ok;
+}
+
+// The sender's KEM half for one report (k_p256_eph_kem): the shared_secret from dh = x([sk_e] pkR)
+// and enc = 0x04 || ex || ey = [sk_e] G, zeroed for a report whose scalar was refused.
+P3G_P256_DEV void p256_eph_shared_secret(const uint32_t salt0_i[8], const uint32_t salt0_o[8],
+                                         const uint32_t dh[8], const uint32_t ex[8],
+                                         const uint32_t ey[8], const P256PublicKey& pk, bool ok,
+                                         uint32_t ss[8]) {
+  p256_kem_shared_secret(salt0_i, salt0_o, dh, ex, ey, pk, ss);
+  const uint32_t m = ok ? 0xffffffffu : 0u;
+#pragma unroll
+  for (int i = 0; i < 8; ++i) ss[i] &= m;
 }
 
 }  // namespace p3g

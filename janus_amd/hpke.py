@@ -67,6 +67,11 @@ class HpkeKeypair:
     private_key: bytes
 
 
+def enc_len(kem_id: int) -> int:
+    """Nenc of a KEM (RFC 9180 §7.1): 65 for DHKEM(P-256, HKDF-SHA256), 32 for X25519."""
+    return 65 if kem_id == KEM_P256_HKDF_SHA256 else 32
+
+
 def _buf(b: bytes):
     return ctypes.c_char_p(bytes(b)) if b else None
 
@@ -233,7 +238,7 @@ def _seal_batch_gpu(entry: str, gpu, config: HpkeConfig, info: bytes, sk_es, aad
     if cts is None:
         cts = np.zeros(max(1, int(np.asarray(ct_offsets)[-1])), np.uint8)
     if encs is None:
-        encs = np.zeros(max(1, n) * 32, np.uint8)
+        encs = np.zeros(max(1, n) * enc_len(config.kem_id), np.uint8)
     if status is None:
         status = np.zeros(max(1, n), np.uint8)
     keep, args = [], []
@@ -257,18 +262,22 @@ def seal_batch_gpu(gpu, config: HpkeConfig, info: bytes, sk_es, aads, aad_offset
                    n: Optional[int] = None):
     """n HPKE seals to ONE recipient config on the GPU (prio3gpu_hpke_seal_batch), each under its
     own ephemeral private key: any DHKEM(X25519, HKDF-SHA256) suite (KDF HKDF-SHA256 / -SHA384 /
-    -SHA512 x AEAD AES-128-GCM / AES-256-GCM / ChaCha20-Poly1305), no option needed.  `ValueError`
-    for any other suite (P-256 seals stay on `seal`), nothing launched.
+    -SHA512 x AEAD AES-128-GCM / AES-256-GCM / ChaCha20-Poly1305), no option needed; after
+    `gpu.set_option("hpke_gpu_p256", 1)` the same choice under DHKEM(P-256, HKDF-SHA256).
+    `ValueError` for any other suite (P-256 without the option), nothing launched; `HpkeError`
+    for a P-256 public key that is not a point.
 
-    `gpu` is a `Prio3Gpu` or a context handle.  Report i: ephemeral key = sk_es[32 i : 32 i + 32],
+    `gpu` is a `Prio3Gpu` or a context handle.  Report i: ephemeral key = sk_es[32 i : 32 i + 32]
+    (for P-256 a big-endian scalar; one outside [1, n) is that report's failure),
     aad = aads[aad_offsets[i] : aad_offsets[i+1]], plaintext = pts[pt_offsets[i] :
     pt_offsets[i+1]].  Buffers are numpy arrays (host), torch tensors (host or device) or integer
     device pointers (then `n`, `encs`, `cts`, `ct_offsets` and `status` must be given).  By
     default ciphertext i has the plaintext's length + 16 and the ciphertexts are packed.
-    -> (encs, cts, ct_offsets, status): enc i = encs[32 i : 32 i + 32], ciphertext || tag i =
-    cts[ct_offsets[i] : ct_offsets[i+1]] -- the bytes `seal` gives with the same ephemeral key.  A
-    report that is not sealed (status non-zero on entry, a public key of small order, a slot that
-    is too short) has zeros in both and, unless it was skipped, status 4."""
+    -> (encs, cts, ct_offsets, status): enc i = encs[Nenc i : Nenc i + Nenc] with Nenc = 32 for
+    X25519 and 65 for P-256 (`enc_len`), ciphertext || tag i = cts[ct_offsets[i] :
+    ct_offsets[i+1]] -- the bytes `seal` gives with the same ephemeral key.  A report that is not
+    sealed (status non-zero on entry, a public key of small order, an invalid P-256 scalar, a slot
+    that is too short) has zeros in both and, unless it was skipped, status 4."""
     return _seal_batch_gpu("prio3gpu_hpke_seal_batch", gpu, config, info, sk_es, aads,
                            aad_offsets, pts, pt_offsets, status, encs, cts, ct_offsets, n)
 
@@ -279,9 +288,10 @@ def seal_long_batch_gpu(gpu, config: HpkeConfig, info: bytes, sk_es, aads, aad_o
     """`seal_batch_gpu` with one GPU wave per report instead of one lane
     (prio3gpu_hpke_seal_long_batch): for plaintexts of many kilobytes, the leader's input shares.
     DHKEM(X25519, HKDF-SHA256) with any KDF and AES-128-GCM / AES-256-GCM, no option needed, and
-    after `gpu.set_option("hpke_team_chacha", 1)` ChaCha20-Poly1305 too; `ValueError` for any
-    other suite (P-256; ChaCha20-Poly1305 without the option), nothing launched.  Same arguments
-    and the same bytes, offsets and statuses.  -> (encs, cts, ct_offsets, status)."""
+    after `gpu.set_option("hpke_team_chacha", 1)` ChaCha20-Poly1305 too; after
+    `gpu.set_option("hpke_gpu_p256", 1)` the same under DHKEM(P-256, HKDF-SHA256).  `ValueError`
+    for any other suite (P-256 or ChaCha20-Poly1305 without its option), nothing launched.  Same
+    arguments and the same bytes, offsets and statuses.  -> (encs, cts, ct_offsets, status)."""
     return _seal_batch_gpu("prio3gpu_hpke_seal_long_batch", gpu, config, info, sk_es, aads,
                            aad_offsets, pts, pt_offsets, status, encs, cts, ct_offsets, n)
 
@@ -311,15 +321,16 @@ def _seal_input_shares_gpu(entry: str, gpu, task_id: bytes, config: HpkeConfig,
         raise ValueError("TaskId is 32 bytes")
     n, slen = int(input_shares.shape[0]), int(input_shares.shape[1])
     plen = 6 + slen + 16
+    nenc = enc_len(config.kem_id)
     if out_encs is None:
-        out_encs = np.zeros((n, 32), np.uint8)
+        out_encs = np.zeros((n, nenc), np.uint8)
     if out_payloads is None:
         out_payloads = np.zeros((n, plen), np.uint8)
     if status is None:
         status = np.zeros(max(1, n), np.uint8)
     pslen = 0 if public_shares is None else int(public_shares.shape[1])
     p_sh, sh_pitch, k0 = _rows(input_shares, n, slen, "input shares")
-    p_enc, enc_pitch, k1 = _rows(out_encs, n, 32, "out_encs")
+    p_enc, enc_pitch, k1 = _rows(out_encs, n, nenc, "out_encs")
     p_pay, pay_pitch, k2 = _rows(out_payloads, n, plen, "out_payloads")
     assert (k1 is out_encs or k1 is None) and (k2 is out_payloads or k2 is None)
     p_rid, k3 = _dev_ptr(report_ids, np.uint8)
@@ -347,7 +358,8 @@ def seal_input_shares_gpu(gpu, task_id: bytes, config: HpkeConfig, recipient_rol
 
     report_ids (n, 16), public_shares (n, public_share_len) or None, sk_es (n, 32): uint8 numpy
     arrays or torch tensors, packed; times (n,) uint64; input_shares (n, len) uint8 whose rows may
-    be a column slice of a wider buffer, like out_encs (n, 32) and out_payloads (n, 6 + len + 16):
+    be a column slice of a wider buffer, like out_encs (n, Nenc: 32, or 65 for a P-256 config
+    with the context's "hpke_gpu_p256" option) and out_payloads (n, 6 + len + 16):
     only those columns are written (host or device; e.g. the columns of a fixed-stride Report
     buffer; allocated as numpy arrays by default).  -> (out_encs, out_payloads, status); a report
     that is not sealed has zeros in both columns and, unless skipped on entry, status 4."""
@@ -374,8 +386,10 @@ def open_long_batch_gpu(gpu, keypair: HpkeKeypair, info: bytes, encs, aads, aad_
     """`open_batch_gpu` with one GPU wave per report instead of one lane
     (prio3gpu_hpke_open_long_batch): for ciphertexts of many kilobytes, the leader's input shares
     at upload.  DHKEM(X25519, HKDF-SHA256) with any KDF and AES-128-GCM / AES-256-GCM, no option
-    needed, and after `gpu.set_option("hpke_team_chacha", 1)` ChaCha20-Poly1305 too; `ValueError`
-    for any other suite (P-256; ChaCha20-Poly1305 without the option), nothing launched.  Same
+    needed, and after `gpu.set_option("hpke_team_chacha", 1)` ChaCha20-Poly1305 too; after
+    `gpu.set_option("hpke_gpu_p256", 1)` the same under DHKEM(P-256, HKDF-SHA256), with encs 65
+    bytes apart.  `ValueError` for any other suite (P-256 or ChaCha20-Poly1305 without its
+    option), nothing launched; `HpkeError` for a P-256 keypair that is none.  Same
     arguments, plaintexts and statuses; buffers are numpy arrays (host), torch tensors (host or
     device) or integer device pointers (then `n`, `pts`, `pt_offsets` and `status` must be given).
     -> (plaintexts, pt_offsets, status); a failed open has status 4 and zeros."""
@@ -416,7 +430,8 @@ def open_input_shares_gpu(gpu, task_id: bytes, keypair: HpkeKeypair, recipient_r
     must be the PlaintextInputShare with no extensions -- neither frame is built in memory.
 
     report_ids (n, 16), public_shares (n, public_share_len) or None: uint8 numpy arrays or torch
-    tensors, packed; times (n,) uint64; encs (n, 32) and payloads (n, 6 + len + 16) uint8 whose
+    tensors, packed; times (n,) uint64; encs (n, Nenc: 32, or 65 under a P-256 keypair with the
+    context's "hpke_gpu_p256" option) and payloads (n, 6 + len + 16) uint8 whose
     rows may be column slices of a wider buffer (host or device; e.g. the columns of a
     fixed-stride Report matrix), like out_shares (n, len): only those columns are written (a numpy
     array by default).  -> (out_shares, status); status 4 and a zero row for a failed open, 8 and
@@ -436,7 +451,7 @@ def open_input_shares_gpu(gpu, task_id: bytes, keypair: HpkeKeypair, recipient_r
     if status is None:
         status = np.zeros(max(1, n), np.uint8)
     pslen = 0 if public_shares is None else int(public_shares.shape[1])
-    p_enc, enc_pitch, k0 = _rows(encs, n, 32, "encs")
+    p_enc, enc_pitch, k0 = _rows(encs, n, enc_len(c.kem_id), "encs")
     p_pay, pay_pitch, k1 = _rows(payloads, n, plen, "payloads")
     p_out, out_pitch, k2 = _rows(out_shares, n, slen, "out_shares")
     assert k2 is out_shares or k2 is None

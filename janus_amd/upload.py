@@ -21,19 +21,20 @@ from typing import Optional, Sequence
 import numpy as np
 
 from . import hpke as H
-from .client import PLAINTEXT_OVERHEAD, ReportLayout
+from .client import ENC_LEN, PLAINTEXT_OVERHEAD, ReportLayout
 
 ST_UNKNOWN_CONFIG, ST_DECRYPT, ST_INVALID_MESSAGE = 3, 4, 8
 ROW_ALIGN = 128
 
 
-def _gpu_suite(c: H.HpkeConfig, team_chacha: bool = False) -> bool:
-    """The suites prio3gpu_open_input_shares takes: X25519 with AES-GCM, and with the context's
-    "hpke_team_chacha" option (`team_chacha`) ChaCha20-Poly1305 too."""
+def _gpu_suite(c: H.HpkeConfig, team_chacha: bool = False, p256: bool = False) -> bool:
+    """The suites prio3gpu_open_input_shares takes: X25519 with AES-GCM, with the context's
+    "hpke_team_chacha" option (`team_chacha`) ChaCha20-Poly1305 too, and with its "hpke_gpu_p256"
+    option (`p256`) the same under P-256."""
     aeads = (H.AEAD_AES128GCM, H.AEAD_AES256GCM) + \
         ((H.AEAD_CHACHA20POLY1305,) if team_chacha else ())
-    return (c.kem_id == H.KEM_X25519_HKDF_SHA256 and c.kdf_id in (1, 2, 3)
-            and c.aead_id in aeads)
+    kems = (H.KEM_X25519_HKDF_SHA256,) + ((H.KEM_P256_HKDF_SHA256,) if p256 else ())
+    return c.kem_id in kems and c.kdf_id in (1, 2, 3) and c.aead_id in aeads
 
 
 class UploadBatch:
@@ -41,11 +42,16 @@ class UploadBatch:
     `HpkeKeypair`s, and the role this aggregator plays (the leader by default: it is whom clients
     upload to).  `team_chacha` sets the option "hpke_team_chacha" on `vdaf`'s context: key groups
     under ChaCha20-Poly1305 are then opened a GPU wave per report like the AES-GCM ones, not one
-    by one on the host."""
+    by one on the host.  `p256` sets the option "hpke_gpu_p256": key groups under DHKEM(P-256,
+    HKDF-SHA256) are then opened on the GPU too, and the report matrix has this aggregator's
+    encapsulated keys at the length of its first key's KEM (65 bytes for P-256) and the other
+    aggregator's at `peer_enc` bytes (32, or 65 when that one's key is P-256) -- the layout
+    `ClientBatch(p256=True)` writes.  Without it the layout and the routing are unchanged: a
+    P-256 key group is opened on the host."""
 
     def __init__(self, vdaf, task_id: bytes, task_keys: Sequence[H.HpkeKeypair],
                  global_keys: Sequence[H.HpkeKeypair] = (), role: int = H.ROLE_LEADER,
-                 team_chacha: bool = False):
+                 team_chacha: bool = False, p256: bool = False, peer_enc: int = ENC_LEN):
         if len(task_id) != 32:
             raise ValueError("TaskId is 32 bytes")
         if role not in (H.ROLE_LEADER, H.ROLE_HELPER):
@@ -53,13 +59,23 @@ class UploadBatch:
         self.team_chacha = bool(team_chacha)
         if self.team_chacha:
             vdaf.set_option("hpke_team_chacha", 1)
+        self.p256 = bool(p256)
+        if self.p256:
+            vdaf.set_option("hpke_gpu_p256", 1)
         self.vdaf, self.task_id, self.role = vdaf, bytes(task_id), role
         self.task_keys, self.global_keys = {}, {}
         for table, kps in ((self.task_keys, task_keys), (self.global_keys, global_keys)):
             for kp in kps:
                 table.setdefault(kp.config.id, kp)   # the first key of an id wins
         s = vdaf.sizes
-        self.layout = ReportLayout(s.public_share, s.leader_input_share, s.helper_input_share)
+        own_enc = ENC_LEN
+        if self.p256:   # this batch's enc length: the KEM of the first key, task keys first
+            for kp in list(task_keys) + list(global_keys):
+                own_enc = H.enc_len(kp.config.kem_id)
+                break
+        encs = (own_enc, int(peer_enc)) if role == H.ROLE_LEADER else (int(peer_enc), own_enc)
+        self.layout = ReportLayout(s.public_share, s.leader_input_share, s.helper_input_share,
+                                   *encs)
         self.which = "leader" if role == H.ROLE_LEADER else "helper"
         self.share_len = s.leader_input_share if role == H.ROLE_LEADER else s.helper_input_share
         self.pitch = max(ROW_ALIGN, -(-self.share_len // ROW_ALIGN) * ROW_ALIGN)
@@ -103,13 +119,13 @@ class UploadBatch:
         failure, `ValueError` for a plaintext that is not an extension-free share of the VDAF's
         length (the caller's status 8)."""
         L = self.layout
-        oe, op, pl = ((L.o_leader_enc, L.o_leader_payload, L.leader_payload)
-                      if self.which == "leader" else
-                      (L.o_helper_enc, L.o_helper_payload, L.helper_payload))
+        oe, op, pl, ne = ((L.o_leader_enc, L.o_leader_payload, L.leader_payload, L.leader_enc)
+                          if self.which == "leader" else
+                          (L.o_helper_enc, L.o_helper_payload, L.helper_payload, L.helper_enc))
         aad = H.input_share_aad(self.task_id, report[:16], time,
                                 report[L.o_public:L.o_public + L.public_share])
         try:
-            pt = H.open_(kp, self.info, report[oe:oe + 32], report[op:op + pl], aad)
+            pt = H.open_(kp, self.info, report[oe:oe + ne], report[op:op + pl], aad)
         except (H.HpkeError, ValueError):
             return None
         if pt[:PLAINTEXT_OVERHEAD] != b"\0\0" + struct.pack(">I", self.share_len) or \
@@ -179,7 +195,9 @@ class UploadBatch:
             first[int(cid)] = kp
             if kp is None:
                 status[idx] = ST_UNKNOWN_CONFIG
-            elif _gpu_suite(kp.config, self.team_chacha):
+            elif _gpu_suite(kp.config, self.team_chacha, self.p256) and \
+                    H.enc_len(kp.config.kem_id) == (L.leader_enc if self.which == "leader"
+                                                    else L.helper_enc):
                 self._open_group(kp, reports, idx, ids, times, rows, status)
             else:
                 self._host_rows(lambda i, kp=kp: kp, reports, idx, times, rows, status)

@@ -39,7 +39,8 @@ import torch  # noqa: E402
 
 from janus_amd import hpke as H  # noqa: E402
 from janus_amd._lib import lib  # noqa: E402
-from janus_amd.client import ClientBatch, encode_plaintext_input_share  # noqa: E402
+from janus_amd.client import (ClientBatch, draw_p256_scalars,  # noqa: E402
+                              encode_plaintext_input_share)
 from janus_amd.prio3 import Prio3Gpu  # noqa: E402
 
 TASK_ID = hashlib.sha256(b"client seal bench").digest()
@@ -60,17 +61,25 @@ def stage_ms(v, fn):
             for i in range(k) if launches[i]}
 
 
+def ephemeral_keys(rng, config, n):
+    """(n, 32) ephemeral private keys for `config`'s KEM: any bytes for X25519, big-endian
+    scalars in [1, n) for P-256."""
+    if config.kem_id == H.KEM_P256_HKDF_SHA256:
+        return draw_p256_scalars(n, lambda k: rng.integers(0, 256, k, dtype=np.uint8).tobytes())
+    return rng.integers(0, 256, (n, 32), dtype=np.uint8)
+
+
 def seal_case(v, kp, role, n, slen, pub_len, reps, host_n, rng, dev):
     """seals/s of seal_input_shares_gpu over n device rows of slen bytes, and of the host loop
     over the first host_n of them, rep by rep in turn."""
     ids = rng.integers(0, 256, (n, 16), dtype=np.uint8)
     times = np.full(n, 1_700_000_000, np.uint64)
     pub = rng.integers(0, 256, (n, pub_len), dtype=np.uint8)
-    sk = rng.integers(0, 256, (n, 32), dtype=np.uint8)
+    sk = ephemeral_keys(rng, kp.config, n)
     d_shares = torch.randint(0, 256, (n, slen), dtype=torch.uint8, device=dev)
     d_ids, d_pub, d_sk = (torch.from_numpy(a).to(dev) for a in (ids, pub, sk))
     d_times = torch.from_numpy(times.view(np.int64)).to(dev)
-    d_encs = torch.empty((n, 32), dtype=torch.uint8, device=dev)
+    d_encs = torch.empty((n, H.enc_len(kp.config.kem_id)), dtype=torch.uint8, device=dev)
     d_pay = torch.empty((n, 6 + slen + 16), dtype=torch.uint8, device=dev)
     info = H.application_info(H.Label.INPUT_SHARE, H.ROLE_CLIENT, role)
 
@@ -132,12 +141,12 @@ def long_case(v, kp, role, n, slen, pub_len, reps, rng, dev):
     ids = rng.integers(0, 256, (n, 16), dtype=np.uint8)
     times = np.full(n, 1_700_000_000, np.uint64)
     pub = rng.integers(0, 256, (n, pub_len), dtype=np.uint8)
-    sk = rng.integers(0, 256, (n, 32), dtype=np.uint8)
+    sk = ephemeral_keys(rng, kp.config, n)
     d_shares = torch.randint(0, 256, (n, slen), dtype=torch.uint8, device=dev)
     d_ids, d_pub, d_sk = (torch.from_numpy(a).to(dev) for a in (ids, pub, sk))
     d_times = torch.from_numpy(times.view(np.int64)).to(dev)
     plen = 6 + slen + 16
-    outs = {k: (torch.empty((n, 32), dtype=torch.uint8, device=dev),
+    outs = {k: (torch.empty((n, H.enc_len(kp.config.kem_id)), dtype=torch.uint8, device=dev),
                 torch.empty((n, plen), dtype=torch.uint8, device=dev)) for k in ("wave", "lane")}
     fns = {"wave": H.seal_input_shares_long_gpu, "lane": H.seal_input_shares_gpu}
 
@@ -177,7 +186,8 @@ def long_main(args, v, lkp, hkp, rng, dev):
     s = v.sizes
     aead = {1: "AES-128-GCM", 2: "AES-256-GCM", 3: "ChaCha20-Poly1305"}[args.aead]
     attr = "LONG_SEAL_MIN_SHARE_CHACHA" if args.aead == 3 else "LONG_SEAL_MIN_SHARE"
-    out = {"what": "client seal on one GPU, a wave per report beside a lane per report: X25519 / "
+    kem = "P-256" if args.kem == H.KEM_P256_HKDF_SHA256 else "X25519"
+    out = {"what": f"client seal on one GPU, a wave per report beside a lane per report: {kem} / "
                    f"HKDF-SHA256 / {aead} seals of Prio3 input shares from device rows, the "
                    "two paths alternating over the same inputs (outputs asserted equal), host "
                    "clock around a synchronise, median of reps with min..max; and whole "
@@ -204,11 +214,13 @@ def long_main(args, v, lkp, hkp, rng, dev):
     meas = rng.integers(0, 256, (n, 1000), dtype=np.int64)
     ids = rng.integers(0, 256, (n, 16), dtype=np.uint8)
     rand = rng.integers(0, 256, (n, v.random_size()), dtype=np.uint8)
-    sk = rng.integers(0, 256, (2, n, 32), dtype=np.uint8)
+    sk = np.stack([ephemeral_keys(rng, lkp.config, n), ephemeral_keys(rng, hkp.config, n)])
     times = np.full(n, 1_700_000_000, np.uint64)
-    chacha = args.aead == 3
-    cbs = {"lane": ClientBatch(v, TASK_ID, lkp.config, hkp.config, 3600, long_seal=False),
-           "auto": ClientBatch(v, TASK_ID, lkp.config, hkp.config, 3600, team_chacha=chacha)}
+    chacha, p256 = args.aead == 3, args.kem == H.KEM_P256_HKDF_SHA256
+    cbs = {"lane": ClientBatch(v, TASK_ID, lkp.config, hkp.config, 3600, long_seal=False,
+                               p256=p256),
+           "auto": ClientBatch(v, TASK_ID, lkp.config, hkp.config, 3600, team_chacha=chacha,
+                               p256=p256)}
 
     def prepare(k):
         r = cbs[k].prepare_reports(meas, report_ids=ids, times=times, rand=rand, sk_es=sk,
@@ -251,6 +263,9 @@ def main():
     ap.add_argument("--aead", type=int, choices=(1, 2, 3), default=1,
                     help="with --long: both aggregators' AEAD; 3 (ChaCha20-Poly1305) sets the "
                          'context option "hpke_team_chacha"')
+    ap.add_argument("--kem", type=lambda x: int(x, 0), choices=(0x20, 0x10), default=0x20,
+                    help='both aggregators\' KEM; 0x10 (P-256) sets the context option '
+                         '"hpke_gpu_p256"')
     ap.add_argument("--out", help="append the JSON line to this file as well")
     args = ap.parse_args()
     if args.long:
@@ -259,7 +274,9 @@ def main():
         v = Prio3Gpu.new_sum_vec(8, 1000, 89, vk, device=0)
         if args.aead == 3:
             v.set_option("hpke_team_chacha", 1)
-        X = H.KEM_X25519_HKDF_SHA256
+        if args.kem == H.KEM_P256_HKDF_SHA256:
+            v.set_option("hpke_gpu_p256", 1)
+        X = args.kem
         line = json.dumps(long_main(args, v,
                                     H.generate_hpke_config_and_private_key(1, X, 1, args.aead),
                                     H.generate_hpke_config_and_private_key(2, X, 1, args.aead),
@@ -275,9 +292,13 @@ def main():
     vk = hashlib.shake_128(b"verify-key client seal").digest(16)
     v = Prio3Gpu.new_sum_vec(8, 1000, 89, vk, device=0)
     s = v.sizes
-    lkp = H.generate_hpke_config_and_private_key(1)
-    hkp = H.generate_hpke_config_and_private_key(2)
-    out = {"what": "client seal on one GPU: X25519 / HKDF-SHA256 / AES-128-GCM seals of Prio3 "
+    p256 = args.kem == H.KEM_P256_HKDF_SHA256
+    if p256:
+        v.set_option("hpke_gpu_p256", 1)
+    lkp = H.generate_hpke_config_and_private_key(1, args.kem)
+    hkp = H.generate_hpke_config_and_private_key(2, args.kem)
+    out = {"what": f"client seal on one GPU: {'P-256' if p256 else 'X25519'} / HKDF-SHA256 / "
+                   "AES-128-GCM seals of Prio3 "
                    "input shares from device rows, whole Prio3SumVec(8, 1000, 89) reports, and "
                    "the host's per-report seal loop over the same inputs",
            "reps": args.reps}
@@ -288,7 +309,7 @@ def main():
     out["leader_share"] = seal_case(v, lkp, H.ROLE_LEADER, args.leader_n, s.leader_input_share,
                                     s.public_share, args.reps, min(64, args.leader_n), rng, dev)
     n = args.reports_n
-    cb = ClientBatch(v, TASK_ID, lkp.config, hkp.config, 3600)
+    cb = ClientBatch(v, TASK_ID, lkp.config, hkp.config, 3600, p256=p256)
     meas = rng.integers(0, 256, (n, 1000), dtype=np.int64)
     cb.prepare_reports(meas[:256])                              # warm-up
     rep_s = []
@@ -305,7 +326,11 @@ def main():
     assert tuple(r.shape) == (n, cb.report_len)
     cb.close()
     v.close()
-    print(json.dumps(out), flush=True)
+    line = json.dumps(out)
+    print(line, flush=True)
+    if args.out:
+        with open(args.out, "a") as f:
+            f.write(line + "\n")
 
 
 if __name__ == "__main__":

@@ -33,6 +33,7 @@ import torch  # noqa: E402
 
 from janus_amd import hpke as H  # noqa: E402
 from janus_amd._lib import lib  # noqa: E402
+from janus_amd.client import draw_p256_scalars  # noqa: E402
 from janus_amd.prio3 import Prio3Gpu  # noqa: E402
 
 TASK_ID = hashlib.sha256(b"upload open bench").digest()
@@ -66,10 +67,13 @@ def open_case(v, kp, case, n, slen, reps, rng, dev, host_n=0):
     times = np.full(n, 1_700_000_000, np.uint64)
     pub = rng.integers(0, 256, (n, PUB_LEN), dtype=np.uint8)
     sk = rng.integers(0, 256, (n, 32), dtype=np.uint8)
+    nenc = H.enc_len(kp.config.kem_id)
+    if nenc == 65:    # P-256: scalars in [1, n)
+        sk = draw_p256_scalars(n, lambda k: rng.integers(0, 256, k, dtype=np.uint8).tobytes())
     d_shares = torch.randint(0, 256, (n, slen), dtype=torch.uint8, device=dev)
     d_ids, d_pub, d_sk = (torch.from_numpy(a).to(dev) for a in (ids, pub, sk))
     d_times = torch.from_numpy(times.view(np.int64)).to(dev)
-    d_encs = torch.empty((n, 32), dtype=torch.uint8, device=dev)
+    d_encs = torch.empty((n, nenc), dtype=torch.uint8, device=dev)
     d_pay = torch.empty((n, plen), dtype=torch.uint8, device=dev)
     torch.cuda.synchronize()
     _, _, st = H.seal_input_shares_gpu(v, TASK_ID, kp.config, role, d_ids, d_times, d_pub,
@@ -130,7 +134,8 @@ def open_case(v, kp, case, n, slen, reps, rng, dev, host_n=0):
         assert pt[6:] == h_shares[i].tobytes()
     host_ms = 1e3 * (time.perf_counter() - t)
     aead = {1: "AES-128-GCM", 2: "AES-256-GCM", 3: "ChaCha20-Poly1305"}[kp.config.aead_id]
-    return {"case": case, "suite": "X25519 / HKDF-SHA256 / " + aead, "n": n,
+    kem = "P-256" if nenc == 65 else "X25519"
+    return {"case": case, "suite": kem + " / HKDF-SHA256 / " + aead, "n": n,
             "payload_bytes": plen, "reps": reps, "host_loop_n": host_n,
             "host_loop_opens_per_s": round(host_n / host_ms * 1e3) if host_n else None,
             "wave_per_report_ms": spread(team_ms), "lane_per_report_ms": spread(lane_ms),
@@ -149,6 +154,8 @@ def main():
     ap.add_argument("--aead", type=int, choices=(1, 2, 3), default=1,
                     help="the key's AEAD; 2 and 3 set \"hpke_gpu_suites\" for the lane path, 3 "
                          "(ChaCha20-Poly1305) also \"hpke_team_chacha\" for the wave path")
+    ap.add_argument("--kem", type=lambda x: int(x, 0), choices=(0x20, 0x10), default=0x20,
+                    help="the key's KEM; 0x10 (P-256) sets \"hpke_gpu_p256\"")
     ap.add_argument("--host-n", type=int, default=256,
                     help="reports of the host's open loop, once (0: none)")
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "upload_open",
@@ -161,7 +168,9 @@ def main():
         v.set_option("hpke_gpu_suites", 1)
     if args.aead == 3:
         v.set_option("hpke_team_chacha", 1)
-    kp = H.generate_hpke_config_and_private_key(1, H.KEM_X25519_HKDF_SHA256, 1, args.aead)
+    if args.kem == H.KEM_P256_HKDF_SHA256:
+        v.set_option("hpke_gpu_p256", 1)
+    kp = H.generate_hpke_config_and_private_key(1, args.kem, 1, args.aead)
     os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
     for case, n, slen in (("leader", args.leader_n, 134_944), ("helper", args.helper_n, 48)):
         if n <= 0:
