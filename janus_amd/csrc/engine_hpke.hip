@@ -1,15 +1,20 @@
-// Host side of the GPU HPKE open and of the helper's aggregate-init from the request's bytes
-// (include/prio3gpu.h: prio3gpu_hpke_open_batch, prio3gpu_hpke_open_report_shares_gpu,
-// prio3gpu_helper_init_request), of the wave-per-report open of long ciphertexts
-// (prio3gpu_hpke_open_long_batch, prio3gpu_open_input_shares), of the GPU HPKE seal
-// (prio3gpu_hpke_seal_batch, prio3gpu_seal_input_shares), of its wave-per-report form for long
-// plaintexts (prio3gpu_hpke_seal_long_batch, prio3gpu_seal_input_shares_long) and the test hooks
-// that launch only their kernels.  No Prio3
+// Host side of the GPU HPKE paths (include/prio3gpu.h) and the test hooks that launch only their
+// kernels.  The opens: prio3gpu_hpke_open_batch (a lane per report) and prio3gpu_hpke_open_long_
+// batch (a wave per report) share hpke_open_batch_entry; prio3gpu_open_input_shares opens share
+// rows in place; prio3gpu_hpke_open_report_shares_gpu packs a request's key groups for the first.
+// The seals: prio3gpu_hpke_seal_batch / _long_batch share hpke_seal_batch_entry, prio3gpu_seal_
+// input_shares / _long share seal_input_shares_entry.  prio3gpu_helper_init_request is the
+// helper's aggregate-init from the request's bytes, in steps req_plan ... req_host_fallback.
+// Every call refuses in one order: null context, suite, keys, n == 0, null arguments, pitches.
+// The context's scratch is named in engine_internal.h; a call's per-report secrets in it belong
+// to one CallSecrets (below), which states what every path keeps about them.  The suite
+// predicates and the column geometry are plan_hpke.h's (no HIP, tested on the CPU).  No Prio3
 // kernel is in scope here: the request path hands over to the Prio3 side (engine.hip) through the
 // public prio3gpu_helper_init alone.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
+#include <cassert>
 #include <cstring>
 #include <string>
 #include <thread>
@@ -50,6 +55,72 @@ void wipe(void* p, size_t n) {  // a memset the compiler may not drop
   memset(p, 0, n);
   __asm__ __volatile__("" : : "r"(p) : "memory");
 }
+
+// The per-report secrets of the current call that lie in the engine's own memory, and their end:
+// regions of the context's scratch and host vectors.  What every GPU HPKE call keeps:
+//  I1. A region is added before the copy or kernel that fills it is queued, and from then on
+//      every way out of the call goes through finish(), which zeroes it on the stream: after a
+//      failed launch and a failed later step too.
+//  I2. A caller's own device buffer, read in place, is never added and so never written:
+//      stage_secret adds a region only when the engine's buffer was used.
+//  I3. finish() comes before any copy-out to the caller, so DH values, ephemeral keys and staged
+//      plaintext inputs are cleared first.  Only staged output rows (prio3gpu_open_input_shares,
+//      the DH test hooks) are added for a second finish() after their copy.
+//  I4. With a non-zero rc the stream is synchronised before finish() returns, and rc and its
+//      message stay the first error's; a failed clear on an otherwise good call is
+//      PRIO3GPU_E_HIP.
+struct CallSecrets {
+  struct Span {
+    void* p;
+    size_t bytes;
+  };
+  Span dev[4];
+  std::vector<uint8_t>* host[3];
+  int n_dev = 0, n_host = 0;
+  void add(void* p, size_t bytes) {
+    assert(n_dev < 4);
+    if (p && bytes) dev[n_dev++] = {p, bytes};
+  }
+  void add(std::vector<uint8_t>& v) {
+    assert(n_host < 3);
+    host[n_host++] = &v;
+  }
+  // Ends what was added, after the call's steps so far ended with rc; nothing is left added.
+  int finish(prio3gpu_ctx* c, int rc) {
+    bool cleared = true, host_read = false;
+    for (int i = 0; i < n_dev; ++i)
+      cleared &= hipMemsetAsync(dev[i].p, 0, dev[i].bytes, c->stream) == hipSuccess;
+    if (!cleared && !rc) {
+      set_err("clearing the call's per-report secrets on the device failed");
+      rc = PRIO3GPU_E_HIP;
+    }
+    for (int i = 0; i < n_host; ++i) host_read |= !host[i]->empty();  // queued copies read them
+    if (rc || host_read) (void)hipStreamSynchronize(c->stream);
+    for (int i = 0; i < n_host; ++i) wipe(host[i]->data(), host[i]->size());
+    n_dev = n_host = 0;
+    return rc;
+  }
+};
+
+// stage_in of a secret input: the engine's copy of it (none where the caller's device buffer is
+// read in place, I2) is the call's to clear.
+int stage_secret(prio3gpu_ctx* c, CallSecrets& sec, DevBuf& buf, const void* src, size_t bytes,
+                 const uint8_t** out) {
+  *out = nullptr;
+  const int rc = stage_in(c, buf, src, bytes, out, kHpkeMinStage);
+  if (*out && *out == buf.u8()) sec.add(buf.p, bytes);
+  return rc;
+}
+
+// The open's DH scratch of n reports: 32 bytes each (X25519: the DH value; P-256: the shared
+// secret), then for P-256 one validity byte each.
+size_t dh_bytes(size_t n, bool p256) { return n * (p256 ? 33 : 32); }
+uint8_t* dh_ok_at(void* d_dh, size_t n) { return static_cast<uint8_t*>(d_dh) + n * 32; }
+
+// The seal ladders' output for n reports: X25519 n encapsulated keys, then n DH values, 32 bytes
+// each; P-256 hpke_seal_gpu.h's layout, whose validity bytes follow the 96 n bytes of both.
+size_t eph_bytes(size_t n, bool p256) { return n * (p256 ? kP256EphBytes : 64); }
+uint8_t* p256_eph_ok_at(void* d_eph, size_t n) { return static_cast<uint8_t*>(d_eph) + n * 96; }
 
 // f(i) for i in [0, n) on up to `threads` host threads (<= 0: all cores), contiguous ranges.
 template <class F>
@@ -104,20 +175,27 @@ int launch_x25519_idx(prio3gpu_ctx* c, const uint8_t* sk, size_t m, const uint32
   });
 }
 
+// A P-256 batch's constants: the coordinates of pk (pkRm of an open, pkR of a seal) and the empty
+// salt's pad states of bc.
+P256DhConsts p256_dh_consts(const uint8_t* pk, const HpkeBatchConsts& bc) {
+  P256DhConsts dc;
+  p256_load_be_words8(pk + 1, dc.pk.x);
+  p256_load_be_words8(pk + 33, dc.pk.y);
+  memcpy(dc.salt0_i, bc.salt0_i, sizeof dc.salt0_i);
+  memcpy(dc.salt0_o, bc.salt0_o, sizeof dc.salt0_o);
+  return dc;
+}
+
 // launch(ks, dc) with sk as a P-256 scalar (little-endian words from the 32 big-endian bytes) and
-// the batch's constants: pkRm's coordinates and the empty salt's pad states of bc.  The keypair
-// has passed p256_keypair_valid.  The scalar's host copy is wiped after the launch.
+// the batch's constants.  The keypair has passed p256_keypair_valid.  The scalar's host copy is
+// wiped after the launch.
 template <class F>
 int with_p256_scalar(const uint8_t* sk, const uint8_t* pk, const HpkeBatchConsts& bc, F&& launch) {
   P256Scalar ks;
   for (int i = 0; i < 8; ++i)
     ks.w[i] = (uint32_t)sk[31 - 4 * i] | ((uint32_t)sk[30 - 4 * i] << 8) |
               ((uint32_t)sk[29 - 4 * i] << 16) | ((uint32_t)sk[28 - 4 * i] << 24);
-  P256DhConsts dc;
-  p256_load_be_words8(pk + 1, dc.pk.x);
-  p256_load_be_words8(pk + 33, dc.pk.y);
-  memcpy(dc.salt0_i, bc.salt0_i, sizeof dc.salt0_i);
-  memcpy(dc.salt0_o, bc.salt0_o, sizeof dc.salt0_o);
+  const P256DhConsts dc = p256_dh_consts(pk, bc);
   launch(ks, dc);
   wipe(&ks, sizeof ks);
   HIPCHK(hipGetLastError());
@@ -147,6 +225,22 @@ int launch_p256_dh_idx(prio3gpu_ctx* c, const uint8_t* sk, const uint8_t* pk,
   });
 }
 
+// The DH step of an open under one keypair: the n packed encapsulated keys at d_points to the
+// context's DH scratch (*d_dh), which is the call's secret from here on.  P-256: the shared
+// secrets (raw: the x coordinates) and the validity bytes, which bc.dh_ok points at.
+int open_dh(prio3gpu_ctx* c, CallSecrets& sec, uint16_t kem_id, const uint8_t* sk,
+            const uint8_t* pk, HpkeBatchConsts& bc, bool raw, size_t n, const uint8_t* d_points,
+            uint32_t** d_dh) {
+  const bool p256 = kem_id == 0x0010;
+  CHK(c->hpke.dh.ensure(dh_bytes(n, p256)));
+  *d_dh = static_cast<uint32_t*>(c->hpke.dh.p);
+  sec.add(*d_dh, dh_bytes(n, p256));
+  if (!p256) return launch_x25519(c, sk, n, d_points, *d_dh);
+  uint8_t* d_ok = dh_ok_at(*d_dh, n);
+  bc.dh_ok = d_ok;
+  return launch_p256_dh(c, sk, pk, bc, raw, n, d_points, *d_dh, d_ok);
+}
+
 // check_request_views (plan_hpke.h) with its message in the thread's error string.
 int check_views(const Cfg& g, const prio3gpu_prepare_init_view* views, size_t n, size_t msg_len) {
   std::string err;
@@ -170,15 +264,26 @@ int launch_req_gather(prio3gpu_ctx* c, size_t n, const uint8_t* d_msg, size_t ms
   return 0;
 }
 
-// The suites the GPU opens on this context (plan_hpke.h).
+// The context's options as plan_hpke.h's mask, and the suite check of an entry point under them:
+// a wave per report (`team`) is hpke_team_suite's for opens and seals alike; a lane per report is
+// hpke_gpu_suite's for an open and hpke_seal_suite's for a seal.
 unsigned hpke_gpu_opts(const prio3gpu_ctx* c) {
-  return (c->hpke_gpu_suites ? HPKE_OPT_SUITES : 0u) | (c->hpke_gpu_p256 ? HPKE_OPT_P256 : 0u);
+  return (c->hpke_gpu_suites ? HPKE_OPT_SUITES : 0u) | (c->hpke_gpu_p256 ? HPKE_OPT_P256 : 0u) |
+         (c->hpke_team_chacha ? HPKE_OPT_TEAM_CHACHA : 0u);
 }
-bool hpke_gpu_suite(const prio3gpu_ctx* c, uint16_t kem, uint16_t kdf, uint16_t aead) {
-  return p3g::hpke_gpu_suite(hpke_gpu_opts(c), kem, kdf, aead);
+int suite_check(const prio3gpu_ctx* c, const char* who, bool seal, bool team, uint16_t kem,
+                uint16_t kdf, uint16_t aead) {
+  const unsigned o = hpke_gpu_opts(c);
+  if (team ? hpke_team_suite(o, kem, kdf, aead)
+           : seal ? hpke_seal_suite(o, kem, kdf, aead) : hpke_gpu_suite(o, kem, kdf, aead))
+    return 0;
+  set_err("%s: HPKE suite 0x%04x/%u/%u is not taken %s on this context", who, kem, kdf, aead,
+          team ? "a wave per report" : "a lane per report");
+  return PRIO3GPU_E_UNSUPPORTED;
 }
 
-// f(KDF, AEAD) with the suite of bc as compile-time constants (one kernel instantiation each).
+// f(KDF, AEAD) with the suite of bc as compile-time constants (one kernel instantiation each of
+// the nine pairs; the entry points have checked the suite, so no other value arrives).
 template <class F>
 void hpke_suite_dispatch(const HpkeBatchConsts& bc, F&& f) {
   auto with_aead = [&](auto kdf) {
@@ -189,83 +294,6 @@ void hpke_suite_dispatch(const HpkeBatchConsts& bc, F&& f) {
   if (bc.kdf_id == 1) with_aead(std::integral_constant<int, 1>{});
   else if (bc.kdf_id == 2) with_aead(std::integral_constant<int, 2>{});
   else with_aead(std::integral_constant<int, 3>{});
-}
-
-// The suites the wave-per-report opens and seals take (hpke_open_team.h, hpke_seal_team.h; they
-// have entry points of their own): DHKEM(X25519, HKDF-SHA256) with KDF 1-3 and AES-128-GCM /
-// AES-256-GCM, and with the context's "hpke_team_chacha" option ChaCha20-Poly1305 too; with its
-// "hpke_gpu_p256" option the same under DHKEM(P-256, HKDF-SHA256).
-bool hpke_team_suite(const prio3gpu_ctx* c, uint16_t kem, uint16_t kdf, uint16_t aead) {
-  return (kem == 0x0020 || (kem == 0x0010 && c->hpke_gpu_p256)) && kdf >= 1 && kdf <= 3 &&
-         (aead == 1 || aead == 2 || (aead == 3 && c->hpke_team_chacha));
-}
-
-// f(KDF, AEAD) for such a suite (the entry points have checked it with hpke_team_suite); the
-// ChaCha20-Poly1305 instantiations are reached with the context's option only.
-template <class F>
-void hpke_team_dispatch(const prio3gpu_ctx* c, const HpkeBatchConsts& bc, F&& f) {
-  auto with_aead = [&](auto kdf) {
-    if (bc.aead_id == 1) f(kdf, std::integral_constant<int, 1>{});
-    else if (bc.aead_id == 2) f(kdf, std::integral_constant<int, 2>{});
-    else if (c->hpke_team_chacha) f(kdf, std::integral_constant<int, 3>{});
-  };
-  if (bc.kdf_id == 1) with_aead(std::integral_constant<int, 1>{});
-  else if (bc.kdf_id == 2) with_aead(std::integral_constant<int, 2>{});
-  else with_aead(std::integral_constant<int, 3>{});
-}
-
-// k_hpke_open_team, instantiated for the suite of bc: k_hpke_open's arguments, a wave per report.
-int launch_hpke_open_team(prio3gpu_ctx* c, const HpkeBatchConsts& bc, size_t n,
-                          const uint32_t* d_dh, const uint8_t* d_enc, const uint8_t* d_aad,
-                          const uint64_t* d_aoff, uint64_t aad_total, const uint8_t* d_ct,
-                          const uint64_t* d_coff, uint64_t ct_total, uint8_t* d_pt,
-                          const uint64_t* d_poff, uint64_t pt_total, uint8_t* d_st) {
-  {
-    PROF(KID_HPKE_OPEN_TEAM);
-    hpke_team_dispatch(c, bc, [&](auto kdf, auto aead) {
-      hipLaunchKernelGGL((k_hpke_open_team<decltype(kdf)::value, decltype(aead)::value>),
-                         dim3((unsigned)((n + kTeamsPerBlock - 1) / kTeamsPerBlock)), dim3(256), 0,
-                         c->stream, (uint32_t)n, bc, d_dh, d_enc, d_aad, d_aoff, aad_total, d_ct,
-                         d_coff, ct_total, d_pt, d_poff, pt_total, d_st);
-    });
-  }
-  HIPCHK(hipGetLastError());
-  return 0;
-}
-
-// k_hpke_open / k_hpke_open_req, instantiated for the suite of bc.
-int launch_hpke_open(prio3gpu_ctx* c, const HpkeBatchConsts& bc, size_t n, const uint32_t* d_dh,
-                     const uint8_t* d_enc, const uint8_t* d_aad, const uint64_t* d_aoff,
-                     uint64_t aad_total, const uint8_t* d_ct, const uint64_t* d_coff,
-                     uint64_t ct_total, uint8_t* d_pt, const uint64_t* d_poff, uint64_t pt_total,
-                     uint8_t* d_st) {
-  {
-    PROF(KID_HPKE_OPEN);
-    hpke_suite_dispatch(bc, [&](auto kdf, auto aead) {
-      hipLaunchKernelGGL((k_hpke_open<decltype(kdf)::value, decltype(aead)::value>),
-                         dim3((unsigned)((n + 255) / 256)), dim3(256), 0, c->stream, (uint32_t)n,
-                         bc, d_dh, d_enc, d_aad, d_aoff, aad_total, d_ct, d_coff, ct_total, d_pt,
-                         d_poff, pt_total, d_st);
-    });
-  }
-  HIPCHK(hipGetLastError());
-  return 0;
-}
-
-int launch_hpke_open_req(prio3gpu_ctx* c, const HpkeBatchConsts& bc, const ReqTaskId& tid,
-                         size_t m, const uint32_t* d_idx, const uint32_t* d_dh,
-                         const uint8_t* d_msg, const ReqView* d_views, uint8_t* d_pts,
-                         const uint64_t* d_poff, uint8_t* d_status) {
-  {
-    PROF(KID_HPKE_OPEN_REQ);
-    hpke_suite_dispatch(bc, [&](auto kdf, auto aead) {
-      hipLaunchKernelGGL((k_hpke_open_req<decltype(kdf)::value, decltype(aead)::value>),
-                         dim3((unsigned)((m + 255) / 256)), dim3(256), 0, c->stream, (uint32_t)m,
-                         bc, tid, d_idx, d_dh, d_msg, d_views, d_pts, d_poff, d_status);
-    });
-  }
-  HIPCHK(hipGetLastError());
-  return 0;
 }
 
 int hpke_open_batch_impl(prio3gpu_ctx* c, uint16_t kem_id, uint16_t kdf_id, uint16_t aead_id,
@@ -279,7 +307,6 @@ int hpke_open_batch_impl(prio3gpu_ctx* c, uint16_t kem_id, uint16_t kdf_id, uint
     set_err("HPKE primitives unavailable");
     return PRIO3GPU_E_UNSUPPORTED;
   }
-  const bool p256 = kem_id == 0x0010;
   HIPCHK(hipSetDevice(c->device));
   uint64_t aad_total = 0, ct_total = 0, pt_total = 0, pt_first = 0;
   CHK(hpke_fetch_u64(c, aad_offsets + n, &aad_total));
@@ -291,52 +318,97 @@ int hpke_open_batch_impl(prio3gpu_ctx* c, uint16_t kem_id, uint16_t kdf_id, uint
     return PRIO3GPU_E_ARG;
   }
   const uint8_t *d_enc, *d_aad, *d_aoff, *d_ct, *d_coff, *d_poff, *d_st_in;
-  CHK(stage_in(c, c->hpke[0], encs, n * bc.nenc, &d_enc, kHpkeMinStage));
-  CHK(stage_in(c, c->hpke[1], aads, aad_total, &d_aad, kHpkeMinStage));
-  CHK(stage_in(c, c->hpke[2], aad_offsets, (n + 1) * 8, &d_aoff, kHpkeMinStage));
-  CHK(stage_in(c, c->hpke[3], cts, ct_total, &d_ct, kHpkeMinStage));
-  CHK(stage_in(c, c->hpke[4], ct_offsets, (n + 1) * 8, &d_coff, kHpkeMinStage));
-  CHK(stage_in(c, c->hpke[6], pt_offsets, (n + 1) * 8, &d_poff, kHpkeMinStage));
-  CHK(stage_in(c, c->hpke[7], status, n, &d_st_in, kHpkeMinStage));
+  CHK(stage_in(c, c->hpke.enc_in, encs, n * bc.nenc, &d_enc, kHpkeMinStage));
+  CHK(stage_in(c, c->hpke.aad, aads, aad_total, &d_aad, kHpkeMinStage));
+  CHK(stage_in(c, c->hpke.aad_off, aad_offsets, (n + 1) * 8, &d_aoff, kHpkeMinStage));
+  CHK(stage_in(c, c->hpke.ct_in, cts, ct_total, &d_ct, kHpkeMinStage));
+  CHK(stage_in(c, c->hpke.ct_off, ct_offsets, (n + 1) * 8, &d_coff, kHpkeMinStage));
+  CHK(stage_in(c, c->hpke.pt_off, pt_offsets, (n + 1) * 8, &d_poff, kHpkeMinStage));
+  CHK(stage_in(c, c->hpke.status, status, n, &d_st_in, kHpkeMinStage));
   uint8_t* d_st = const_cast<uint8_t*>(d_st_in);
   uint8_t* d_pt = pts;
   const bool pt_host = !(pts && is_device_ptr(pts));
   if (pt_host) {
-    CHK(c->hpke[5].ensure(std::max<uint64_t>(pt_total, 16)));
-    d_pt = c->hpke[5].u8();
+    CHK(c->hpke.pt_out.ensure(std::max<uint64_t>(pt_total, 16)));
+    d_pt = c->hpke.pt_out.u8();
     if (pt_total) HIPCHK(hipMemsetAsync(d_pt, 0, pt_total, c->stream));
   }
-  // per report 32 bytes of DH value (P-256: shared secret) and, for P-256, one validity byte
-  const size_t dh_bytes = n * (p256 ? 33 : 32);
-  CHK(c->hpke[8].ensure(dh_bytes));
-  uint32_t* d_dh = static_cast<uint32_t*>(c->hpke[8].p);
-  int rc;
-  if (p256) {
-    uint8_t* d_ok = c->hpke[8].u8() + n * 32;
-    bc.dh_ok = d_ok;
-    rc = launch_p256_dh(c, sk, pk, bc, /*raw=*/false, n, d_enc, d_dh, d_ok);
-  } else {
-    rc = launch_x25519(c, sk, n, d_enc, d_dh);
-  }
-  if (!rc)  // a lane per report, or (prio3gpu_hpke_open_long_batch) a wave per report
-    rc = (team ? launch_hpke_open_team : launch_hpke_open)(
-        c, bc, n, d_dh, d_enc, d_aad, reinterpret_cast<const uint64_t*>(d_aoff), aad_total, d_ct,
-        reinterpret_cast<const uint64_t*>(d_coff), ct_total, d_pt,
-        reinterpret_cast<const uint64_t*>(d_poff), pt_total, d_st);
   // the per-report secrets: the DH values (keys and nonces never leave registers)
-  if (hipMemsetAsync(d_dh, 0, dh_bytes, c->stream) != hipSuccess && !rc) {
-    set_err("clearing the DH values failed");
-    rc = PRIO3GPU_E_HIP;
-  }
-  if (rc) {
-    (void)hipStreamSynchronize(c->stream);
-    return rc;
-  }
+  CallSecrets sec;
+  int rc = [&]() -> int {
+    uint32_t* d_dh;
+    CHK(open_dh(c, sec, kem_id, sk, pk, bc, /*raw=*/false, n, d_enc, &d_dh));
+    // a lane per report, or (prio3gpu_hpke_open_long_batch) a wave per report
+    auto launch = [&](auto kernel, size_t per_block) {
+      hipLaunchKernelGGL(kernel, dim3((unsigned)((n + per_block - 1) / per_block)), dim3(256), 0,
+                         c->stream, (uint32_t)n, bc, d_dh, d_enc, d_aad,
+                         reinterpret_cast<const uint64_t*>(d_aoff), aad_total, d_ct,
+                         reinterpret_cast<const uint64_t*>(d_coff), ct_total, d_pt,
+                         reinterpret_cast<const uint64_t*>(d_poff), pt_total, d_st);
+    };
+    if (team) {
+      PROF(KID_HPKE_OPEN_TEAM);
+      hpke_suite_dispatch(bc, [&](auto kdf, auto aead) {
+        launch(k_hpke_open_team<decltype(kdf)::value, decltype(aead)::value>, kTeamsPerBlock);
+      });
+    } else {
+      PROF(KID_HPKE_OPEN);
+      hpke_suite_dispatch(bc, [&](auto kdf, auto aead) {
+        launch(k_hpke_open<decltype(kdf)::value, decltype(aead)::value>, 256);
+      });
+    }
+    HIPCHK(hipGetLastError());
+    return 0;
+  }();
+  CHK(sec.finish(c, rc));
   if (pt_host && pt_total > pt_first)
     HIPCHK(hipMemcpyAsync(pts + pt_first, d_pt + pt_first, pt_total - pt_first,
                           hipMemcpyDeviceToHost, c->stream));
   if (d_st != status) HIPCHK(hipMemcpyAsync(status, d_st, n, hipMemcpyDeviceToHost, c->stream));
   return finish_call(c, {encs, aads, aad_offsets, cts, ct_offsets, pts, pt_offsets, status});
+}
+
+// The key check of an open entry point: a 32-byte private key, an Npk-byte public key, and for
+// P-256 a keypair (a scalar outside [1, n) fails the host's open of every report with this code;
+// a public key that is no point can have sealed nothing).
+int open_key_check(const char* who, uint16_t kem_id, const uint8_t* sk, size_t sk_len,
+                   const uint8_t* pk, size_t pk_len) {
+  const size_t npk = hpke_kem_nenc(kem_id);
+  if (!sk || sk_len != 32 || !pk || pk_len != npk) {
+    set_err("%s: the private key is 32 bytes, the public key %zu", who, npk);
+    return PRIO3GPU_E_ARG;
+  }
+  if (kem_id == 0x0010 && !p256_keypair_valid(sk, sk_len, pk, pk_len)) {
+    set_err("%s: not a P-256 keypair", who);
+    return PRIO3GPU_E_HPKE;
+  }
+  return 0;
+}
+
+// prio3gpu_hpke_open_batch and, with `team`, prio3gpu_hpke_open_long_batch.
+int hpke_open_batch_entry(prio3gpu_ctx* c, uint16_t kem_id, uint16_t kdf_id, uint16_t aead_id,
+                          const uint8_t* sk, size_t sk_len, const uint8_t* pk, size_t pk_len,
+                          const uint8_t* info, size_t info_len, size_t n, const uint8_t* encs,
+                          const uint8_t* aads, const uint64_t* aad_offsets, const uint8_t* cts,
+                          const uint64_t* ct_offsets, uint8_t* pts, const uint64_t* pt_offsets,
+                          uint8_t* status, bool team) {
+  if (!c) {
+    set_err("null context");
+    return PRIO3GPU_E_ARG;
+  }
+  CHK(suite_check(c, "HPKE open", /*seal=*/false, team, kem_id, kdf_id, aead_id));
+  if (info_len && !info) {  // with the key lengths: before the keypair's check
+    set_err("HPKE open: null info");
+    return PRIO3GPU_E_ARG;
+  }
+  CHK(open_key_check("HPKE open", kem_id, sk, sk_len, pk, pk_len));
+  if (n == 0) return 0;
+  if (!encs || !aad_offsets || !ct_offsets || !pt_offsets || !status || n > 0x7FFFFFFFu) {
+    set_err("HPKE open: null argument");
+    return PRIO3GPU_E_ARG;
+  }
+  return hpke_open_batch_impl(c, kem_id, kdf_id, aead_id, sk, pk, info, info_len, n, encs, aads,
+                              aad_offsets, cts, ct_offsets, pts, pt_offsets, status, team);
 }
 
 // The packed inputs and outputs of one key group's batch, reused from group to group.
@@ -403,6 +475,23 @@ int open_group_packed(prio3gpu_ctx* c, const HpkePlan& plan, size_t k, const uin
 }
 
 // ---- prio3gpu_helper_init_request, step by step -------------------------------------------------
+// k_hpke_open_req over one key group, instantiated for the suite of bc.
+int launch_hpke_open_req(prio3gpu_ctx* c, const HpkeBatchConsts& bc, const ReqTaskId& tid,
+                         size_t m, const uint32_t* d_idx, const uint32_t* d_dh,
+                         const uint8_t* d_msg, const ReqView* d_views, uint8_t* d_pts,
+                         const uint64_t* d_poff, uint8_t* d_status) {
+  {
+    PROF(KID_HPKE_OPEN_REQ);
+    hpke_suite_dispatch(bc, [&](auto kdf, auto aead) {
+      hipLaunchKernelGGL((k_hpke_open_req<decltype(kdf)::value, decltype(aead)::value>),
+                         dim3((unsigned)((m + 255) / 256)), dim3(256), 0, c->stream, (uint32_t)m,
+                         bc, tid, d_idx, d_dh, d_msg, d_views, d_pts, d_poff, d_status);
+    });
+  }
+  HIPCHK(hipGetLastError());
+  return 0;
+}
+
 // One call's arguments, plan and buffers.
 struct ReqCall {
   prio3gpu_ctx* c;
@@ -428,6 +517,9 @@ struct ReqCall {
   const uint64_t* d_poff;
   uint8_t *d_faults, *d_status, *d_in;
   std::vector<uint8_t> hp, hin, fb;  // host fallback: plaintexts, decoded rows, packed upload
+  // the per-report secrets outside the engine's rows: the DH values and the plaintexts on the
+  // device, the fallback's vectors on the host (ended after steps 3 to 6)
+  CallSecrets sec;
 };
 
 // 1. Who opens which report, the status image the kernels start from, each group's constants.
@@ -463,12 +555,12 @@ int req_reserve(ReqCall& q) {
   const size_t n = q.n;
   HIPCHK(hipSetDevice(c->device));
   q.in_pitch = input_pitch(st);
-  CHK(c->req[1].ensure(n * sizeof(ReqView)));
-  CHK(c->req[2].ensure(std::max<size_t>(q.plan.idx.size(), 1) * 4));
-  CHK(c->req[3].ensure(n * 33));  // DH values / shared secrets, then P-256's validity bytes
-  CHK(c->req[4].ensure(std::max<uint64_t>(q.poff[n], 16)));
-  CHK(c->req[5].ensure((n + 1) * 8));
-  CHK(c->req[6].ensure(n));
+  CHK(c->req.views.ensure(n * sizeof(ReqView)));
+  CHK(c->req.group_idx.ensure(std::max<size_t>(q.plan.idx.size(), 1) * 4));
+  CHK(c->req.dh.ensure(dh_bytes(n, /*p256=*/true)));  // a group of either KEM fits
+  CHK(c->req.pt.ensure(std::max<uint64_t>(q.poff[n], 16)));
+  CHK(c->req.pt_off.ensure((n + 1) * 8));
+  CHK(c->req.faults.ensure(n));
   CHK(st->status.ensure(n));
   CHK(st->nonces.ensure(n * 16));
   CHK(st->pub.ensure(std::max<size_t>(n * g.public_share_len, 16)));
@@ -476,16 +568,19 @@ int req_reserve(ReqCall& q) {
   CHK(c->io[0].ensure(std::max<size_t>(n * g.prep_share_len, 16)));
   {
     PROF(KID_REQ_COPY);
-    CHK(stage_in(c, c->req[0], q.msg, q.msg_len, &q.d_msg, 16));
+    CHK(stage_in(c, c->req.msg, q.msg, q.msg_len, &q.d_msg, 16));
   }
-  q.d_views = static_cast<const ReqView*>(c->req[1].p);
-  q.d_idx = static_cast<const uint32_t*>(c->req[2].p);
-  q.d_dh = static_cast<uint32_t*>(c->req[3].p);
-  q.d_pts = c->req[4].u8();
-  q.d_poff = static_cast<const uint64_t*>(c->req[5].p);
-  q.d_faults = c->req[6].u8();
+  q.d_views = static_cast<const ReqView*>(c->req.views.p);
+  q.d_idx = static_cast<const uint32_t*>(c->req.group_idx.p);
+  q.d_dh = static_cast<uint32_t*>(c->req.dh.p);
+  q.d_pts = c->req.pt.u8();
+  q.d_poff = static_cast<const uint64_t*>(c->req.pt_off.p);
+  q.d_faults = c->req.faults.u8();
   q.d_status = st->status.u8();
   q.d_in = st->input.u8();
+  q.sec.add(q.d_dh, dh_bytes(n, /*p256=*/true));
+  q.sec.add(q.d_pts, q.poff[n]);
+  q.sec.add(q.hp), q.sec.add(q.hin), q.sec.add(q.fb);
   return 0;
 }
 
@@ -495,12 +590,12 @@ int req_upload_gather(ReqCall& q) {
   prio3gpu_ctx* c = q.c;
   const size_t n = q.n;
   const std::vector<uint32_t>& idx = q.plan.idx;
-  HIPCHK(hipMemcpyAsync(c->req[1].p, q.views, n * sizeof(ReqView), hipMemcpyHostToDevice,
+  HIPCHK(hipMemcpyAsync(c->req.views.p, q.views, n * sizeof(ReqView), hipMemcpyHostToDevice,
                         c->stream));
   if (!idx.empty())
-    HIPCHK(hipMemcpyAsync(c->req[2].p, idx.data(), idx.size() * 4, hipMemcpyHostToDevice,
+    HIPCHK(hipMemcpyAsync(c->req.group_idx.p, idx.data(), idx.size() * 4, hipMemcpyHostToDevice,
                           c->stream));
-  HIPCHK(hipMemcpyAsync(c->req[5].p, q.poff.data(), (n + 1) * 8, hipMemcpyHostToDevice,
+  HIPCHK(hipMemcpyAsync(c->req.pt_off.p, q.poff.data(), (n + 1) * 8, hipMemcpyHostToDevice,
                         c->stream));
   HIPCHK(hipMemcpyAsync(q.d_status, q.dst.data(), n, hipMemcpyHostToDevice, c->stream));
   return launch_req_gather(c, n, q.d_msg, q.msg_len, q.d_views, q.st->nonces.u8(), q.st->pub.u8(),
@@ -514,7 +609,7 @@ int req_open_groups(ReqCall& q) {
     const uint32_t* d_idx = q.d_idx + q.plan.gbeg[k];
     const prio3gpu_hpke_keypair* kp = q.plan.groups[k];
     if (kp->kem_id == 0x0010) {
-      uint8_t* d_ok = reinterpret_cast<uint8_t*>(q.d_dh) + q.n * 32;
+      uint8_t* d_ok = dh_ok_at(q.d_dh, q.n);
       q.bcs[k].dh_ok = d_ok;
       CHK(launch_p256_dh_idx(q.c, kp->private_key, kp->public_key, q.bcs[k], m, d_idx, q.d_msg,
                              q.d_views, q.d_dh, d_ok));
@@ -589,8 +684,8 @@ int req_host_fallback(ReqCall& q) {
   std::vector<uint8_t> st_fb;
   CHK(req_host_open(q, f, st_fb));
   const FallbackLayout l = pack_fallback(f, q.n, q.hin.data(), st_fb.data(), want, &q.fb);
-  CHK(c->req[7].ensure(l.bytes));
-  uint8_t* d_fb = c->req[7].u8();
+  CHK(c->req.fallback.ensure(l.bytes));
+  uint8_t* d_fb = c->req.fallback.u8();
   HIPCHK(hipMemcpyAsync(d_fb, q.fb.data(), l.bytes, hipMemcpyHostToDevice, c->stream));
   {
     PROF(KID_REQ_SCATTER);
@@ -603,33 +698,7 @@ int req_host_fallback(ReqCall& q) {
   return 0;
 }
 
-// 7. The per-report secrets outside the engine's rows, after steps 3 to 6 ended with rc: the DH
-// values and the plaintexts on the device, the fallback's vectors on the host.
-int req_clear_secrets(ReqCall& q, int rc) {
-  prio3gpu_ctx* c = q.c;
-  bool cleared = hipMemsetAsync(q.d_dh, 0, q.n * 33, c->stream) == hipSuccess;
-  if (q.poff[q.n])
-    cleared &= hipMemsetAsync(q.d_pts, 0, q.poff[q.n], c->stream) == hipSuccess;
-  if (!cleared && !rc) {
-    set_err("clearing the request's secrets failed");
-    rc = PRIO3GPU_E_HIP;
-  }
-  if (rc || !q.fb.empty()) (void)hipStreamSynchronize(c->stream);  // fb, hp, hin are read by copies
-  wipe(q.hp.data(), q.hp.size());
-  wipe(q.hin.data(), q.hin.size());
-  wipe(q.fb.data(), q.fb.size());
-  return rc;
-}
-
 // ---- batched HPKE seal on the GPU (hpke_seal_gpu.h) ---------------------------------------------
-// The suites the GPU seals: DHKEM(X25519, HKDF-SHA256) with KDF 1-3 and AEAD 1-3 (no option: the
-// seal has entry points of its own), and with the context's "hpke_gpu_p256" option the same under
-// DHKEM(P-256, HKDF-SHA256).
-bool hpke_seal_suite(const prio3gpu_ctx* c, uint16_t kem, uint16_t kdf, uint16_t aead) {
-  return (kem == 0x0020 || (kem == 0x0010 && c->hpke_gpu_p256)) && kdf >= 1 && kdf <= 3 &&
-         aead >= 1 && aead <= 3;
-}
-
 // The recipient's public key of a seal entry point: 32 bytes for X25519; for P-256 the 65 bytes
 // of a point DeserializePublicKey takes (p256.h's decoder), checked before anything is launched.
 int seal_pk_check(uint16_t kem_id, const uint8_t* pk, size_t pk_len) {
@@ -647,18 +716,6 @@ int seal_pk_check(uint16_t kem_id, const uint8_t* pk, size_t pk_len) {
   }
   return 0;
 }
-
-// The per-report secrets of one seal call on the device: the engine's copies of the ephemeral
-// keys and of the plaintexts (null where the caller's own device buffer is read in place) and the
-// ladders' output (n encapsulated keys, then n DH values, 8 words each).
-struct SealSecrets {
-  const uint8_t* d_sk = nullptr;
-  size_t sk_bytes = 0;
-  const uint8_t* d_pt = nullptr;
-  size_t pt_bytes = 0;
-  uint32_t* d_eph = nullptr;
-  size_t eph_bytes = 0;
-};
 
 // The generator, as SerializePublicKey writes it
 const uint8_t kP256G[65] = {
@@ -682,37 +739,32 @@ int launch_p256_eph(prio3gpu_ctx* c, const uint8_t* pk, size_t n, const uint8_t*
   {
     PROF(KID_P256_EPH);
     hipLaunchKernelGGL(k_p256_eph, dim3((unsigned)((n + 63) / 64), 2), dim3(64), 0, c->stream,
-                       (uint32_t)n, d_sk, pts, d_eph,
-                       reinterpret_cast<uint8_t*>(d_eph) + n * 96);
+                       (uint32_t)n, d_sk, pts, d_eph, p256_eph_ok_at(d_eph, n));
   }
   HIPCHK(hipGetLastError());
   return 0;
 }
 
-// Stage the n ephemeral keys and run both ladders of every report: s->d_eph.  Under P-256 the KEM
-// half follows (k_p256_eph_kem) and bc.dh_ok is set to the validity bytes.
-int seal_ladders(prio3gpu_ctx* c, HpkeBatchConsts& bc, const uint8_t* pk, size_t n,
-                 const uint8_t* sk_es, SealSecrets* s) {
+// Stage the n ephemeral keys and run both ladders of every report into the context's eph scratch
+// (*d_eph), both the call's secrets from here on.  Under P-256 the KEM half follows
+// (k_p256_eph_kem) and bc.dh_ok is set to the validity bytes.
+int seal_ladders(prio3gpu_ctx* c, CallSecrets& sec, HpkeBatchConsts& bc, const uint8_t* pk,
+                 size_t n, const uint8_t* sk_es, uint32_t** d_eph) {
   const bool p256 = bc.kem_lo == 0x10;
-  const size_t eph_bytes = n * (p256 ? kP256EphBytes : 64);
-  CHK(c->seal[1].ensure(eph_bytes));
-  s->d_eph = static_cast<uint32_t*>(c->seal[1].p);
-  s->eph_bytes = eph_bytes;
-  s->sk_bytes = n * 32;
-  CHK(stage_in(c, c->seal[0], sk_es, n * 32, &s->d_sk, kHpkeMinStage));
+  CHK(c->seal.eph.ensure(eph_bytes(n, p256)));
+  uint32_t* eph = *d_eph = static_cast<uint32_t*>(c->seal.eph.p);
+  sec.add(eph, eph_bytes(n, p256));
+  const uint8_t* d_sk;
+  CHK(stage_secret(c, sec, c->seal.eph_sk, sk_es, n * 32, &d_sk));
   if (p256) {
-    uint8_t* d_ok = c->seal[1].u8() + n * 96;
+    uint8_t* d_ok = p256_eph_ok_at(eph, n);
     bc.dh_ok = d_ok;
-    CHK(launch_p256_eph(c, pk, n, s->d_sk, s->d_eph));
-    P256DhConsts dc;
-    p256_load_be_words8(pk + 1, dc.pk.x);
-    p256_load_be_words8(pk + 33, dc.pk.y);
-    memcpy(dc.salt0_i, bc.salt0_i, sizeof dc.salt0_i);
-    memcpy(dc.salt0_o, bc.salt0_o, sizeof dc.salt0_o);
+    CHK(launch_p256_eph(c, pk, n, d_sk, eph));
+    const P256DhConsts dc = p256_dh_consts(pk, bc);
     {
       PROF(KID_P256_EPH_KEM);
       hipLaunchKernelGGL(k_p256_eph_kem, dim3((unsigned)((n + 255) / 256)), dim3(256), 0,
-                         c->stream, (uint32_t)n, dc, s->d_eph, d_ok);
+                         c->stream, (uint32_t)n, dc, eph, d_ok);
     }
     HIPCHK(hipGetLastError());
     return 0;
@@ -722,26 +774,10 @@ int seal_ladders(prio3gpu_ctx* c, HpkeBatchConsts& bc, const uint8_t* pk, size_t
   {
     PROF(KID_X25519_EPH);
     hipLaunchKernelGGL(k_x25519_eph, dim3((unsigned)((n + 63) / 64), 2), dim3(64), 0, c->stream,
-                       (uint32_t)n, s->d_sk, pkw, s->d_eph);
+                       (uint32_t)n, d_sk, pkw, eph);
   }
   HIPCHK(hipGetLastError());
   return 0;
-}
-
-// Zero the engine's copies of a seal call's secrets, after its launches ended with rc.
-int seal_clear_secrets(prio3gpu_ctx* c, const SealSecrets& s, int rc) {
-  bool cleared = true;
-  if (s.d_sk && s.d_sk == c->seal[0].u8())
-    cleared &= hipMemsetAsync(c->seal[0].p, 0, s.sk_bytes, c->stream) == hipSuccess;
-  if (s.d_pt && s.d_pt == c->seal[2].u8() && s.pt_bytes)
-    cleared &= hipMemsetAsync(c->seal[2].p, 0, s.pt_bytes, c->stream) == hipSuccess;
-  if (s.d_eph) cleared &= hipMemsetAsync(s.d_eph, 0, s.eph_bytes, c->stream) == hipSuccess;
-  if (!cleared && !rc) {
-    set_err("clearing the seal's secrets failed");
-    rc = PRIO3GPU_E_HIP;
-  }
-  if (rc) (void)hipStreamSynchronize(c->stream);
-  return rc;
 }
 
 // Where a seal writes an output of `bytes` bytes: the caller's buffer when it is device memory,
@@ -757,11 +793,29 @@ int seal_out(prio3gpu_ctx* c, DevBuf& buf, uint8_t* dst, size_t bytes, uint8_t**
   return 0;
 }
 
-int hpke_seal_batch_impl(prio3gpu_ctx* c, uint16_t kem_id, uint16_t kdf_id, uint16_t aead_id,
-                         const uint8_t* pk, const uint8_t* info, size_t info_len, size_t n,
-                         const uint8_t* sk_es, const uint8_t* aads, const uint64_t* aad_offsets,
-                         const uint8_t* pts, const uint64_t* pt_offsets, uint8_t* encs,
-                         uint8_t* cts, const uint64_t* ct_offsets, uint8_t* status, bool team) {
+// prio3gpu_hpke_seal_batch and, with `team`, prio3gpu_hpke_seal_long_batch.
+int hpke_seal_batch_entry(prio3gpu_ctx* c, uint16_t kem_id, uint16_t kdf_id, uint16_t aead_id,
+                          const uint8_t* pk, size_t pk_len, const uint8_t* info, size_t info_len,
+                          size_t n, const uint8_t* sk_es, const uint8_t* aads,
+                          const uint64_t* aad_offsets, const uint8_t* pts,
+                          const uint64_t* pt_offsets, uint8_t* encs, uint8_t* cts,
+                          const uint64_t* ct_offsets, uint8_t* status, bool team) {
+  if (!c) {
+    set_err("null context");
+    return PRIO3GPU_E_ARG;
+  }
+  CHK(suite_check(c, "HPKE seal", /*seal=*/true, team, kem_id, kdf_id, aead_id));
+  CHK(seal_pk_check(kem_id, pk, pk_len));
+  if (info_len && !info) {
+    set_err("HPKE seal: null info");
+    return PRIO3GPU_E_ARG;
+  }
+  if (n == 0) return 0;
+  if (!sk_es || !aad_offsets || !pt_offsets || !encs || !ct_offsets || !status ||
+      n > 0x7FFFFFFFu) {
+    set_err("HPKE seal: null argument");
+    return PRIO3GPU_E_ARG;
+  }
   HpkeBatchConsts bc;
   if (!hpke_batch_consts(kem_id, kdf_id, aead_id, pk, info, info_len, &bc)) {
     set_err("HPKE primitives unavailable");
@@ -777,32 +831,34 @@ int hpke_seal_batch_impl(prio3gpu_ctx* c, uint16_t kem_id, uint16_t kdf_id, uint
     set_err("HPKE seal: null data buffer or offsets out of order");
     return PRIO3GPU_E_ARG;
   }
-  SealSecrets s;
+  // the per-report secrets: the engine's copies of the ephemeral keys and of the plaintexts, and
+  // the ladders' output
+  CallSecrets sec;
   uint8_t *d_enc = nullptr, *d_ct = nullptr, *d_st = nullptr;
   int rc = [&]() -> int {
-    const uint8_t *d_aad, *d_aoff, *d_poff, *d_coff, *d_st_in;
-    CHK(stage_in(c, c->hpke[1], aads, aad_total, &d_aad, kHpkeMinStage));
-    CHK(stage_in(c, c->hpke[2], aad_offsets, (n + 1) * 8, &d_aoff, kHpkeMinStage));
-    CHK(stage_in(c, c->seal[3], pt_offsets, (n + 1) * 8, &d_poff, kHpkeMinStage));
-    CHK(stage_in(c, c->hpke[4], ct_offsets, (n + 1) * 8, &d_coff, kHpkeMinStage));
-    CHK(stage_in(c, c->hpke[7], status, n, &d_st_in, kHpkeMinStage));
+    const uint8_t *d_aad, *d_aoff, *d_poff, *d_coff, *d_st_in, *d_pt;
+    uint32_t* d_eph;
+    CHK(stage_in(c, c->hpke.aad, aads, aad_total, &d_aad, kHpkeMinStage));
+    CHK(stage_in(c, c->hpke.aad_off, aad_offsets, (n + 1) * 8, &d_aoff, kHpkeMinStage));
+    CHK(stage_in(c, c->seal.pt_off, pt_offsets, (n + 1) * 8, &d_poff, kHpkeMinStage));
+    CHK(stage_in(c, c->hpke.ct_off, ct_offsets, (n + 1) * 8, &d_coff, kHpkeMinStage));
+    CHK(stage_in(c, c->hpke.status, status, n, &d_st_in, kHpkeMinStage));
     d_st = const_cast<uint8_t*>(d_st_in);
-    CHK(seal_out(c, c->seal[7], encs, n * bc.nenc, &d_enc));
-    CHK(seal_out(c, c->seal[8], cts, ct_total, &d_ct));
-    s.pt_bytes = pt_total;
-    CHK(stage_in(c, c->seal[2], pts, pt_total, &s.d_pt, kHpkeMinStage));
-    CHK(seal_ladders(c, bc, pk, n, sk_es, &s));
+    CHK(seal_out(c, c->seal.enc_packed, encs, n * bc.nenc, &d_enc));
+    CHK(seal_out(c, c->seal.ct_out, cts, ct_total, &d_ct));
+    CHK(stage_secret(c, sec, c->seal.pt_in, pts, pt_total, &d_pt));
+    CHK(seal_ladders(c, sec, bc, pk, n, sk_es, &d_eph));
     // a lane per report, or (prio3gpu_hpke_seal_long_batch) a wave per report
     auto launch = [&](auto kernel, size_t per_block) {
       hipLaunchKernelGGL(kernel, dim3((unsigned)((n + per_block - 1) / per_block)), dim3(256), 0,
-                         c->stream, (uint32_t)n, bc, s.d_eph, d_aad,
-                         reinterpret_cast<const uint64_t*>(d_aoff), aad_total, s.d_pt,
+                         c->stream, (uint32_t)n, bc, d_eph, d_aad,
+                         reinterpret_cast<const uint64_t*>(d_aoff), aad_total, d_pt,
                          reinterpret_cast<const uint64_t*>(d_poff), pt_total, d_enc, d_ct,
                          reinterpret_cast<const uint64_t*>(d_coff), ct_total, d_st);
     };
     if (team) {
       PROF(KID_HPKE_SEAL_TEAM);
-      hpke_team_dispatch(c, bc, [&](auto kdf, auto aead) {
+      hpke_suite_dispatch(bc, [&](auto kdf, auto aead) {
         launch(k_hpke_seal_team<decltype(kdf)::value, decltype(aead)::value>, kTeamsPerBlock);
       });
     } else {
@@ -814,7 +870,7 @@ int hpke_seal_batch_impl(prio3gpu_ctx* c, uint16_t kem_id, uint16_t kdf_id, uint
     HIPCHK(hipGetLastError());
     return 0;
   }();
-  CHK(seal_clear_secrets(c, s, rc));
+  CHK(sec.finish(c, rc));
   CHK(copy_out(c, encs, d_enc, n * bc.nenc));
   if (d_ct != cts && ct_total > ct_first)
     HIPCHK(hipMemcpyAsync(cts + ct_first, d_ct + ct_first, ct_total - ct_first,
@@ -823,10 +879,11 @@ int hpke_seal_batch_impl(prio3gpu_ctx* c, uint16_t kem_id, uint16_t kdf_id, uint
   return finish_call(c, {sk_es, aads, aad_offsets, pts, pt_offsets, encs, cts, ct_offsets, status});
 }
 
-// `rows` rows of `width` bytes from packed device rows to the caller's host rows `pitch` apart,
-// through host memory: only the rows' own bytes are written.
-int seal_rows_to_host(prio3gpu_ctx* c, uint8_t* dst, size_t pitch, const uint8_t* d_src,
-                      size_t width, size_t rows) {
+// `rows` rows of `width` bytes from packed device rows (a seal's encs and payloads, an open's
+// shares) to the caller's host rows `pitch` apart, through host memory: only the rows' own bytes
+// are written.
+int packed_rows_to_host(prio3gpu_ctx* c, uint8_t* dst, size_t pitch, const uint8_t* d_src,
+                        size_t width, size_t rows) {
   if (pitch == width) {
     HIPCHK(hipMemcpyAsync(dst, d_src, rows * width, hipMemcpyDeviceToHost, c->stream));
     return 0;
@@ -836,45 +893,6 @@ int seal_rows_to_host(prio3gpu_ctx* c, uint8_t* dst, size_t pitch, const uint8_t
   HIPCHK(hipStreamSynchronize(c->stream));
   for (size_t i = 0; i < rows; ++i) memcpy(dst + i * pitch, tmp.data() + i * width, width);
   return 0;
-}
-
-// The suite check of a seal entry point: a lane per report (hpke_seal_gpu.h), or with `team` a wave
-// per report (hpke_seal_team.h: the suites of the wave-per-report open on this context).
-int seal_suite_check(const prio3gpu_ctx* c, uint16_t kem_id, uint16_t kdf_id, uint16_t aead_id,
-                     bool team) {
-  if (team ? hpke_team_suite(c, kem_id, kdf_id, aead_id)
-           : hpke_seal_suite(c, kem_id, kdf_id, aead_id))
-    return 0;
-  set_err("HPKE suite 0x%04x/%u/%u is not sealed %s", kem_id, kdf_id, aead_id,
-          team ? "a wave per report" : "on the GPU");
-  return PRIO3GPU_E_UNSUPPORTED;
-}
-
-// prio3gpu_hpke_seal_batch and, with `team`, prio3gpu_hpke_seal_long_batch.
-int hpke_seal_batch_entry(prio3gpu_ctx* c, uint16_t kem_id, uint16_t kdf_id, uint16_t aead_id,
-                          const uint8_t* pk, size_t pk_len, const uint8_t* info, size_t info_len,
-                          size_t n, const uint8_t* sk_es, const uint8_t* aads,
-                          const uint64_t* aad_offsets, const uint8_t* pts,
-                          const uint64_t* pt_offsets, uint8_t* encs, uint8_t* cts,
-                          const uint64_t* ct_offsets, uint8_t* status, bool team) {
-  if (!c) {
-    set_err("null context");
-    return PRIO3GPU_E_ARG;
-  }
-  CHK(seal_suite_check(c, kem_id, kdf_id, aead_id, team));
-  CHK(seal_pk_check(kem_id, pk, pk_len));
-  if (info_len && !info) {
-    set_err("HPKE seal: null info");
-    return PRIO3GPU_E_ARG;
-  }
-  if (n == 0) return 0;
-  if (!sk_es || !aad_offsets || !pt_offsets || !encs || !ct_offsets || !status ||
-      n > 0x7FFFFFFFu) {
-    set_err("HPKE seal: null argument");
-    return PRIO3GPU_E_ARG;
-  }
-  return hpke_seal_batch_impl(c, kem_id, kdf_id, aead_id, pk, info, info_len, n, sk_es, aads,
-                              aad_offsets, pts, pt_offsets, encs, cts, ct_offsets, status, team);
 }
 
 // prio3gpu_seal_input_shares and, with `team`, prio3gpu_seal_input_shares_long.
@@ -891,28 +909,27 @@ int seal_input_shares_entry(prio3gpu_ctx* c, const uint8_t* task_id, uint16_t ke
     set_err("null context");
     return PRIO3GPU_E_ARG;
   }
-  CHK(seal_suite_check(c, kem_id, kdf_id, aead_id, team));
+  CHK(suite_check(c, "seal_input_shares", /*seal=*/true, team, kem_id, kdf_id, aead_id));
   CHK(seal_pk_check(kem_id, pk, pk_len));
   if (!task_id) {
     set_err("seal_input_shares: null task id");
     return PRIO3GPU_E_ARG;
   }
   if (n == 0) return 0;
-  const size_t nenc = hpke_kem_nenc(kem_id);
-  const size_t plen = 6 + (size_t)input_share_len + 16;
-  const size_t spitch = input_share_pitch ? input_share_pitch : input_share_len;
-  const size_t epitch = enc_pitch ? enc_pitch : nenc;
-  const size_t ppitch = payload_pitch ? payload_pitch : plen;
   if (!report_ids || !times || (public_share_len && !public_shares) ||
       (input_share_len && !input_shares) || !sk_es || !out_encs || !out_payloads || !status ||
       n > 0x7FFFFFFFu) {
     set_err("seal_input_shares: null argument");
     return PRIO3GPU_E_ARG;
   }
-  if (spitch < input_share_len || epitch < nenc || ppitch < plen) {
+  const ShareColumns g =
+      share_columns(kem_id, input_share_len, enc_pitch, payload_pitch, input_share_pitch);
+  if (!g.ok()) {
     set_err("seal_input_shares: a pitch is shorter than its row");
     return PRIO3GPU_E_ARG;
   }
+  const size_t nenc = g.nenc, plen = g.plen;
+  const size_t spitch = g.share_pitch, epitch = g.enc_pitch, ppitch = g.payload_pitch;
   uint8_t info[20];
   input_share_info(/*ROLE_CLIENT*/ 1, recipient_role, info);
   HpkeBatchConsts bc;
@@ -923,36 +940,38 @@ int seal_input_shares_entry(prio3gpu_ctx* c, const uint8_t* task_id, uint16_t ke
   ReqTaskId tid;
   memcpy(tid.w, task_id, 32);  // little-endian host: byte j at bits 8 (j & 3) of word j >> 2
   HIPCHK(hipSetDevice(c->device));
-  const size_t share_bytes = (n - 1) * spitch + input_share_len;
-  SealSecrets s;
+  // the per-report secrets: the engine's copies of the ephemeral keys and of the share rows, and
+  // the ladders' output
+  CallSecrets sec;
   // host outputs are sealed into packed staging rows, device outputs in place at their pitches
   const bool enc_host = !is_device_ptr(out_encs), pay_host = !is_device_ptr(out_payloads);
   uint8_t *d_enc = nullptr, *d_pay = nullptr, *d_st = nullptr;
   int rc = [&]() -> int {
-    const uint8_t *d_rid, *d_time, *d_pub, *d_st_in;
-    CHK(stage_in(c, c->seal[4], report_ids, n * 16, &d_rid, kHpkeMinStage));
-    CHK(stage_in(c, c->seal[5], times, n * 8, &d_time, kHpkeMinStage));
-    CHK(stage_in(c, c->seal[6], public_shares, n * (size_t)public_share_len, &d_pub,
+    const uint8_t *d_rid, *d_time, *d_pub, *d_st_in, *d_sh;
+    uint32_t* d_eph;
+    CHK(stage_in(c, c->seal.rid, report_ids, n * 16, &d_rid, kHpkeMinStage));
+    CHK(stage_in(c, c->seal.time, times, n * 8, &d_time, kHpkeMinStage));
+    CHK(stage_in(c, c->seal.pub, public_shares, n * (size_t)public_share_len, &d_pub,
                  kHpkeMinStage));
-    CHK(stage_in(c, c->hpke[7], status, n, &d_st_in, kHpkeMinStage));
+    CHK(stage_in(c, c->hpke.status, status, n, &d_st_in, kHpkeMinStage));
     d_st = const_cast<uint8_t*>(d_st_in);
-    CHK(seal_out(c, c->seal[7], enc_host ? nullptr : out_encs, n * nenc, &d_enc));
-    CHK(seal_out(c, c->seal[8], pay_host ? nullptr : out_payloads, n * plen, &d_pay));
-    s.pt_bytes = share_bytes;
-    CHK(stage_in(c, c->seal[2], input_shares, share_bytes, &s.d_pt, kHpkeMinStage));
-    CHK(seal_ladders(c, bc, pk, n, sk_es, &s));
+    CHK(seal_out(c, c->seal.enc_packed, enc_host ? nullptr : out_encs, n * nenc, &d_enc));
+    CHK(seal_out(c, c->seal.ct_out, pay_host ? nullptr : out_payloads, n * plen, &d_pay));
+    CHK(stage_secret(c, sec, c->seal.pt_in, input_shares,
+                     rows_span(n, spitch, input_share_len), &d_sh));
+    CHK(seal_ladders(c, sec, bc, pk, n, sk_es, &d_eph));
     // a lane per report, or (prio3gpu_seal_input_shares_long) a wave per report
     auto launch = [&](auto kernel, size_t per_block) {
       hipLaunchKernelGGL(kernel, dim3((unsigned)((n + per_block - 1) / per_block)), dim3(256), 0,
-                         c->stream, (uint32_t)n, bc, tid, s.d_eph, d_rid,
+                         c->stream, (uint32_t)n, bc, tid, d_eph, d_rid,
                          reinterpret_cast<const uint64_t*>(d_time), d_pub, public_share_len,
-                         s.d_pt, input_share_len, (uint64_t)spitch, d_enc,
+                         d_sh, input_share_len, (uint64_t)spitch, d_enc,
                          (uint64_t)(enc_host ? nenc : epitch), d_pay,
                          (uint64_t)(pay_host ? plen : ppitch), d_st);
     };
     if (team) {
       PROF(KID_HPKE_SEAL_TEAM_SHARES);
-      hpke_team_dispatch(c, bc, [&](auto kdf, auto aead) {
+      hpke_suite_dispatch(bc, [&](auto kdf, auto aead) {
         launch(k_hpke_seal_team_shares<decltype(kdf)::value, decltype(aead)::value>,
                kTeamsPerBlock);
       });
@@ -965,9 +984,9 @@ int seal_input_shares_entry(prio3gpu_ctx* c, const uint8_t* task_id, uint16_t ke
     HIPCHK(hipGetLastError());
     return 0;
   }();
-  CHK(seal_clear_secrets(c, s, rc));
-  if (enc_host) CHK(seal_rows_to_host(c, out_encs, epitch, d_enc, nenc, n));
-  if (pay_host) CHK(seal_rows_to_host(c, out_payloads, ppitch, d_pay, plen, n));
+  CHK(sec.finish(c, rc));
+  if (enc_host) CHK(packed_rows_to_host(c, out_encs, epitch, d_enc, nenc, n));
+  if (pay_host) CHK(packed_rows_to_host(c, out_payloads, ppitch, d_pay, plen, n));
   CHK(copy_out(c, status, d_st, n));
   return finish_call(c, {report_ids, times, public_shares, input_shares, sk_es, out_encs,
                          out_payloads, status});
@@ -1036,32 +1055,9 @@ int prio3gpu_hpke_open_batch(prio3gpu_ctx* c, uint16_t kem_id, uint16_t kdf_id, 
                              const uint8_t* aads, const uint64_t* aad_offsets, const uint8_t* cts,
                              const uint64_t* ct_offsets, uint8_t* pts, const uint64_t* pt_offsets,
                              uint8_t* status) {
-  if (!c) {
-    set_err("null context");
-    return PRIO3GPU_E_ARG;
-  }
-  if (!hpke_gpu_suite(c, kem_id, kdf_id, aead_id)) {
-    set_err("HPKE suite 0x%04x/%u/%u is not opened on the GPU", kem_id, kdf_id, aead_id);
-    return PRIO3GPU_E_UNSUPPORTED;
-  }
-  const size_t npk = hpke_kem_nenc(kem_id);
-  if (!sk || sk_len != 32 || !pk || pk_len != npk || (info_len && !info)) {
-    set_err("HPKE open: the private key is 32 bytes, the public key %zu", npk);
-    return PRIO3GPU_E_ARG;
-  }
-  // a P-256 scalar outside [1, n) fails the host's open of every report with this code; a public
-  // key that is no point can have sealed nothing
-  if (kem_id == 0x0010 && !p256_keypair_valid(sk, sk_len, pk, pk_len)) {
-    set_err("HPKE open: not a P-256 keypair");
-    return PRIO3GPU_E_HPKE;
-  }
-  if (n == 0) return 0;
-  if (!encs || !aad_offsets || !ct_offsets || !pt_offsets || !status || n > 0x7FFFFFFFu) {
-    set_err("HPKE open: null argument");
-    return PRIO3GPU_E_ARG;
-  }
-  return hpke_open_batch_impl(c, kem_id, kdf_id, aead_id, sk, pk, info, info_len, n, encs, aads,
-                              aad_offsets, cts, ct_offsets, pts, pt_offsets, status);
+  return hpke_open_batch_entry(c, kem_id, kdf_id, aead_id, sk, sk_len, pk, pk_len, info, info_len,
+                               n, encs, aads, aad_offsets, cts, ct_offsets, pts, pt_offsets,
+                               status, /*team=*/false);
 }
 
 int prio3gpu_hpke_open_long_batch(prio3gpu_ctx* c, uint16_t kem_id, uint16_t kdf_id,
@@ -1071,31 +1067,9 @@ int prio3gpu_hpke_open_long_batch(prio3gpu_ctx* c, uint16_t kem_id, uint16_t kdf
                                   const uint8_t* aads, const uint64_t* aad_offsets,
                                   const uint8_t* cts, const uint64_t* ct_offsets, uint8_t* pts,
                                   const uint64_t* pt_offsets, uint8_t* status) {
-  if (!c) {
-    set_err("null context");
-    return PRIO3GPU_E_ARG;
-  }
-  if (!hpke_team_suite(c, kem_id, kdf_id, aead_id)) {
-    set_err("HPKE suite 0x%04x/%u/%u is not opened a wave per report", kem_id, kdf_id, aead_id);
-    return PRIO3GPU_E_UNSUPPORTED;
-  }
-  const size_t npk = hpke_kem_nenc(kem_id);
-  if (!sk || sk_len != 32 || !pk || pk_len != npk || (info_len && !info)) {
-    set_err("HPKE open: the private key is 32 bytes, the public key %zu", npk);
-    return PRIO3GPU_E_ARG;
-  }
-  if (kem_id == 0x0010 && !p256_keypair_valid(sk, sk_len, pk, pk_len)) {
-    set_err("HPKE open: not a P-256 keypair");
-    return PRIO3GPU_E_HPKE;
-  }
-  if (n == 0) return 0;
-  if (!encs || !aad_offsets || !ct_offsets || !pt_offsets || !status || n > 0x7FFFFFFFu) {
-    set_err("HPKE open: null argument");
-    return PRIO3GPU_E_ARG;
-  }
-  return hpke_open_batch_impl(c, kem_id, kdf_id, aead_id, sk, pk, info, info_len, n, encs, aads,
-                              aad_offsets, cts, ct_offsets, pts, pt_offsets, status,
-                              /*team=*/true);
+  return hpke_open_batch_entry(c, kem_id, kdf_id, aead_id, sk, sk_len, pk, pk_len, info, info_len,
+                               n, encs, aads, aad_offsets, cts, ct_offsets, pts, pt_offsets,
+                               status, /*team=*/true);
 }
 
 int prio3gpu_open_input_shares(prio3gpu_ctx* c, const uint8_t* task_id, uint16_t kem_id,
@@ -1110,35 +1084,26 @@ int prio3gpu_open_input_shares(prio3gpu_ctx* c, const uint8_t* task_id, uint16_t
     set_err("null context");
     return PRIO3GPU_E_ARG;
   }
-  if (!hpke_team_suite(c, kem_id, kdf_id, aead_id)) {
-    set_err("HPKE suite 0x%04x/%u/%u is not opened a wave per report", kem_id, kdf_id, aead_id);
-    return PRIO3GPU_E_UNSUPPORTED;
-  }
-  const bool p256 = kem_id == 0x0010;
-  const size_t nenc = hpke_kem_nenc(kem_id);
-  if (!sk || sk_len != 32 || !pk || pk_len != nenc || !task_id) {
-    set_err("open_input_shares: the private key and the task id are 32 bytes, the public key %zu",
-            nenc);
+  CHK(suite_check(c, "open_input_shares", /*seal=*/false, /*team=*/true, kem_id, kdf_id, aead_id));
+  if (!task_id) {  // with the key lengths: before the keypair's check
+    set_err("open_input_shares: null task id");
     return PRIO3GPU_E_ARG;
   }
-  if (p256 && !p256_keypair_valid(sk, sk_len, pk, pk_len)) {
-    set_err("open_input_shares: not a P-256 keypair");
-    return PRIO3GPU_E_HPKE;
-  }
+  CHK(open_key_check("open_input_shares", kem_id, sk, sk_len, pk, pk_len));
   if (n == 0) return 0;
-  const size_t plen = 6 + (size_t)input_share_len + 16;
-  const size_t epitch = enc_pitch ? enc_pitch : nenc;
-  const size_t ppitch = payload_pitch ? payload_pitch : plen;
-  const size_t spitch = share_pitch ? share_pitch : input_share_len;
   if (!report_ids || !times || (public_share_len && !public_shares) || !encs || !payloads ||
       (input_share_len && !out_shares) || !status || n > 0x7FFFFFFFu) {
     set_err("open_input_shares: null argument");
     return PRIO3GPU_E_ARG;
   }
-  if (epitch < nenc || ppitch < plen || spitch < input_share_len) {
+  const ShareColumns g =
+      share_columns(kem_id, input_share_len, enc_pitch, payload_pitch, share_pitch);
+  if (!g.ok()) {
     set_err("open_input_shares: a pitch is shorter than its row");
     return PRIO3GPU_E_ARG;
   }
+  const size_t nenc = g.nenc, plen = g.plen;
+  const size_t epitch = g.enc_pitch, ppitch = g.payload_pitch, spitch = g.share_pitch;
   uint8_t info[20];
   input_share_info(/*ROLE_CLIENT*/ 1, recipient_role, info);
   HpkeBatchConsts bc;
@@ -1152,44 +1117,38 @@ int prio3gpu_open_input_shares(prio3gpu_ctx* c, const uint8_t* task_id, uint16_t
   // host rows are staged with their gaps, one span per column; a host output is opened into
   // packed staging rows (zeroed after the copy: they are input shares), a device one in place
   const bool out_host = !(out_shares && is_device_ptr(out_shares));
-  // per report 32 bytes of DH value (P-256: shared secret) and, for P-256, one validity byte
-  const size_t out_bytes = n * (size_t)input_share_len, dh_bytes = n * (p256 ? 33 : 32);
+  const size_t out_bytes = n * (size_t)input_share_len;
   const uint8_t *d_rid, *d_time, *d_pub, *d_enc, *d_pay, *d_st_in;
-  CHK(stage_in(c, c->seal[4], report_ids, n * 16, &d_rid, kHpkeMinStage));
-  CHK(stage_in(c, c->seal[5], times, n * 8, &d_time, kHpkeMinStage));
-  CHK(stage_in(c, c->seal[6], public_shares, n * (size_t)public_share_len, &d_pub,
+  CHK(stage_in(c, c->seal.rid, report_ids, n * 16, &d_rid, kHpkeMinStage));
+  CHK(stage_in(c, c->seal.time, times, n * 8, &d_time, kHpkeMinStage));
+  CHK(stage_in(c, c->seal.pub, public_shares, n * (size_t)public_share_len, &d_pub,
                kHpkeMinStage));
-  CHK(stage_in(c, c->hpke[0], encs, (n - 1) * epitch + nenc, &d_enc, kHpkeMinStage));
-  CHK(stage_in(c, c->hpke[3], payloads, (n - 1) * ppitch + plen, &d_pay, kHpkeMinStage));
-  CHK(stage_in(c, c->hpke[7], status, n, &d_st_in, kHpkeMinStage));
+  CHK(stage_in(c, c->hpke.enc_in, encs, rows_span(n, epitch, nenc), &d_enc, kHpkeMinStage));
+  CHK(stage_in(c, c->hpke.ct_in, payloads, rows_span(n, ppitch, plen), &d_pay, kHpkeMinStage));
+  CHK(stage_in(c, c->hpke.status, status, n, &d_st_in, kHpkeMinStage));
   uint8_t* d_st = const_cast<uint8_t*>(d_st_in);
   uint8_t* d_out = out_shares;
   if (out_host) {
-    CHK(c->hpke[5].ensure(std::max<size_t>(out_bytes, kHpkeMinStage)));
-    d_out = c->hpke[5].u8();
+    CHK(c->hpke.pt_out.ensure(std::max<size_t>(out_bytes, kHpkeMinStage)));
+    d_out = c->hpke.pt_out.u8();
   }
-  CHK(c->hpke[8].ensure(dh_bytes));
-  uint32_t* d_dh = static_cast<uint32_t*>(c->hpke[8].p);
   // the ladder reads packed encapsulated keys: a pitched column is gathered first
   const uint8_t* d_enc_packed = d_enc;
   if (epitch != nenc) {
-    CHK(c->seal[7].ensure(n * nenc));
-    HIPCHK(hipMemcpy2DAsync(c->seal[7].p, nenc, d_enc, epitch, nenc, n, hipMemcpyDeviceToDevice,
-                            c->stream));
-    d_enc_packed = c->seal[7].u8();
+    CHK(c->seal.enc_packed.ensure(n * nenc));
+    HIPCHK(hipMemcpy2DAsync(c->seal.enc_packed.p, nenc, d_enc, epitch, nenc, n,
+                            hipMemcpyDeviceToDevice, c->stream));
+    d_enc_packed = c->seal.enc_packed.u8();
   }
-  int rc;
-  if (p256) {
-    uint8_t* d_ok = c->hpke[8].u8() + n * 32;
-    bc.dh_ok = d_ok;
-    rc = launch_p256_dh(c, sk, pk, bc, /*raw=*/false, n, d_enc_packed, d_dh, d_ok);
-  } else {
-    rc = launch_x25519(c, sk, n, d_enc_packed, d_dh);
-  }
-  if (!rc) {
+  // the per-report secrets: the DH values (keys, nonces and round keys never leave registers)
+  // and, after their copy, the staged share rows
+  CallSecrets sec;
+  int rc = [&]() -> int {
+    uint32_t* d_dh;
+    CHK(open_dh(c, sec, kem_id, sk, pk, bc, /*raw=*/false, n, d_enc_packed, &d_dh));
     {
       PROF(KID_HPKE_OPEN_TEAM_SHARES);
-      hpke_team_dispatch(c, bc, [&](auto kdf, auto aead) {
+      hpke_suite_dispatch(bc, [&](auto kdf, auto aead) {
         hipLaunchKernelGGL((k_hpke_open_team_shares<decltype(kdf)::value, decltype(aead)::value>),
                            dim3((unsigned)((n + kTeamsPerBlock - 1) / kTeamsPerBlock)), dim3(256),
                            0, c->stream, (uint32_t)n, bc, tid, d_dh, d_rid,
@@ -1198,27 +1157,16 @@ int prio3gpu_open_input_shares(prio3gpu_ctx* c, const uint8_t* task_id, uint16_t
                            d_out, (uint64_t)(out_host ? input_share_len : spitch), d_st);
       });
     }
-    if (hipGetLastError() != hipSuccess) {
-      set_err("launching k_hpke_open_team_shares failed");
-      rc = PRIO3GPU_E_HIP;
-    }
+    HIPCHK(hipGetLastError());
+    return 0;
+  }();
+  rc = sec.finish(c, rc);
+  if (out_host && out_bytes) {
+    sec.add(d_out, out_bytes);
+    if (!rc) rc = packed_rows_to_host(c, out_shares, spitch, d_out, input_share_len, n);
+    rc = sec.finish(c, rc);
   }
-  // the per-report secrets: the DH values (keys, nonces and round keys never leave registers)
-  if (hipMemsetAsync(d_dh, 0, dh_bytes, c->stream) != hipSuccess && !rc) {
-    set_err("clearing the DH values failed");
-    rc = PRIO3GPU_E_HIP;
-  }
-  if (!rc && out_host && out_bytes) {
-    rc = seal_rows_to_host(c, out_shares, spitch, d_out, input_share_len, n);
-    if (hipMemsetAsync(d_out, 0, out_bytes, c->stream) != hipSuccess && !rc) {
-      set_err("clearing the staged input shares failed");
-      rc = PRIO3GPU_E_HIP;
-    }
-  }
-  if (rc) {
-    (void)hipStreamSynchronize(c->stream);
-    return rc;
-  }
+  if (rc) return rc;
   CHK(copy_out(c, status, d_st, n));
   return finish_call(c, {report_ids, times, public_shares, encs, payloads, out_shares, status});
 }
@@ -1312,7 +1260,7 @@ int prio3gpu_helper_init_request(
   if (!rc) rc = req_open_groups(q);
   if (!rc) rc = req_decode(q);
   if (!rc) rc = req_host_fallback(q);
-  CHK(req_clear_secrets(q, rc));
+  CHK(q.sec.finish(c, rc));
   CHK(copy_out(c, out_nonces, st->nonces.u8(), n * 16));
   rc = prio3gpu_helper_init(c, st, n, st->nonces.u8(), st->pub.u8(), q.d_in, c->io[0].u8(),
                             batch_slots, out_prep_msgs, q.d_status, agg);
@@ -1340,20 +1288,20 @@ int prio3gpu_test_req_gather(prio3gpu_ctx* c, const uint8_t* msg, size_t msg_len
   HIPCHK(hipSetDevice(c->device));
   const size_t nb_pub = n * (size_t)g.public_share_len, nb_lps = n * (size_t)g.prep_share_len;
   const uint8_t* d_msg;
-  CHK(stage_in(c, c->req[0], msg, msg_len, &d_msg, 16));
-  CHK(c->req[1].ensure(n * sizeof(ReqView)));
-  CHK(c->req[6].ensure(n));
+  CHK(stage_in(c, c->req.msg, msg, msg_len, &d_msg, 16));
+  CHK(c->req.views.ensure(n * sizeof(ReqView)));
+  CHK(c->req.faults.ensure(n));
   CHK(c->io[0].ensure(std::max<size_t>(nb_lps, 16)));
   CHK(c->io[1].ensure(std::max<size_t>(nb_pub, 16)));
   CHK(c->io[2].ensure(n * 16));
-  HIPCHK(hipMemcpyAsync(c->req[1].p, views, n * sizeof(ReqView), hipMemcpyHostToDevice,
+  HIPCHK(hipMemcpyAsync(c->req.views.p, views, n * sizeof(ReqView), hipMemcpyHostToDevice,
                         c->stream));
-  CHK(launch_req_gather(c, n, d_msg, msg_len, static_cast<const ReqView*>(c->req[1].p),
-                        c->io[2].u8(), c->io[1].u8(), c->io[0].u8(), c->req[6].u8()));
+  CHK(launch_req_gather(c, n, d_msg, msg_len, static_cast<const ReqView*>(c->req.views.p),
+                        c->io[2].u8(), c->io[1].u8(), c->io[0].u8(), c->req.faults.u8()));
   CHK(copy_out(c, nonces, c->io[2].u8(), n * 16));
   CHK(copy_out(c, public_shares, c->io[1].u8(), nb_pub));
   CHK(copy_out(c, leader_prep_shares, c->io[0].u8(), nb_lps));
-  CHK(copy_out(c, faults, c->req[6].u8(), n));
+  CHK(copy_out(c, faults, c->req.faults.u8(), n));
   HIPCHK(hipStreamSynchronize(c->stream));
   return 0;
 }
@@ -1367,19 +1315,15 @@ int prio3gpu_test_x25519_gpu(prio3gpu_ctx* c, const uint8_t* sk, const uint8_t* 
   if (n == 0) return 0;
   HIPCHK(hipSetDevice(c->device));
   const uint8_t* d_pts;
-  CHK(stage_in(c, c->hpke[0], points, n * 32, &d_pts, kHpkeMinStage));
-  uint8_t* d_out = out;
-  if (!is_device_ptr(out)) {
-    CHK(c->hpke[8].ensure(n * 32));
-    d_out = c->hpke[8].u8();
-  }
-  CHK(launch_x25519(c, sk, n, d_pts, reinterpret_cast<uint32_t*>(d_out)));
-  if (d_out != out) {
-    HIPCHK(hipMemcpyAsync(out, d_out, n * 32, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(hipMemsetAsync(d_out, 0, n * 32, c->stream));
-  }
+  CHK(stage_in(c, c->hpke.enc_in, points, n * 32, &d_pts, kHpkeMinStage));
+  CallSecrets sec;  // the DH values are this hook's output: cleared after their copy
+  HpkeBatchConsts bc{};
+  uint32_t* d_dh;
+  int rc = open_dh(c, sec, 0x0020, sk, nullptr, bc, /*raw=*/false, n, d_pts, &d_dh);
+  if (!rc) rc = copy_out(c, out, d_dh, n * 32);
+  rc = sec.finish(c, rc);
   HIPCHK(hipStreamSynchronize(c->stream));
-  return 0;
+  return rc;
 }
 
 int prio3gpu_test_p256_gpu(prio3gpu_ctx* c, const uint8_t* sk, const uint8_t* points, size_t n,
@@ -1397,16 +1341,13 @@ int prio3gpu_test_p256_gpu(prio3gpu_ctx* c, const uint8_t* sk, const uint8_t* po
   HpkeBatchConsts bc{};  // raw mode hashes nothing: the pad states are not read
   HIPCHK(hipSetDevice(c->device));
   const uint8_t* d_pts;
-  CHK(stage_in(c, c->hpke[0], points, n * 65, &d_pts, kHpkeMinStage));
-  CHK(c->hpke[8].ensure(n * 33));
-  uint8_t* d_out = c->hpke[8].u8();
-  int rc = launch_p256_dh(c, sk, kP256G, bc, /*raw=*/true, n, d_pts,
-                          reinterpret_cast<uint32_t*>(d_out), d_out + n * 32);
-  if (!rc && hipMemcpyAsync(out_x, d_out, n * 32, hipMemcpyDeviceToHost, c->stream) != hipSuccess)
-    rc = PRIO3GPU_E_HIP;
-  if (!rc && hipMemcpyAsync(ok, d_out + n * 32, n, hipMemcpyDeviceToHost, c->stream) != hipSuccess)
-    rc = PRIO3GPU_E_HIP;
-  (void)hipMemsetAsync(d_out, 0, n * 33, c->stream);
+  CHK(stage_in(c, c->hpke.enc_in, points, n * 65, &d_pts, kHpkeMinStage));
+  CallSecrets sec;  // the DH values are this hook's output: cleared after their copy
+  uint32_t* d_dh;
+  int rc = open_dh(c, sec, 0x0010, sk, kP256G, bc, /*raw=*/true, n, d_pts, &d_dh);
+  if (!rc) rc = copy_out(c, out_x, d_dh, n * 32);
+  if (!rc) rc = copy_out(c, ok, dh_ok_at(d_dh, n), n);
+  rc = sec.finish(c, rc);
   HIPCHK(hipStreamSynchronize(c->stream));
   return rc;
 }
@@ -1421,21 +1362,20 @@ int prio3gpu_test_p256_eph_gpu(prio3gpu_ctx* c, const uint8_t* pk, const uint8_t
   if (n == 0) return 0;
   HIPCHK(hipSetDevice(c->device));
   const uint8_t* d_sk;
-  const size_t eph_bytes = n * kP256EphBytes;
-  CHK(stage_in(c, c->seal[0], sk_es, n * 32, &d_sk, kHpkeMinStage));
-  CHK(c->seal[1].ensure(eph_bytes));
-  uint8_t* d_eph = c->seal[1].u8();
-  std::vector<uint8_t> h(eph_bytes);
-  int rc = launch_p256_eph(c, pk, n, d_sk, reinterpret_cast<uint32_t*>(d_eph));
-  if (!rc && hipMemcpyAsync(h.data(), d_eph, eph_bytes, hipMemcpyDeviceToHost, c->stream) !=
-                 hipSuccess)
-    rc = PRIO3GPU_E_HIP;
-  (void)hipMemsetAsync(d_eph, 0, eph_bytes, c->stream);
-  if (d_sk == c->seal[0].u8()) (void)hipMemsetAsync(c->seal[0].p, 0, n * 32, c->stream);
+  const size_t nb = eph_bytes(n, /*p256=*/true);
+  CHK(c->seal.eph.ensure(nb));
+  uint8_t* d_eph = c->seal.eph.u8();
+  std::vector<uint8_t> h(nb);
+  CallSecrets sec;  // the ladders' output is this hook's: cleared after its copy
+  sec.add(d_eph, nb);
+  int rc = stage_secret(c, sec, c->seal.eph_sk, sk_es, n * 32, &d_sk);
+  if (!rc) rc = launch_p256_eph(c, pk, n, d_sk, reinterpret_cast<uint32_t*>(d_eph));
+  if (!rc) rc = copy_out(c, h.data(), d_eph, nb);
+  rc = sec.finish(c, rc);
   HIPCHK(hipStreamSynchronize(c->stream));
   if (rc) return rc;
   for (size_t i = 0; i < n; ++i) {  // enc = 0x04 || x || y; all zeros for a refused scalar
-    ok[i] = h[n * 96 + i];
+    ok[i] = p256_eph_ok_at(h.data(), n)[i];
     out_enc[i * 65] = ok[i] ? 0x04 : 0x00;
     memcpy(out_enc + i * 65 + 1, &h[i * 64], 64);
     memcpy(out_dh_x + i * 32, &h[n * 64 + i * 32], 32);
@@ -1463,15 +1403,15 @@ int prio3gpu_test_poly1305_gpu(prio3gpu_ctx* c, const uint8_t* keys, const uint8
   }
   HIPCHK(hipSetDevice(c->device));
   const uint8_t *d_keys, *d_msgs, *d_off;
-  CHK(stage_in(c, c->hpke[0], keys, n * 32, &d_keys, kHpkeMinStage));
-  CHK(stage_in(c, c->hpke[1], msgs, total, &d_msgs, kHpkeMinStage));
-  CHK(stage_in(c, c->hpke[2], msg_offsets, (n + 1) * 8, &d_off, kHpkeMinStage));
-  CHK(c->hpke[5].ensure(n * 16));
+  CHK(stage_in(c, c->hpke.enc_in, keys, n * 32, &d_keys, kHpkeMinStage));
+  CHK(stage_in(c, c->hpke.aad, msgs, total, &d_msgs, kHpkeMinStage));
+  CHK(stage_in(c, c->hpke.aad_off, msg_offsets, (n + 1) * 8, &d_off, kHpkeMinStage));
+  CHK(c->hpke.pt_out.ensure(n * 16));
   hipLaunchKernelGGL(k_test_poly1305, dim3((unsigned)((n + 63) / 64)), dim3(64), 0, c->stream,
                      (uint32_t)n, d_keys, d_msgs, reinterpret_cast<const uint64_t*>(d_off),
-                     c->hpke[5].u8());
+                     c->hpke.pt_out.u8());
   HIPCHK(hipGetLastError());
-  HIPCHK(hipMemcpyAsync(tags, c->hpke[5].u8(), n * 16, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(hipMemcpyAsync(tags, c->hpke.pt_out.u8(), n * 16, hipMemcpyDeviceToHost, c->stream));
   HIPCHK(hipStreamSynchronize(c->stream));
   return 0;
 }

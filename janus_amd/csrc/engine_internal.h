@@ -112,6 +112,34 @@ struct Prof {
   }
 };
 
+// The context's scratch of the GPU HPKE paths (engine_hpke.hip), a member per buffer, named after
+// its widest use and grown on demand to the largest call seen.  Where a call uses another
+// family's member it is said here, so a reader sees which uses may overlap.
+
+// The opens: staging of host inputs and outputs, and the ladder's DH values (dh_bytes: 32 bytes
+// per report, for P-256 the shared secrets, then P-256's validity bytes).  The seals stage their
+// AADs, AAD offsets, ciphertext offsets and statuses in aad, aad_off, ct_off and status;
+// prio3gpu_open_input_shares has its payload rows in ct_in and its opened share rows in pt_out.
+struct HpkeOpenScratch {
+  DevBuf enc_in, aad, aad_off, ct_in, ct_off, pt_out, pt_off, status, dh;
+};
+
+// The seals: staging of host inputs (ephemeral keys, plaintexts or share rows, plaintext
+// offsets, report IDs, times, public shares), the ladders' output (eph_bytes) and staging of host
+// outputs.  prio3gpu_open_input_shares stages its report IDs, times and public shares in rid,
+// time and pub.  enc_packed has two roles: the seals' staged enc rows, and the packed copy that
+// open's ladder reads when its enc column is pitched.
+struct HpkeSealScratch {
+  DevBuf eph_sk, eph, pt_in, pt_off, rid, time, pub, enc_packed, ct_out;
+};
+
+// prio3gpu_helper_init_request: the request, its views, the key groups' member lists, DH values
+// (as HpkeOpenScratch::dh), plaintexts, their offsets, the gather's fault bytes, and the
+// host-fallback reports' packed upload.
+struct ReqScratch {
+  DevBuf msg, views, group_idx, dh, pt, pt_off, faults, fallback;
+};
+
 }  // namespace p3g::eng
 
 // The engine's units work inside these two namespaces; the ABI's handle types below are global.
@@ -133,19 +161,9 @@ struct prio3gpu_ctx {
   // generic staging (inputs given as host pointers) and scratch
   DevBuf io[6];
   DevBuf perm, chunks, partials, pcounts, spec_idx;
-  // prio3gpu_hpke_open_batch: staging of host inputs / outputs (enc, aad, aad offsets, ct, ct
-  // offsets, pt, pt offsets, status) and the ladder's DH values (for P-256 the shared secrets
-  // and, behind them, one validity byte per report); grown on demand
-  DevBuf hpke[9];
-  // prio3gpu_helper_init_request: the request, its views, key-group index lists, DH values,
-  // plaintexts, plaintext offsets, faults, and the host-fallback reports' compact rows; grown on
-  // demand to the largest job seen
-  DevBuf req[8];
-  // prio3gpu_hpke_seal_batch / prio3gpu_seal_input_shares: staging of host inputs (ephemeral keys,
-  // plaintexts or share rows, plaintext offsets, report IDs, times, public shares), the ladders'
-  // encapsulated keys and DH values, and staging of host outputs (encs, ciphertexts); grown on
-  // demand.  The AADs, their offsets, the ciphertext offsets and the statuses share hpke[]
-  DevBuf seal[9];
+  HpkeOpenScratch hpke;  // the GPU HPKE paths' scratch, by family (above)
+  ReqScratch req;
+  HpkeSealScratch seal;
   // Engine options (prio3gpu_ctx_set_option; include/prio3gpu.h lists them).  The defaults are the
   // measured-fastest paths; every alternative is parity-tested against the oracle.
   bool speculate = true;     // "speculate": accumulation from k_jr's column sums (0: direct)

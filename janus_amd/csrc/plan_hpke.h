@@ -46,6 +46,9 @@ inline void plaintext_offsets(const prio3gpu_prepare_init_view* views, size_t n,
 // HPKE_OPT_SUITES, what the parameter meant while it was a bool).
 constexpr unsigned HPKE_OPT_SUITES = 1u;  // "hpke_gpu_suites": every KDF and AEAD
 constexpr unsigned HPKE_OPT_P256 = 2u;    // "hpke_gpu_p256": DHKEM(P-256, HKDF-SHA256) too
+// "hpke_team_chacha": the wave-per-report opens and seals take ChaCha20-Poly1305 (no part in what
+// hpke_gpu_suite, and so plan_hpke, answers)
+constexpr unsigned HPKE_OPT_TEAM_CHACHA = 4u;
 
 // The suites the GPU opens: DHKEM(X25519, HKDF-SHA256) / HKDF-SHA256 / AES-128-GCM always; with
 // HPKE_OPT_P256 the same under DHKEM(P-256, HKDF-SHA256); with HPKE_OPT_SUITES every KDF and AEAD
@@ -56,8 +59,51 @@ inline bool hpke_gpu_suite(unsigned opts, uint16_t kem, uint16_t kdf, uint16_t a
   return (opts & HPKE_OPT_SUITES) && kdf >= 1 && kdf <= 3 && aead >= 1 && aead <= 3;
 }
 
+// The suites the GPU seals a lane per report (the seal has entry points of its own, so no option
+// but the KEM's): DHKEM(X25519, HKDF-SHA256) with KDF 1-3 and AEAD 1-3, and with HPKE_OPT_P256
+// the same under DHKEM(P-256, HKDF-SHA256).
+inline bool hpke_seal_suite(unsigned opts, uint16_t kem, uint16_t kdf, uint16_t aead) {
+  return (kem == 0x0020 || (kem == 0x0010 && (opts & HPKE_OPT_P256))) && kdf >= 1 && kdf <= 3 &&
+         aead >= 1 && aead <= 3;
+}
+
+// The suites the wave-per-report opens and seals take (hpke_open_team.h, hpke_seal_team.h):
+// hpke_seal_suite's, ChaCha20-Poly1305 (AEAD 3) only with HPKE_OPT_TEAM_CHACHA.
+inline bool hpke_team_suite(unsigned opts, uint16_t kem, uint16_t kdf, uint16_t aead) {
+  return hpke_seal_suite(opts, kem, kdf, aead) && (aead != 3 || (opts & HPKE_OPT_TEAM_CHACHA));
+}
+
 // Nenc = Npk of a KEM the GPU opens (RFC 9180 §7.1): 32 for X25519, 65 for P-256.
 inline uint32_t hpke_kem_nenc(uint16_t kem) { return kem == 0x0010 ? 65u : 32u; }
+
+// The three columns of prio3gpu_seal_input_shares[_long] and prio3gpu_open_input_shares: rows of
+// nenc (encapsulated key), plen (payload: the 6 bytes around an extension-free share, the share,
+// the 16-byte tag) and input_share_len bytes, each `pitch` bytes apart; a pitch of 0 means
+// packed, the row's own width.  *_ok: the pitch holds its row.
+struct ShareColumns {
+  uint64_t nenc, plen;
+  uint64_t enc_pitch, payload_pitch, share_pitch;  // effective
+  bool enc_ok, payload_ok, share_ok;
+  bool ok() const { return enc_ok && payload_ok && share_ok; }
+};
+inline ShareColumns share_columns(uint16_t kem, uint32_t input_share_len, uint64_t enc_pitch,
+                                  uint64_t payload_pitch, uint64_t share_pitch) {
+  ShareColumns g{};
+  g.nenc = hpke_kem_nenc(kem);
+  g.plen = 6 + (uint64_t)input_share_len + 16;
+  g.enc_pitch = enc_pitch ? enc_pitch : g.nenc;
+  g.payload_pitch = payload_pitch ? payload_pitch : g.plen;
+  g.share_pitch = share_pitch ? share_pitch : input_share_len;
+  g.enc_ok = g.enc_pitch >= g.nenc;
+  g.payload_ok = g.payload_pitch >= g.plen;
+  g.share_ok = g.share_pitch >= input_share_len;
+  return g;
+}
+
+// Bytes from the first row's start to the last row's end: n >= 1 rows of `width` bytes.
+inline uint64_t rows_span(uint64_t n, uint64_t pitch, uint64_t width) {
+  return (n - 1) * pitch + width;
+}
 
 // P-256 order n, big-endian
 constexpr uint8_t kP256Order[32] = {0xff, 0xff, 0xff, 0xff, 0x00, 0x00, 0x00, 0x00, 0xff, 0xff, 0xff,

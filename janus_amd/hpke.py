@@ -175,6 +175,45 @@ def _ptr(x, dtype):
     return a.ctypes.data, a
 
 
+def _dev_ptr(x, dtype):
+    """_ptr that also takes a torch tensor (host or device): its pointer, the tensor kept alive."""
+    if hasattr(x, "data_ptr"):
+        if not x.is_contiguous():
+            raise ValueError("tensors must be contiguous")
+        return x.data_ptr(), x
+    return _ptr(x, dtype)
+
+
+def _open_batch_gpu(entry: str, what: str, gpu, keypair: HpkeKeypair, info: bytes, encs, aads,
+                    aad_offsets, cts, ct_offsets, pts, pt_offsets, status, n):
+    """`open_batch_gpu` / `open_long_batch_gpu` through the library's entry point `entry`."""
+    c = keypair.config
+    if n is None:
+        n = len(np.asarray(ct_offsets)) - 1
+    if pt_offsets is None:
+        lens = np.diff(np.asarray(ct_offsets, np.uint64).astype(np.int64)) - 16
+        pt_offsets = np.concatenate([[0], np.cumsum(np.maximum(lens, 0))]).astype(np.uint64)
+    if pts is None:
+        pts = np.zeros(max(1, int(np.asarray(pt_offsets)[-1])), np.uint8)
+    if status is None:
+        status = np.zeros(max(1, n), np.uint8)
+    keep, args = [], []
+    for x, dt in ((encs, np.uint8), (aads, np.uint8), (aad_offsets, np.uint64), (cts, np.uint8),
+                  (ct_offsets, np.uint64), (pts, np.uint8), (pt_offsets, np.uint64),
+                  (status, np.uint8)):
+        p, k = _dev_ptr(x, dt)
+        args.append(p)
+        keep.append(k)
+    for out, k in ((pts, keep[5]), (status, keep[7])):  # outputs must be written in place
+        assert k is None or k is out, "pts / status must be contiguous uint8 arrays"
+    _rc(getattr(lib(), entry)(_ctx_handle(gpu), c.kem_id, c.kdf_id, c.aead_id,
+                              _buf(keypair.private_key), len(keypair.private_key),
+                              _buf(c.public_key), len(c.public_key), _buf(info), len(info), n,
+                              *args), what)
+    del keep
+    return pts, pt_offsets, status
+
+
 def open_batch_gpu(gpu, keypair: HpkeKeypair, info: bytes, encs, aads, aad_offsets, cts,
                    ct_offsets, pts=None, pt_offsets=None, status=None, n: Optional[int] = None):
     """n HPKE opens under ONE keypair on the GPU (prio3gpu_hpke_open_batch).  By default only
@@ -186,45 +225,13 @@ def open_batch_gpu(gpu, keypair: HpkeKeypair, info: bytes, encs, aads, aad_offse
     `gpu` is a `Prio3Gpu` or a context handle.  Report i: enc = encs[Nenc i : Nenc i + Nenc] with
     Nenc = 32 for X25519 and 65 for P-256 (the stride follows the keypair's KEM), aad =
     aads[aad_offsets[i] : aad_offsets[i+1]], ciphertext || tag = cts[ct_offsets[i] :
-    ct_offsets[i+1]].  Buffers are numpy arrays (host) or integer device pointers (then `n`,
-    `pts`, `pt_offsets` and `status` must be given).  By default plaintext i has the ciphertext's
+    ct_offsets[i+1]].  Buffers are numpy arrays (host), integer device pointers (then `n`, `pts`,
+    `pt_offsets` and `status` must be given) or, as `open_long_batch_gpu` has always taken them,
+    contiguous torch tensors (host or device).  By default plaintext i has the ciphertext's
     length - 16 and the plaintexts are packed.
     -> (plaintexts, pt_offsets, status); a failed open has status 4 and zeros."""
-    c = keypair.config
-    if n is None:
-        n = len(np.asarray(ct_offsets)) - 1
-    if pt_offsets is None:
-        lens = np.diff(np.asarray(ct_offsets, np.uint64).astype(np.int64)) - 16
-        pt_offsets = np.concatenate([[0], np.cumsum(np.maximum(lens, 0))]).astype(np.uint64)
-    if pts is None:
-        pts = np.zeros(max(1, int(np.asarray(pt_offsets)[-1])), np.uint8)
-    if status is None:
-        status = np.zeros(max(1, n), np.uint8)
-    keep = []
-    args = []
-    for x, dt in ((encs, np.uint8), (aads, np.uint8), (aad_offsets, np.uint64), (cts, np.uint8),
-                  (ct_offsets, np.uint64), (pts, np.uint8), (pt_offsets, np.uint64),
-                  (status, np.uint8)):
-        p, k = _ptr(x, dt)
-        args.append(p)
-        keep.append(k)
-    for out, k in ((pts, keep[5]), (status, keep[7])):  # outputs must be written in place
-        assert k is None or k is out, "pts / status must be contiguous uint8 arrays"
-    _rc(lib().prio3gpu_hpke_open_batch(_ctx_handle(gpu), c.kem_id, c.kdf_id, c.aead_id,
-                                       _buf(keypair.private_key), len(keypair.private_key),
-                                       _buf(c.public_key), len(c.public_key), _buf(info),
-                                       len(info), n, *args), "HPKE GPU open")
-    del keep
-    return pts, pt_offsets, status
-
-
-def _dev_ptr(x, dtype):
-    """_ptr that also takes a torch tensor (host or device): its pointer, the tensor kept alive."""
-    if hasattr(x, "data_ptr"):
-        if not x.is_contiguous():
-            raise ValueError("tensors must be contiguous")
-        return x.data_ptr(), x
-    return _ptr(x, dtype)
+    return _open_batch_gpu("prio3gpu_hpke_open_batch", "HPKE GPU open", gpu, keypair, info, encs,
+                           aads, aad_offsets, cts, ct_offsets, pts, pt_offsets, status, n)
 
 
 def _seal_batch_gpu(entry: str, gpu, config: HpkeConfig, info: bytes, sk_es, aads, aad_offsets,
@@ -393,31 +400,9 @@ def open_long_batch_gpu(gpu, keypair: HpkeKeypair, info: bytes, encs, aads, aad_
     arguments, plaintexts and statuses; buffers are numpy arrays (host), torch tensors (host or
     device) or integer device pointers (then `n`, `pts`, `pt_offsets` and `status` must be given).
     -> (plaintexts, pt_offsets, status); a failed open has status 4 and zeros."""
-    c = keypair.config
-    if n is None:
-        n = len(np.asarray(ct_offsets)) - 1
-    if pt_offsets is None:
-        lens = np.diff(np.asarray(ct_offsets, np.uint64).astype(np.int64)) - 16
-        pt_offsets = np.concatenate([[0], np.cumsum(np.maximum(lens, 0))]).astype(np.uint64)
-    if pts is None:
-        pts = np.zeros(max(1, int(np.asarray(pt_offsets)[-1])), np.uint8)
-    if status is None:
-        status = np.zeros(max(1, n), np.uint8)
-    keep, args = [], []
-    for x, dt in ((encs, np.uint8), (aads, np.uint8), (aad_offsets, np.uint64), (cts, np.uint8),
-                  (ct_offsets, np.uint64), (pts, np.uint8), (pt_offsets, np.uint64),
-                  (status, np.uint8)):
-        p, k = _dev_ptr(x, dt)
-        args.append(p)
-        keep.append(k)
-    for out, k in ((pts, keep[5]), (status, keep[7])):  # outputs must be written in place
-        assert k is None or k is out, "pts / status must be contiguous uint8 arrays"
-    _rc(lib().prio3gpu_hpke_open_long_batch(_ctx_handle(gpu), c.kem_id, c.kdf_id, c.aead_id,
-                                            _buf(keypair.private_key), len(keypair.private_key),
-                                            _buf(c.public_key), len(c.public_key), _buf(info),
-                                            len(info), n, *args), "HPKE GPU open (long)")
-    del keep
-    return pts, pt_offsets, status
+    return _open_batch_gpu("prio3gpu_hpke_open_long_batch", "HPKE GPU open (long)", gpu, keypair,
+                           info, encs, aads, aad_offsets, cts, ct_offsets, pts, pt_offsets,
+                           status, n)
 
 
 def open_input_shares_gpu(gpu, task_id: bytes, keypair: HpkeKeypair, recipient_role: int,

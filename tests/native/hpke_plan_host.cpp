@@ -14,6 +14,10 @@
 //       PUBLIC_SHARE_OFF PUBLIC_SHARE_LEN ENC_OFF ENC_LEN PAYLOAD_OFF PAYLOAD_LEN PREP_SHARE_OFF
 //       PREP_SHARE_LEN PREP_MSG_OFF PREP_MSG_LEN" (the other views are all zero)
 //       -> "ok" or "err CODE MESSAGE"
+//   suites OPTS KEM KDF AEAD -> "G T S": hpke_gpu_suite, hpke_team_suite, hpke_seal_suite (0 / 1)
+//   columns KEM SHARE_LEN ENC_PITCH PAYLOAD_PITCH SHARE_PITCH -> share_columns: "NENC PLEN
+//       ENC_PITCH PAYLOAD_PITCH SHARE_PITCH ENC_OK PAYLOAD_OK SHARE_OK OK"
+//   rows N PITCH WIDTH -> rows_span
 #include <stdio.h>
 
 #include <iostream>
@@ -140,6 +144,26 @@ int main() {
       uint64_t off, len, total;
       in >> off >> len >> total;
       printf("%d\n", (int)span_fits(off, len, total));
+    } else if (cmd == "suites") {
+      unsigned opts, kem, kdf, aead;
+      in >> opts >> kem >> kdf >> aead;
+      printf("%d %d %d\n", (int)hpke_gpu_suite(opts, (uint16_t)kem, (uint16_t)kdf, (uint16_t)aead),
+             (int)hpke_team_suite(opts, (uint16_t)kem, (uint16_t)kdf, (uint16_t)aead),
+             (int)hpke_seal_suite(opts, (uint16_t)kem, (uint16_t)kdf, (uint16_t)aead));
+    } else if (cmd == "columns") {
+      unsigned kem;
+      uint32_t share_len;
+      uint64_t ep, pp, sp;
+      in >> kem >> share_len >> ep >> pp >> sp;
+      const ShareColumns g = share_columns((uint16_t)kem, share_len, ep, pp, sp);
+      printf("%llu %llu %llu %llu %llu %d %d %d %d\n", (unsigned long long)g.nenc,
+             (unsigned long long)g.plen, (unsigned long long)g.enc_pitch,
+             (unsigned long long)g.payload_pitch, (unsigned long long)g.share_pitch,
+             (int)g.enc_ok, (int)g.payload_ok, (int)g.share_ok, (int)g.ok());
+    } else if (cmd == "rows") {
+      uint64_t n, pitch, width;
+      in >> n >> pitch >> width;
+      printf("%llu\n", (unsigned long long)rows_span(n, pitch, width));
     } else if (cmd == "blocks" || cmd == "views") {
       Cfg g{};
       in >> g.public_share_len >> g.prep_share_len;

@@ -293,3 +293,73 @@ def test_req_gather_blocks_and_capacity(plan_bin):
     assert gather_blocks(pub, 0, n_over - 1) <= 0x7FFFFFFF
     out = run(plan_bin, ["views %d 0 16 %d 0" % (pub, k) for k in (n_over - 1, n_over)])
     assert out == ["ok", "err %d job too large for one gather launch" % E_CAPACITY]
+
+
+# ---- the suites of the three families of entry points --------------------------------------------
+OPT_SUITES, OPT_P256, OPT_TEAM_CHACHA = 1, 2, 4
+
+
+def suites_model(opts, kem, kdf, aead):
+    """(hpke_gpu_suite, hpke_team_suite, hpke_seal_suite), restated."""
+    kem_ok = kem == X25519 or (kem == P256 and bool(opts & OPT_P256))
+    nine = kdf in (1, 2, 3) and aead in (1, 2, 3)
+    gpu = kem_ok and ((kdf, aead) == (1, 1) or (bool(opts & OPT_SUITES) and nine))
+    team = kem_ok and nine and (aead != 3 or bool(opts & OPT_TEAM_CHACHA))
+    return int(gpu), int(team), int(kem_ok and nine)
+
+
+def test_suite_predicates_over_the_full_table(plan_bin):
+    table = [(o, kem, kdf, aead) for o in range(8) for kem in (P256, X25519, 0x21)
+             for kdf in range(5) for aead in range(5)]
+    out = run(plan_bin, ["suites %d %d %d %d" % t for t in table])
+    got = dict(zip(table, (tuple(map(int, line.split())) for line in out)))
+    assert len(out) == len(table) == 600
+    assert got == {t: suites_model(*t) for t in table}
+    # the restatement itself, at the corners: (open a lane, a wave per report, seal a lane)
+    assert got[(0, X25519, 1, 1)] == (1, 1, 1) and got[(0, X25519, 1, 3)] == (0, 0, 1)
+    assert got[(OPT_SUITES, X25519, 3, 3)] == (1, 0, 1)
+    assert got[(OPT_TEAM_CHACHA, X25519, 2, 3)] == (0, 1, 1)
+    assert got[(OPT_SUITES | OPT_TEAM_CHACHA, P256, 1, 1)] == (0, 0, 0)
+    assert got[(OPT_P256, P256, 1, 1)] == (1, 1, 1) and got[(OPT_P256, P256, 2, 2)] == (0, 1, 1)
+    assert got[(7, P256, 3, 3)] == (1, 1, 1) and got[(7, 0x21, 1, 1)] == (0, 0, 0)
+    assert got[(7, X25519, 0, 1)] == got[(7, X25519, 4, 1)] == got[(7, X25519, 1, 4)] == (0, 0, 0)
+
+
+# ---- the column geometry of the input-share seals and open ---------------------------------------
+def columns_model(kem, slen, ep, pp, sp):
+    nenc, plen = (65 if kem == P256 else 32), 6 + slen + 16
+    e, p, s = ep or nenc, pp or plen, sp or slen
+    oks = [int(e >= nenc), int(p >= plen), int(s >= slen)]
+    return (nenc, plen, e, p, s, *oks, int(all(oks)))
+
+
+@pytest.mark.parametrize("kem,nenc", [(X25519, 32), (P256, 65)])
+def test_share_columns(plan_bin, kem, nenc):
+    slen, plen = 100, 122
+    cases = [(kem, slen, 0, 0, 0),                        # packed
+             (kem, slen, nenc, plen, slen),               # pitch = width
+             (kem, slen, nenc - 1, plen, slen),           # one column a byte short, in turn
+             (kem, slen, nenc, plen - 1, slen),
+             (kem, slen, nenc, plen, slen - 1),
+             (kem, slen, nenc + 7, 4096, slen + 1),       # gaps
+             (kem, 0, 0, 0, 0), (kem, 0, 0, 21, 0),       # an empty share: the payload is 22 bytes
+             (kem, 0xFFFFFFFF, 0, 0, 0),                  # no 32-bit wrap
+             (kem, 0xFFFFFFFF, 0, 0xFFFFFFFF + 21, 0xFFFFFFFE)]
+    out = run(plan_bin, ["columns %d %d %d %d %d" % c for c in cases])
+    got = [tuple(map(int, line.split())) for line in out]
+    assert got == [columns_model(*c) for c in cases]
+    assert got[0] == got[1] == (nenc, plen, nenc, plen, slen, 1, 1, 1, 1)
+    assert [g[5:] for g in got[2:6]] == [(0, 1, 1, 0), (1, 0, 1, 0), (1, 1, 0, 0), (1, 1, 1, 1)]
+    assert got[6] == (nenc, 22, nenc, 22, 0, 1, 1, 1, 1) and got[7][5:] == (1, 0, 1, 0)
+    assert got[8] == (nenc, 2**32 + 21, nenc, 2**32 + 21, 2**32 - 1, 1, 1, 1, 1)
+    assert got[9][5:] == (1, 0, 0, 0)
+
+
+def test_rows_span(plan_bin):
+    big = 6 + 0xFFFFFFFF + 16
+    cases = [(1, 0, 7), (1, 4096, 122), (2, 122, 122), (3, 10, 4), (5, 32, 0),
+             (0x7FFFFFFF, big, big), (0x7FFFFFFF, 2**32, 0xFFFFFFFF)]
+    out = run(plan_bin, ["rows %d %d %d" % c for c in cases])
+    assert list(map(int, out)) == [(n - 1) * pitch + width for n, pitch, width in cases]
+    assert list(map(int, out[:4])) == [7, 122, 244, 24]      # n = 1: the row's own width
+    assert all(int(x) > 2**62 for x in out[5:])              # and nothing wrapped at 32 bits
