@@ -186,6 +186,26 @@ int prio3gpu_ctx_set_async(prio3gpu_ctx* ctx, int on);
  *                   PRIO3GPU_E_UNSUPPORTED for ChaCha20-Poly1305 (AEAD 3).  1: they take 0x0020 /
  *                   KDF 1-3 / AEAD 3 as well (chacha_poly_team.h).  It changes no other entry
  *                   point.  Any other value is PRIO3GPU_E_ARG
+ *   "hpke_team_split"  0 (default) to 256: the most waves prio3gpu_open_input_shares and
+ *                   prio3gpu_seal_input_shares_long give one report.  0 and 1: one wave per report,
+ *                   the same kernels and launches as without the option.  k >= 2: a call whose
+ *                   reports do not fill the chip by themselves cuts every report's body (6 +
+ *                   input_share_len bytes) into at most k segments, a wave each, then computes the
+ *                   tags per report (janus_amd/csrc/hpke_team_split.h; team_split_plan in
+ *                   plan_hpke.h chooses the count from n, the body, k, the option below and the
+ *                   device's wave slots, and falls back to one wave per report whenever two
+ *                   segments of the smallest size do not fit or n alone fills the chip).  Output
+ *                   bytes, statuses and the handling of secrets are the same either way.  It
+ *                   affects those two entry points only: the packed prio3gpu_hpke_open_long_batch
+ *                   and prio3gpu_hpke_seal_long_batch and every other call ignore it.  It adds no
+ *                   suite: the KEM and AEAD options above apply unchanged.  Any other value is
+ *                   PRIO3GPU_E_ARG
+ *   "hpke_team_split_blocks"  the smallest segment "hpke_team_split" gives a wave, in 16-byte
+ *                   blocks: a multiple of 256 from 256 to 2^24.  Default 16384 (256 KiB), the
+ *                   smallest measured size at which a share of two such segments is sealed and
+ *                   opened faster by two waves than by one: the tags per
+ *                   report cost about 0.6 ms of their own under AES-GCM, so shorter segments
+ *                   lose.  Any other value is PRIO3GPU_E_ARG
  * The engine reads no environment variables.  PRIO3GPU_E_ARG for an unknown name. */
 int prio3gpu_ctx_set_option(prio3gpu_ctx* ctx, const char* name, int64_t value);
 /* Work queued on `ctx` from now on starts only after all work queued on `other` so far. */
@@ -686,7 +706,14 @@ int prio3gpu_hpke_open_long_batch(prio3gpu_ctx* ctx, uint16_t kem_id, uint16_t k
  * task_id, sk and pk are host memory; every other pointer may be host or device (detected).
  * Secrets: the private key reaches the GPU only as a kernel argument; the buffer of the DH values
  * and the engine's staged copy of the opened rows (host out_shares) are zeroed before the call
- * returns; keys, nonces and round keys never leave registers. */
+ * returns; keys, nonces and round keys never leave registers.
+ * Output contract: no unauthenticated plaintext is in out_shares once the call's work on the
+ * context's stream is done -- in an async context before anything queued later on the stream runs,
+ * for a host out_shares before the copy-out.  With "hpke_team_split" >= 2 a report may get several
+ * waves: the rows then hold plaintext without a verdict between the call's own kernels (segments,
+ * then the verdicts per report, then zeros over every row whose status is not 0, queued back to
+ * back), and nowhere else; the segments' sums and header flags in the engine's scratch are
+ * key-derived and zeroed before the call returns, on its error paths too. */
 int prio3gpu_open_input_shares(prio3gpu_ctx* ctx, const uint8_t* task_id, uint16_t kem_id,
                                uint16_t kdf_id, uint16_t aead_id, const uint8_t* sk, size_t sk_len,
                                const uint8_t* pk, size_t pk_len, uint8_t recipient_role, size_t n,
@@ -723,7 +750,9 @@ int prio3gpu_hpke_seal_long_batch(prio3gpu_ctx* ctx, uint16_t kem_id, uint16_t k
  * arguments, pitches (0 = packed; shorter than the row = PRIO3GPU_E_ARG), statuses, handling of
  * secrets and bytes.  The enc and payload columns may sit at any alignment (a whole 16-byte block
  * leaves as the widest naturally aligned pieces its address allows); no byte outside the two
- * columns is written. */
+ * columns is written.  With "hpke_team_split" >= 2 a report may get several waves (the option's
+ * comment): the same bytes and statuses; the segments' sums in the engine's scratch are zeroed
+ * before the call returns like the ladders' output. */
 int prio3gpu_seal_input_shares_long(prio3gpu_ctx* ctx, const uint8_t* task_id, uint16_t kem_id,
                                     uint16_t kdf_id, uint16_t aead_id, const uint8_t* pk,
                                     size_t pk_len, uint8_t recipient_role, size_t n,

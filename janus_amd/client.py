@@ -204,6 +204,14 @@ class ClientBatch:
     under `long_seal=None` such a config takes the wave from `LONG_SEAL_MIN_SHARE_CHACHA` bytes
     on.  Without it a ChaCha20-Poly1305 config is sealed a lane per report, as before.
 
+    `team_split` and `team_split_blocks` set the options "hpke_team_split" and
+    "hpke_team_split_blocks" on `vdaf`'s context: where a wave per report seals a share, a small
+    batch of very long shares gets up to `team_split` waves per report, none with fewer than
+    `team_split_blocks` 16-byte blocks.  Like `team_chacha`, either is set only when given: 0 (the
+    default) and None leave the context as it is -- one wave per report on a context nobody
+    switched, still split on a `vdaf` an earlier batch switched on (`vdaf.set_option(
+    "hpke_team_split", 0)` turns it off).  The report bytes never depend on either.
+
     `p256` sets the option "hpke_gpu_p256" on `vdaf`'s context and admits P-256 configs: such an
     aggregator's encapsulated keys are 65 bytes (`layout`), its ephemeral private keys are drawn
     in [1, n) (`draw_p256_scalars`), and a caller's `sk_es` outside that range raise `HpkeError`.
@@ -226,7 +234,8 @@ class ClientBatch:
     def __init__(self, vdaf, task_id: bytes, leader_config: H.HpkeConfig,
                  helper_config: H.HpkeConfig, time_precision: int,
                  long_seal: Optional[bool] = None, team_chacha: bool = False,
-                 p256: bool = False):
+                 p256: bool = False, team_split: int = 0,
+                 team_split_blocks: Optional[int] = None):
         if len(task_id) != 32:
             raise ValueError("TaskId is 32 bytes")
         if time_precision <= 0:
@@ -250,6 +259,10 @@ class ClientBatch:
             vdaf.set_option("hpke_team_chacha", 1)
         if p256:
             vdaf.set_option("hpke_gpu_p256", 1)
+        if team_split_blocks is not None:
+            vdaf.set_option("hpke_team_split_blocks", team_split_blocks)
+        if team_split:
+            vdaf.set_option("hpke_team_split", team_split)
         s = vdaf.sizes
         # (leader, helper): whether a wave per report seals that aggregator's shares
         self._wave = tuple(

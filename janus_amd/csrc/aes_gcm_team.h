@@ -7,6 +7,9 @@
 //   gf128_powers_step                 the table H^1 .. H^T by doubling, log2 T products per lane
 //   gcm_team_power, gcm_team_stripe   one lane's share of GHASH and of the CTR decryption
 //   gcm_team_join                     the GHASH of the whole ciphertext from the lanes' XOR
+//   gcm_team_stripe_range, gcm_team_seal_stripe_range, gf128_pow, gcm_split_join
+//                                     the same over a sub-range of the blocks, and the GHASH of a
+//                                     text from its segments' sums (several waves per report)
 //   gcm_team_wipe, team_zero          zeros where a report failed, and in a slot's tail
 //   PackedSink, ShareSink             where the plaintext goes: a packed slot, or a share row with
 //                                     the PlaintextInputShare header checked and dropped
@@ -74,19 +77,22 @@ DEVI const uint32_t* gcm_team_power(const uint32_t* tbl, uint64_t b, uint64_t nb
 // 16 bytes at p (any alignment) as block words
 DEVI void load_block16(const uint8_t* p, uint32_t d[4]) { __builtin_memcpy(d, p, 16); }
 
-// One lane's stripe of a ciphertext of clen bytes (nb = ceil(clen / 16) blocks, the last one
-// zero-padded): blocks lane, lane + team, ...  With GHASH, acc (zero on entry) absorbs them as
-// acc = (acc ^ X_b) * power(b); block 0 also takes y0, the GHASH of the AAD, so the XOR of all
-// lanes' acc is the GHASH of pad16(aad) || pad16(ct).  With CTR, block b is XORed with
-// E(K, nonce || b + 2) (ctr is aes_gcm_start's; its last word is not read) and handed to
-// sink.put(b, words, bytes): all sixteen bytes, or the partial last block's.
+// One lane's stripe of the blocks [b0, b1) of a ciphertext of clen bytes (nb = ceil(clen / 16)
+// blocks, the last one zero-padded; b1 <= nb): blocks b0 + lane, b0 + lane + team, ...  Block
+// indices are the ciphertext's own, so the counter, the offsets and the padding are those of the
+// whole text.  With GHASH, acc (zero on entry) absorbs them as acc = (acc ^ X_b) * power(b), the
+// power carrying to b1; block 0 also takes y0, the GHASH of the AAD, so the XOR of all lanes' acc
+// is sum_b X_b H^(b1 - b): for [0, nb) the GHASH of pad16(aad) || pad16(ct).  With CTR, block b is
+// XORed with E(K, nonce || b + 2) (ctr is aes_gcm_start's; its last word is not read) and handed
+// to sink.put(b, words, bytes): all sixteen bytes, or the partial last block's.  The counter is 32
+// bits wide: a text of more than 2^32 - 2 blocks would wrap it, which no caller can reach (the
+// share rows' length is a u32 of bytes, the packed slots' far below).
 template <int NK, bool GHASH, bool CTR, class Sink>
-DEVI void gcm_team_stripe(const uint8_t* sbox, const uint32_t* rk, const uint32_t ctr[4],
-                          const uint32_t* tbl, const uint32_t y0[4], const uint8_t* ct,
-                          uint64_t clen, uint32_t lane, uint32_t team, uint32_t acc[4],
-                          Sink& sink) {
-  const uint64_t nb = (clen + 15) / 16;
-  for (uint64_t b = lane; b < nb; b += team) {
+DEVI void gcm_team_stripe_range(const uint8_t* sbox, const uint32_t* rk, const uint32_t ctr[4],
+                                const uint32_t* tbl, const uint32_t y0[4], const uint8_t* ct,
+                                uint64_t clen, uint64_t b0, uint64_t b1, uint32_t lane,
+                                uint32_t team, uint32_t acc[4], Sink& sink) {
+  for (uint64_t b = b0 + lane; b < b1; b += team) {
     const uint64_t o = 16 * b, rem = clen - o;
     uint32_t d[4];
     if (rem >= 16) load_block16(ct + o, d);
@@ -95,7 +101,7 @@ DEVI void gcm_team_stripe(const uint8_t* sbox, const uint32_t* rk, const uint32_
       uint32_t x[4];
 #pragma unroll
       for (int i = 0; i < 4; ++i) x[i] = bswap32(d[i]) ^ acc[i] ^ (b == 0 ? y0[i] : 0u);
-      gf128_mul(x, gcm_team_power(tbl, b, nb, team), acc);
+      gf128_mul(x, gcm_team_power(tbl, b, b1, team), acc);
     }
     if constexpr (CTR) {
       const uint32_t c[4] = {ctr[0], ctr[1], ctr[2], bswap32((uint32_t)b + 2u)};
@@ -106,6 +112,16 @@ DEVI void gcm_team_stripe(const uint8_t* sbox, const uint32_t* rk, const uint32_
       sink.put(b, d, rem < 16 ? (uint32_t)rem : 16u);
     }
   }
+}
+
+// The whole ciphertext: gcm_team_stripe_range over [0, nb).
+template <int NK, bool GHASH, bool CTR, class Sink>
+DEVI void gcm_team_stripe(const uint8_t* sbox, const uint32_t* rk, const uint32_t ctr[4],
+                          const uint32_t* tbl, const uint32_t y0[4], const uint8_t* ct,
+                          uint64_t clen, uint32_t lane, uint32_t team, uint32_t acc[4],
+                          Sink& sink) {
+  gcm_team_stripe_range<NK, GHASH, CTR>(sbox, rk, ctr, tbl, y0, ct, clen, 0, (clen + 15) / 16,
+                                        lane, team, acc, sink);
 }
 
 // The sixteen bytes at offset o of a byte source, all of which exist: the source's own whole-block
@@ -119,17 +135,19 @@ DEVI void src_whole_block(const Src& s, uint64_t o, uint32_t d[4], long) {
   s.block(o, d);
 }
 
-// The seal's mirror of gcm_team_stripe: one lane's stripe of a plaintext, a byte source (len(),
-// block(o, d)) of nb = ceil(len / 16) blocks.  Block b = lane, lane + team, ... is XORed with
-// E(K, nonce || b + 2), zeroed past the end of a partial last block, handed to
-// sink.put(b, words, bytes) and then absorbed: acc = (acc ^ C_b [^ y0 when b == 0]) * power(b), so
-// the XOR of all lanes' acc (zero on entry) is the GHASH of pad16(aad) || pad16(ciphertext).
+// The seal's mirror of gcm_team_stripe_range: one lane's stripe of the blocks [b0, b1) of a
+// plaintext, a byte source (len(), block(o, d)) of nb = ceil(len / 16) blocks (b1 <= nb).  Block
+// b = b0 + lane, b0 + lane + team, ... is XORed with E(K, nonce || b + 2), zeroed past the end of
+// a partial last block, handed to sink.put(b, words, bytes) and then absorbed:
+// acc = (acc ^ C_b [^ y0 when b == 0]) * power(b), so the XOR of all lanes' acc (zero on entry) is
+// sum_b C_b H^(b1 - b): for [0, nb) the GHASH of pad16(aad) || pad16(ciphertext).
 template <int NK, class Src, class Sink>
-DEVI void gcm_team_seal_stripe(const uint8_t* sbox, const uint32_t* rk, const uint32_t ctr[4],
-                               const uint32_t* tbl, const uint32_t y0[4], const Src& pt,
-                               uint32_t lane, uint32_t team, uint32_t acc[4], Sink& sink) {
-  const uint64_t plen = pt.len(), nb = (plen + 15) / 16;
-  for (uint64_t b = lane; b < nb; b += team) {
+DEVI void gcm_team_seal_stripe_range(const uint8_t* sbox, const uint32_t* rk,
+                                     const uint32_t ctr[4], const uint32_t* tbl,
+                                     const uint32_t y0[4], const Src& pt, uint64_t b0, uint64_t b1,
+                                     uint32_t lane, uint32_t team, uint32_t acc[4], Sink& sink) {
+  const uint64_t plen = pt.len();
+  for (uint64_t b = b0 + lane; b < b1; b += team) {
     const uint64_t o = 16 * b, rem = plen - o;
     uint32_t d[4], ek[4], x[4];
     if (rem >= 16) src_whole_block(pt, o, d, 0);
@@ -142,8 +160,17 @@ DEVI void gcm_team_seal_stripe(const uint8_t* sbox, const uint32_t* rk, const ui
     sink.put(b, d, rem < 16 ? (uint32_t)rem : 16u);
 #pragma unroll
     for (int i = 0; i < 4; ++i) x[i] = bswap32(d[i]) ^ acc[i] ^ (b == 0 ? y0[i] : 0u);
-    gf128_mul(x, gcm_team_power(tbl, b, nb, team), acc);
+    gf128_mul(x, gcm_team_power(tbl, b, b1, team), acc);
   }
+}
+
+// The whole plaintext: gcm_team_seal_stripe_range over [0, nb).
+template <int NK, class Src, class Sink>
+DEVI void gcm_team_seal_stripe(const uint8_t* sbox, const uint32_t* rk, const uint32_t ctr[4],
+                               const uint32_t* tbl, const uint32_t y0[4], const Src& pt,
+                               uint32_t lane, uint32_t team, uint32_t acc[4], Sink& sink) {
+  gcm_team_seal_stripe_range<NK>(sbox, rk, ctr, tbl, y0, pt, 0, (pt.len() + 15) / 16, lane, team,
+                                 acc, sink);
 }
 
 // y = the GHASH so far, given sum = the XOR of every lane's acc: sum itself, or y0 when there was
@@ -152,6 +179,58 @@ DEVI void gcm_team_join(uint32_t y[4], const uint32_t sum[4], const uint32_t y0[
 #pragma unroll
   for (int i = 0; i < 4; ++i) y[i] = clen ? sum[i] : y0[i];
 }
+
+// out = a^e in GF(2^128) for a public exponent e (e = 0 gives 1, the block 80 00 .. 00):
+// square-and-multiply from bit 31 down with the multiplication selected, not branched on --
+// sixty-four products whatever e is.  The exponents are block counts.
+DEVI void gf128_pow(const uint32_t a[4], uint32_t e, uint32_t out[4]) {
+  uint32_t acc[4] = {0x80000000u, 0u, 0u, 0u};
+#pragma unroll 1
+  for (int bit = 31; bit >= 0; --bit) {
+    uint32_t t[4];
+    gf128_mul(acc, acc, acc);
+    gf128_mul(acc, a, t);
+    const uint32_t m = 0u - ((e >> bit) & 1u);
+#pragma unroll
+    for (int i = 0; i < 4; ++i) acc[i] = (acc[i] & ~m) | (t[i] & m);
+  }
+#pragma unroll
+  for (int i = 0; i < 4; ++i) out[i] = acc[i];
+}
+
+// A text of nb blocks cut into S >= 2 segments of L blocks (the last one shorter: plan_hpke.h's
+// team_split_plan), each segment's sum P_s = sum_b X_b H^(end_s - b) carried to its own end
+// (gcm_team_stripe_range's XOR over the lanes, y0 inside P_0) at parts[pitch s ..]: y = the GHASH
+// so far of the whole text, by Horner over the segments,
+//   y = (..((P_0 H^L ^ P_1) H^L ^ P_2)..) H^(nb - (S - 1) L) ^ P_(S-1),
+// two exponentiations and S - 1 products.  L and nb are below 2^32 (gcm_team_stripe_range).
+DEVI void gcm_split_join(const uint32_t h[4], const uint32_t* parts, uint32_t pitch, uint32_t S,
+                         uint64_t L, uint64_t nb, uint32_t y[4]) {
+  uint32_t hl[4], hlast[4];
+  gf128_pow(h, (uint32_t)L, hl);
+  gf128_pow(h, (uint32_t)(nb - (uint64_t)(S - 1) * L), hlast);
+#pragma unroll
+  for (int i = 0; i < 4; ++i) y[i] = parts[i];
+  for (uint32_t s = 1; s < S; ++s) {
+    uint32_t pw[4];
+#pragma unroll
+    for (int i = 0; i < 4; ++i) pw[i] = s + 1 == S ? hlast[i] : hl[i];
+    gf128_mul(y, pw, y);
+#pragma unroll
+    for (int i = 0; i < 4; ++i) y[i] ^= parts[(size_t)pitch * s + i];
+  }
+}
+
+// An AAD that only the first segment of a split text absorbs: the source itself there, an empty
+// one (y0 = 0, which no later segment's blocks take) elsewhere.  len() is the absorbed length; the
+// tag's length block takes the source's own.
+template <class Aad>
+struct FirstSegmentAad {
+  const Aad& aad;
+  bool first;
+  DEVI uint64_t len() const { return first ? aad.len() : 0; }
+  DEVI void block(uint64_t o, uint32_t d[4]) const { aad.block(o, d); }
+};
 
 // Zeros over what the lane's stripe wrote (sink.store with the stripe's own block-to-lane map, so
 // a lane overwrites its own stores).

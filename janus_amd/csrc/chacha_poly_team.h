@@ -11,6 +11,9 @@
 //   chacha_team_start                 the one-time key from block 0, then poly_team_start
 //   chacha_team_stripe<SEAL>          one lane's chunks: load, [absorb,] XOR, store[, absorb]
 //   poly_team_tag                     the tag from the joined sum, on every lane alike
+//   poly_team_start_range, chacha_team_stripe_range, poly1305_pow64, poly_split_join
+//                                     the same over a sub-range of the chunks, and the sum of a
+//                                     body from its segments' sums (several waves per report)
 //   chacha_team_wipe                  zeros over what the lane's stripe stored
 // The MAC across lanes.  With h_a the state after the padded AAD, c_0 .. c_(nb-1) the zero-padded
 // ciphertext blocks (each with the 2^128 bit: the AEAD pads to 16) and L the length block, the
@@ -105,6 +108,24 @@ DEVI void poly1305_pow(const uint32_t r[5], uint32_t e, uint32_t out[5]) {
   for (int i = 0; i < 5; ++i) out[i] = acc[i];
 }
 
+// out = r^e mod 2^130 - 5 for any public 64-bit e: poly1305_pow's square-and-multiply from bit 63
+// down, 128 products whatever e is.  For the segments' join (poly_split_join), whose exponents are
+// block counts.
+DEVI void poly1305_pow64(const uint32_t r[5], uint64_t e, uint32_t out[5]) {
+  uint32_t acc[5] = {1u, 0u, 0u, 0u, 0u};
+#pragma unroll 1
+  for (int bit = 63; bit >= 0; --bit) {
+    uint32_t t[5];
+    poly1305_mul(acc, acc, acc);
+    poly1305_mul(acc, r, t);
+    const uint32_t m = 0u - (uint32_t)((e >> bit) & 1u);
+#pragma unroll
+    for (int i = 0; i < 5; ++i) acc[i] = (acc[i] & ~m) | (t[i] & m);
+  }
+#pragma unroll
+  for (int i = 0; i < 5; ++i) out[i] = acc[i];
+}
+
 // A lane's share of the MAC: mac.r and mac.s the one-time key, mac.h the lane's running sum, rs =
 // r^(4 team - 3) (from a chunk's last block to the lane's next chunk) and rd = r^d, d = nb - b
 // for the last block b of the lane's last chunk where that chunk is whole.
@@ -113,33 +134,46 @@ struct PolyTeam {
   uint32_t rs[5], rd[5];
 };
 
-// The lane's state before its stripe of a body of `len` bytes, from the one-time key otk (r || s,
-// 8 little-endian words; r is clamped here) and the AAD: every lane absorbs the padded AAD, lane 0
-// keeps that state as its sum and the others start from zero.  team <= 64 (the exponents fit
-// poly1305_pow); rs is computed only where some lane has a second chunk, and a lane without a
-// whole last chunk gets rd = r (never used).  Both choices depend on len, lane and team only.
+// The lane's state before its stripe of the chunks [c0, c1) of a body, whose blocks end at block
+// b1 (c1 = ceil(b1 / 4); the whole body: c0 = 0 and b1 = nb), from the one-time key otk (r || s, 8
+// little-endian words; r is clamped here) and the AAD.  With `first` (the range starts the body)
+// every lane absorbs the padded AAD and lane 0 keeps that state as its sum; every other sum starts
+// from zero, and a later range does not read the AAD.  The powers carry to b1, so the lanes' sums
+// add up to [h_a r^b1 +] sum_b c_b r^(b1 - b) over the range's blocks.  team <= 64 (the exponents
+// fit poly1305_pow); rs is computed only where some lane has a second chunk, and a lane without a
+// whole last chunk gets rd = r (never used).  Both choices depend on lengths, lane and team only.
+template <class Aad>
+DEVI void poly_team_start_range(PolyTeam& t, const uint32_t otk[8], const Aad& aad, bool first,
+                                uint64_t c0, uint64_t c1, uint64_t b1, uint32_t lane,
+                                uint32_t team) {
+  poly1305_init(t.mac, otk);
+  if (first) {
+    const uint64_t alen = aad.len();
+    for (uint64_t o = 0; o < alen; o += 16) {
+      uint32_t d[4];
+      aad.block(o, d);
+      poly1305_block(t.mac, d, 1u << 24);
+    }
+  }
+#pragma unroll
+  for (int i = 0; i < 5; ++i) t.mac.h[i] = first && lane == 0 ? t.mac.h[i] : 0u;
+#pragma unroll
+  for (int i = 0; i < 5; ++i) t.rs[i] = t.mac.r[i];
+  if (c1 - c0 > team) poly1305_pow(t.mac.r, 4u * team - 3u, t.rs);
+  uint32_t d = 1;
+  if (c0 + lane < c1) {
+    const uint64_t k0 = c0 + lane;
+    const uint64_t last = k0 + team * ((c1 - 1 - k0) / team);    // the lane's last chunk
+    if (4 * last + 3 < b1) d = (uint32_t)(b1 - (4 * last + 3));  // <= 4 team - 3
+  }
+  poly1305_pow(t.mac.r, d, t.rd);
+}
+
+// The whole body of `len` bytes: poly_team_start_range over every chunk.
 template <class Aad>
 DEVI void poly_team_start(PolyTeam& t, const uint32_t otk[8], const Aad& aad, uint64_t len,
                           uint32_t lane, uint32_t team) {
-  poly1305_init(t.mac, otk);
-  const uint64_t alen = aad.len();
-  for (uint64_t o = 0; o < alen; o += 16) {
-    uint32_t d[4];
-    aad.block(o, d);
-    poly1305_block(t.mac, d, 1u << 24);
-  }
-#pragma unroll
-  for (int i = 0; i < 5; ++i) t.mac.h[i] = lane == 0 ? t.mac.h[i] : 0u;
-  const uint64_t nb = (len + 15) / 16, nch = (len + 63) / 64;
-#pragma unroll
-  for (int i = 0; i < 5; ++i) t.rs[i] = t.mac.r[i];
-  if (nch > team) poly1305_pow(t.mac.r, 4u * team - 3u, t.rs);
-  uint32_t d = 1;
-  if (lane < nch) {
-    const uint64_t last = lane + team * ((nch - 1 - lane) / team);  // the lane's last chunk
-    if (4 * last + 3 < nb) d = (uint32_t)(nb - (4 * last + 3));     // <= 4 team - 3
-  }
-  poly1305_pow(t.mac.r, d, t.rd);
+  poly_team_start_range(t, otk, aad, true, 0, (len + 63) / 64, (len + 15) / 16, lane, team);
 }
 
 // h += the sixteen bytes m as a number, with the 2^128 bit
@@ -190,18 +224,22 @@ DEVI void chacha_team_start(PolyTeam& t, const uint32_t key[8], const uint32_t n
   poly_team_start(t, ks, aad, len, lane, team);
 }
 
-// One lane's stripe of a body, a byte source (len(), block(o, d), whole(o, d) where it has one):
-// chunks lane, lane + team, ... of 64 bytes.  A chunk's (up to) four blocks are loaded, the
+// One lane's stripe of the chunks [c0, c1) of a body, a byte source (len(), block(o, d),
+// whole(o, d) where it has one): chunks c0 + lane, c0 + lane + team, ... of 64 bytes, c1 at most
+// the body's chunk count.  Chunk and block indices are the body's own, so the counter, the offsets
+// and the padding are those of the whole body.  A chunk's (up to) four blocks are loaded, the
 // keystream block with counter chunk + 1 is computed, and block b = 4 chunk + q is
 //   open (SEAL false): absorbed as it came, XORed, and handed to sink.put(b, words, bytes);
 //   seal:              XORed, zeroed past the end of a partial last block, handed to sink.put and
 //                      then absorbed.
-// t is the lane's poly_team_start state; afterwards t.mac.h is the lane's sum.
+// t is the lane's poly_team_start_range state for the same range; afterwards t.mac.h is the
+// lane's sum.  (The counter is 32 bits wide, as RFC 8439's: 2^32 chunks are 256 GiB.)
 template <bool SEAL, class Src, class Sink>
-DEVI void chacha_team_stripe(PolyTeam& t, const uint32_t key[8], const uint32_t nonce[3],
-                             const Src& src, uint32_t lane, uint32_t team, Sink& sink) {
-  const uint64_t len = src.len(), nch = (len + 63) / 64;
-  for (uint64_t k = lane; k < nch; k += team) {
+DEVI void chacha_team_stripe_range(PolyTeam& t, const uint32_t key[8], const uint32_t nonce[3],
+                                   const Src& src, uint64_t c0, uint64_t c1, uint32_t lane,
+                                   uint32_t team, Sink& sink) {
+  const uint64_t len = src.len();
+  for (uint64_t k = c0 + lane; k < c1; k += team) {
     uint32_t d[4][4], ks[16];
 #pragma unroll
     for (int q = 0; q < 4; ++q) {
@@ -216,7 +254,7 @@ DEVI void chacha_team_stripe(PolyTeam& t, const uint32_t key[8], const uint32_t 
       }
     }
     chacha20_block(key, (uint32_t)k + 1u, nonce, ks);
-    const bool more = k + team < nch;
+    const bool more = k + team < c1;
 #pragma unroll
     for (int q = 0; q < 4; ++q) {
       const uint64_t o = 64 * k + 16 * q;
@@ -230,6 +268,40 @@ DEVI void chacha_team_stripe(PolyTeam& t, const uint32_t key[8], const uint32_t 
         if constexpr (SEAL) poly_team_absorb(t, d[q], q, more);
       }
     }
+  }
+}
+
+// The whole body: chacha_team_stripe_range over every chunk, after poly_team_start.
+template <bool SEAL, class Src, class Sink>
+DEVI void chacha_team_stripe(PolyTeam& t, const uint32_t key[8], const uint32_t nonce[3],
+                             const Src& src, uint32_t lane, uint32_t team, Sink& sink) {
+  chacha_team_stripe_range<SEAL>(t, key, nonce, src, 0, (src.len() + 63) / 64, lane, team, sink);
+}
+
+// A body of nb blocks cut into S >= 2 segments of L blocks (L a multiple of 4 team; the last one
+// shorter: plan_hpke.h's team_split_plan), each segment's sum P_s = [h_a r^L +] sum_b c_b
+// r^(end_s - b) carried to its own end (the lanes' sums added and carried, limbs below
+// 2^26 + 2^9) at parts[pitch s ..]: sum = h_a r^nb + sum_b c_b r^(nb - b), what poly_team_tag
+// takes, by Horner over the segments,
+//   sum = (..((P_0 r^L + P_1) r^L + P_2)..) r^(nb - (S - 1) L) + P_(S-1),
+// two exponentiations and S - 1 products.  A product's limbs (below 2^26 + 2^10) plus a sum's
+// stay within poly1305_carry's 32 bits; carried, they are within poly1305_mul's bound again and,
+// at the end, within poly_team_tag's.
+DEVI void poly_split_join(const uint32_t r[5], const uint32_t* parts, uint32_t pitch, uint32_t S,
+                          uint64_t L, uint64_t nb, uint32_t sum[5]) {
+  uint32_t rl[5], rlast[5];
+  poly1305_pow64(r, L, rl);
+  poly1305_pow64(r, nb - (uint64_t)(S - 1) * L, rlast);
+#pragma unroll
+  for (int i = 0; i < 5; ++i) sum[i] = parts[i];
+  for (uint32_t s = 1; s < S; ++s) {
+    uint32_t pw[5];
+#pragma unroll
+    for (int i = 0; i < 5; ++i) pw[i] = s + 1 == S ? rlast[i] : rl[i];
+    poly1305_mul(sum, pw, sum);
+#pragma unroll
+    for (int i = 0; i < 5; ++i) sum[i] += parts[(size_t)pitch * s + i];
+    poly1305_carry(sum);
   }
 }
 

@@ -69,7 +69,8 @@ const char* const kKernelNames[KID_COUNT] = {
     // not a kernel: the request's one host-to-device copy in prio3gpu_helper_init_request
     "copy_request", "k_p256_dh", "k_p256_dh_idx", "k_x25519_eph", "k_hpke_seal",
     "k_hpke_seal_shares", "k_hpke_open_team", "k_hpke_open_team_shares", "k_hpke_seal_team",
-    "k_hpke_seal_team_shares", "k_p256_eph", "k_p256_eph_kem"};
+    "k_hpke_seal_team_shares", "k_p256_eph", "k_p256_eph_kem", "k_hpke_open_team_split",
+    "k_hpke_open_team_join", "k_hpke_team_wipe", "k_hpke_seal_team_split", "k_hpke_seal_team_join"};
 
 }  // namespace
 
@@ -1451,6 +1452,19 @@ int prio3gpu_ctx_set_option(prio3gpu_ctx* c, const char* name, int64_t value) {
       return PRIO3GPU_E_ARG;
     }
     c->hpke_team_chacha = on;
+  } else if (k == "hpke_team_split") {
+    if (value < 0 || value > 256) {
+      set_err("option hpke_team_split: %lld is outside [0, 256]", (long long)value);
+      return PRIO3GPU_E_ARG;
+    }
+    c->hpke_team_split = (uint32_t)value;
+  } else if (k == "hpke_team_split_blocks") {
+    if (value < 256 || value > (1 << 24) || value % 256 != 0) {
+      set_err("option hpke_team_split_blocks: %lld is no multiple of 256 in [256, 2^24]",
+              (long long)value);
+      return PRIO3GPU_E_ARG;
+    }
+    c->hpke_team_split_blocks = (uint32_t)value;
   } else if (k == "expand_lds" || k == "jr_lds") {
     if (value < 0 || value > 160 * 1024) {
       set_err("option %s: %lld bytes is outside [0, 163840]", name, (long long)value);

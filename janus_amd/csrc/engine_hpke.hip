@@ -3,7 +3,9 @@
 // batch (a wave per report) share hpke_open_batch_entry; prio3gpu_open_input_shares opens share
 // rows in place; prio3gpu_hpke_open_report_shares_gpu packs a request's key groups for the first.
 // The seals: prio3gpu_hpke_seal_batch / _long_batch share hpke_seal_batch_entry, prio3gpu_seal_
-// input_shares / _long share seal_input_shares_entry.  prio3gpu_helper_init_request is the
+// input_shares / _long share seal_input_shares_entry.  With the "hpke_team_split" option the two
+// share-row calls may give a report several waves: share_split decides, and the kernels and their
+// launches are engine_hpke_split.hip's (hpke_split_launch.h).  prio3gpu_helper_init_request is the
 // helper's aggregate-init from the request's bytes, in steps req_plan ... req_host_fallback.
 // Every call refuses in one order: null context, suite, keys, n == 0, null arguments, pitches.
 // The context's scratch is named in engine_internal.h; a call's per-report secrets in it belong
@@ -30,6 +32,7 @@
 #include "hpke_seal_gpu.h"
 #include "hpke_open_team.h"
 #include "hpke_seal_team.h"
+#include "hpke_split_launch.h"
 
 using namespace p3g;
 using namespace p3g::eng;
@@ -74,6 +77,9 @@ struct CallSecrets {
     void* p;
     size_t bytes;
   };
+  // the most a call adds: four device spans (the split seal from host memory: the staged share
+  // rows, the ladders' output, the staged ephemeral keys, the segments' sums) and three host
+  // vectors (the request path); a call that needs more widens these
   Span dev[4];
   std::vector<uint8_t>* host[3];
   int n_dev = 0, n_host = 0;
@@ -895,6 +901,33 @@ int packed_rows_to_host(prio3gpu_ctx* c, uint8_t* dst, size_t pitch, const uint8
   return 0;
 }
 
+// How a share-row call cuts its reports ("hpke_team_split", "hpke_team_split_blocks"): S = 1 means
+// the one-wave kernels and nothing else.  Every report of the call has the same body.  A batch
+// beyond the wipe kernel's grid (one y per report) could not split anyway: it fills the chip.
+TeamSplit share_split(const prio3gpu_ctx* c, size_t n, uint32_t input_share_len,
+                      uint16_t aead_id) {
+  const uint64_t body = 6 + (uint64_t)input_share_len;
+  if (c->hpke_team_split < 2 || n > 65535) return {1, (body + 15) / 16};
+  return team_split_plan(n, body, aead_id == 3 ? 4 * kTeam : kTeam, c->hpke_team_split,
+                         c->hpke_team_split_blocks,
+                         (uint64_t)c->cus * 4 * split_waves_per_simd(aead_id));
+}
+
+// What a split call's kernels share (hpke_split_launch.h), with the call's scratch: the
+// segments' sums and the header flags, the call's secret from here on.
+int split_call(prio3gpu_ctx* c, CallSecrets& sec, const TeamSplit& sp, size_t n,
+               const HpkeBatchConsts& bc, const ReqTaskId& tid, const uint8_t* d_rid,
+               const uint8_t* d_time, const uint8_t* d_pub, uint32_t public_share_len,
+               uint32_t input_share_len, uint8_t* d_st, SplitShareCall* q) {
+  const size_t bytes = split_scratch_bytes(n, sp.S);
+  CHK(c->hpke.split.ensure(bytes));
+  sec.add(c->hpke.split.p, bytes);
+  *q = SplitShareCall{(uint32_t)n, sp.S, sp.L, bc, tid, d_rid,
+                      reinterpret_cast<const uint64_t*>(d_time), d_pub, public_share_len,
+                      input_share_len, c->hpke.split.u8(), d_st};
+  return 0;
+}
+
 // prio3gpu_seal_input_shares and, with `team`, prio3gpu_seal_input_shares_long.
 int seal_input_shares_entry(prio3gpu_ctx* c, const uint8_t* task_id, uint16_t kem_id,
                             uint16_t kdf_id, uint16_t aead_id, const uint8_t* pk, size_t pk_len,
@@ -969,7 +1002,15 @@ int seal_input_shares_entry(prio3gpu_ctx* c, const uint8_t* task_id, uint16_t ke
                          (uint64_t)(enc_host ? nenc : epitch), d_pay,
                          (uint64_t)(pay_host ? plen : ppitch), d_st);
     };
-    if (team) {
+    const TeamSplit sp = team ? share_split(c, n, input_share_len, aead_id)
+                              : TeamSplit{1, 0};
+    if (sp.S >= 2) {  // several waves per report: the segments, then the tags and encs
+      SplitShareCall q;
+      CHK(split_call(c, sec, sp, n, bc, tid, d_rid, d_time, d_pub, public_share_len,
+                     input_share_len, d_st, &q));
+      CHK(launch_seal_team_split(c, q, d_eph, d_sh, spitch, d_enc, enc_host ? nenc : epitch,
+                                 d_pay, pay_host ? plen : ppitch));
+    } else if (team) {
       PROF(KID_HPKE_SEAL_TEAM_SHARES);
       hpke_suite_dispatch(bc, [&](auto kdf, auto aead) {
         launch(k_hpke_seal_team_shares<decltype(kdf)::value, decltype(aead)::value>,
@@ -1146,6 +1187,16 @@ int prio3gpu_open_input_shares(prio3gpu_ctx* c, const uint8_t* task_id, uint16_t
   int rc = [&]() -> int {
     uint32_t* d_dh;
     CHK(open_dh(c, sec, kem_id, sk, pk, bc, /*raw=*/false, n, d_enc_packed, &d_dh));
+    const TeamSplit sp = share_split(c, n, input_share_len, aead_id);
+    if (sp.S >= 2) {
+      // several waves per report: the segments, the verdicts, and zeros over every failed row,
+      // queued back to back -- nothing later on the stream sees unauthenticated plaintext
+      SplitShareCall q;
+      CHK(split_call(c, sec, sp, n, bc, tid, d_rid, d_time, d_pub, public_share_len,
+                     input_share_len, d_st, &q));
+      return launch_open_team_split(c, q, d_dh, d_enc, epitch, d_pay, ppitch, d_out,
+                                    out_host ? input_share_len : spitch);
+    }
     {
       PROF(KID_HPKE_OPEN_TEAM_SHARES);
       hpke_suite_dispatch(bc, [&](auto kdf, auto aead) {

@@ -88,7 +88,9 @@ enum KernelId {
   KID_FPV_REGEN, KID_X25519, KID_HPKE_OPEN, KID_REQ_GATHER, KID_X25519_IDX, KID_HPKE_OPEN_REQ,
   KID_DECODE_PT, KID_REQ_SCATTER, KID_REQ_COPY, KID_P256_DH, KID_P256_DH_IDX, KID_X25519_EPH,
   KID_HPKE_SEAL, KID_HPKE_SEAL_SHARES, KID_HPKE_OPEN_TEAM, KID_HPKE_OPEN_TEAM_SHARES,
-  KID_HPKE_SEAL_TEAM, KID_HPKE_SEAL_TEAM_SHARES, KID_P256_EPH, KID_P256_EPH_KEM, KID_COUNT
+  KID_HPKE_SEAL_TEAM, KID_HPKE_SEAL_TEAM_SHARES, KID_P256_EPH, KID_P256_EPH_KEM,
+  KID_HPKE_OPEN_TEAM_SPLIT, KID_HPKE_OPEN_TEAM_JOIN, KID_HPKE_TEAM_WIPE, KID_HPKE_SEAL_TEAM_SPLIT,
+  KID_HPKE_SEAL_TEAM_JOIN, KID_COUNT
 };
 
 // Per-kernel HIP-event timing on the context's stream (opt-in; used by bench.py).
@@ -120,8 +122,10 @@ struct Prof {
 // per report, for P-256 the shared secrets, then P-256's validity bytes).  The seals stage their
 // AADs, AAD offsets, ciphertext offsets and statuses in aad, aad_off, ct_off and status;
 // prio3gpu_open_input_shares has its payload rows in ct_in and its opened share rows in pt_out.
+// split: the segments' sums and the header flags of a call that gives a report several waves
+// (hpke_team_split.h), opens and seals alike.
 struct HpkeOpenScratch {
-  DevBuf enc_in, aad, aad_off, ct_in, ct_off, pt_out, pt_off, status, dh;
+  DevBuf enc_in, aad, aad_off, ct_in, ct_off, pt_out, pt_off, status, dh, split;
 };
 
 // The seals: staging of host inputs (ephemeral keys, plaintexts or share rows, plaintext
@@ -200,6 +204,12 @@ struct prio3gpu_ctx {
   // "hpke_team_chacha": 1 lets the wave-per-report opens and seals (hpke_team_suite) take
   // ChaCha20-Poly1305 (AEAD 3) beside AES-GCM; 0 leaves it PRIO3GPU_E_UNSUPPORTED there
   bool hpke_team_chacha = false;
+  // "hpke_team_split": at most this many waves per report in prio3gpu_open_input_shares and
+  // prio3gpu_seal_input_shares_long (hpke_team_split.h; 0 and 1: one wave, the one-wave kernels);
+  // "hpke_team_split_blocks": the smallest segment a wave is given, in 16-byte blocks (256 KiB:
+  // the smallest measured size at which two segments beat one wave)
+  uint32_t hpke_team_split = 0;
+  uint32_t hpke_team_split_blocks = 16384;
   size_t expand_lds = 0;     // "expand_lds": dynamic LDS per k_expand block (occupancy cap)
   size_t jr_lds = 0;         // "jr_lds": dynamic LDS per k_jr block (occupancy cap)
   uint32_t cus = 0;          // compute units of the device

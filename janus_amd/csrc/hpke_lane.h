@@ -140,6 +140,17 @@ DEVI void hpke_seal_lane(const uint8_t* sbox, const HpkeBatchConsts& bc, const u
   for (uint64_t j = plen + 16; j < ct_cap; ++j) ct[j] = 0;
 }
 
+// Where report r's enc and DH words lie in the seal ladders' output (hpke_seal_gpu.h):
+// k_x25519_eph's n encs of 8 words, then n DH values; under P-256 (bc.dh_ok) n points of 16 words,
+// then n shared secrets.
+DEVI const uint32_t* eph_enc(const HpkeBatchConsts& bc, const uint32_t* eph, uint32_t r) {
+  return eph + (size_t)r * (bc.dh_ok ? 16 : 8);
+}
+DEVI const uint32_t* eph_dh(const HpkeBatchConsts& bc, const uint32_t* eph, uint32_t n,
+                            uint32_t r) {
+  return eph + (size_t)n * (bc.dh_ok ? 16 : 8) + (size_t)r * 8;
+}
+
 struct ReqTaskId {  // the 32-byte TaskId as block words (byte j at bits 8 (j & 3) of word j >> 2)
   uint32_t w[8];
 };

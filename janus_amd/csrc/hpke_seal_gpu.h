@@ -110,16 +110,6 @@ __global__ void __launch_bounds__(256) k_p256_eph_kem(uint32_t n, P256DhConsts d
   for (int i = 0; i < 8; ++i) d[i] = bswap32(ss[i]);
 }
 
-// Where report r's enc and DH words lie in the ladders' output: k_x25519_eph's n encs of 8 words,
-// then n DH values; under P-256 (bc.dh_ok) n points of 16 words, then n shared secrets.
-DEVI const uint32_t* eph_enc(const HpkeBatchConsts& bc, const uint32_t* eph, uint32_t r) {
-  return eph + (size_t)r * (bc.dh_ok ? 16 : 8);
-}
-DEVI const uint32_t* eph_dh(const HpkeBatchConsts& bc, const uint32_t* eph, uint32_t n,
-                            uint32_t r) {
-  return eph + (size_t)n * (bc.dh_ok ? 16 : 8) + (size_t)r * 8;
-}
-
 // One lane per report: hpke_seal_lane over packed plaintexts and AADs; report r's ciphertext ||
 // tag goes to cts[ct_off[r] .. ct_off[r + 1]) and its enc to encs[bc.nenc r ..].  A slot shorter than
 // the plaintext + 16 or offsets that do not fit: zeros and status 4.  A report whose status is

@@ -105,6 +105,31 @@ inline uint64_t rows_span(uint64_t n, uint64_t pitch, uint64_t width) {
   return (n - 1) * pitch + width;
 }
 
+// Several waves per report ("hpke_team_split"): a body of body_bytes (nb 16-byte blocks) is cut
+// into S segments of L blocks, segment s covering blocks [s L, min((s + 1) L, nb)), each run by a
+// wave of its own (hpke_team_split.h).  n reports in the call; `unit` one team stripe in blocks
+// (64 for AES-GCM, 256 for ChaCha20-Poly1305: L is a multiple, so a segment starts on a stripe);
+// cap the option's value; min_blocks "hpke_team_split_blocks", the smallest segment worth a wave;
+// wave_slots the waves the chip holds at once.  S = 1 (L = nb) means no split: the one-wave
+// kernels run.  A call that fills the chip by itself (n >= wave_slots) never splits.
+struct TeamSplit {
+  uint32_t S;
+  uint64_t L;
+};
+inline TeamSplit team_split_plan(uint64_t n, uint64_t body_bytes, uint32_t unit, uint32_t cap,
+                                 uint64_t min_blocks, uint64_t wave_slots) {
+  const uint64_t nb = (body_bytes + 15) / 16;
+  if (n == 0 || unit == 0 || min_blocks == 0) return {1, nb};
+  const uint64_t want = (wave_slots + n - 1) / n;
+  const uint64_t s0 = std::min<uint64_t>(std::min<uint64_t>(cap, want), nb / min_blocks);
+  if (s0 < 2) return {1, nb};
+  const uint64_t per = (nb + s0 - 1) / s0;
+  const uint64_t L = (per + unit - 1) / unit * unit;
+  const uint64_t S = (nb + L - 1) / L;
+  if (S < 2) return {1, nb};
+  return {(uint32_t)S, L};
+}
+
 // P-256 order n, big-endian
 constexpr uint8_t kP256Order[32] = {0xff, 0xff, 0xff, 0xff, 0x00, 0x00, 0x00, 0x00, 0xff, 0xff, 0xff,
                                     0xff, 0xff, 0xff, 0xff, 0xff, 0xbc, 0xe6, 0xfa, 0xad, 0xa7, 0x17,

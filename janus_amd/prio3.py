@@ -316,7 +316,7 @@ class Prio3Gpu:
         """Engine option of this context (prio3gpu_ctx_set_option: "speculate", "wires_mfma",
         "wires_cols", "fused_helper", "helper_snap", "snap_chunk", "jr_ring", "spread",
         "expand_lds", "jr_lds", "exact_squeeze", "hpke_gpu_suites", "hpke_gpu_p256",
-        "hpke_team_chacha")."""
+        "hpke_team_chacha", "hpke_team_split", "hpke_team_split_blocks")."""
         check(lib().prio3gpu_ctx_set_option(self._ctx, name.encode(), int(value)),
               f"ctx_set_option({name})")
 

@@ -47,11 +47,18 @@ class UploadBatch:
     encapsulated keys at the length of its first key's KEM (65 bytes for P-256) and the other
     aggregator's at `peer_enc` bytes (32, or 65 when that one's key is P-256) -- the layout
     `ClientBatch(p256=True)` writes.  Without it the layout and the routing are unchanged: a
-    P-256 key group is opened on the host."""
+    P-256 key group is opened on the host.  `team_split` and `team_split_blocks` set the options
+    "hpke_team_split" and "hpke_team_split_blocks": a small batch of very long shares is opened
+    with up to `team_split` waves per report, none with fewer than `team_split_blocks` 16-byte
+    blocks.  Like `team_chacha`, either is set only when given: 0 (the default) and None leave the
+    context as it is -- one wave per report on a context nobody switched, still split on a `vdaf`
+    an earlier batch switched on (`vdaf.set_option("hpke_team_split", 0)` turns it off).  The
+    opened rows and statuses never depend on either."""
 
     def __init__(self, vdaf, task_id: bytes, task_keys: Sequence[H.HpkeKeypair],
                  global_keys: Sequence[H.HpkeKeypair] = (), role: int = H.ROLE_LEADER,
-                 team_chacha: bool = False, p256: bool = False, peer_enc: int = ENC_LEN):
+                 team_chacha: bool = False, p256: bool = False, peer_enc: int = ENC_LEN,
+                 team_split: int = 0, team_split_blocks: Optional[int] = None):
         if len(task_id) != 32:
             raise ValueError("TaskId is 32 bytes")
         if role not in (H.ROLE_LEADER, H.ROLE_HELPER):
@@ -62,6 +69,10 @@ class UploadBatch:
         self.p256 = bool(p256)
         if self.p256:
             vdaf.set_option("hpke_gpu_p256", 1)
+        if team_split_blocks is not None:
+            vdaf.set_option("hpke_team_split_blocks", team_split_blocks)
+        if team_split:
+            vdaf.set_option("hpke_team_split", team_split)
         self.vdaf, self.task_id, self.role = vdaf, bytes(task_id), role
         self.task_keys, self.global_keys = {}, {}
         for table, kps in ((self.task_keys, task_keys), (self.global_keys, global_keys)):

@@ -45,7 +45,9 @@ fn main() {
         .arg("-o")
         .arg(out.join("libprio3gpu.so"))
         .args(
-            ["engine.hip", "engine_hpke.hip", "codec.cpp", "hpke.cpp"].iter().map(|f| csrc.join(f)),
+            ["engine.hip", "engine_hpke.hip", "engine_hpke_split.hip", "codec.cpp", "hpke.cpp"]
+                .iter()
+                .map(|f| csrc.join(f)),
         )
         .args(["-lrccl", "-lcrypto"])
         .status()
