@@ -245,6 +245,26 @@ int prio3gpu_state_destroy(prio3gpu_state* st);
  * (pitch 135,040) gives k_jr's LDS-DMA windows and the FLP wire pass line-aligned rows
  * (aggregator_core/src/datastore.rs:1298-1304 decodes each LeaderStoredReport's share). */
 int prio3gpu_state_set_input_pitch(prio3gpu_state* st, size_t pitch);
+/* Reports of several tasks in one batch: report r of the next calls on `st` is prepared under
+ * verify_keys[key_index[r]] instead of the context's key.  Of all Prio3 preparation only the query
+ * randomness t = XOF(verify_key, dst5, nonce) reads the key, so the tasks need nothing else in
+ * common than the context's VDAF shape (kind, bits, length, chunk length, XOF).
+ * `verify_keys` and `key_index` are host or device memory; both are copied into buffers the state
+ * owns, and the caller's memory is free again on return.  Those buffers are allocated by the first
+ * keyed use (the index for the state's capacity; the table grows with num_keys): one more exception
+ * to the no-allocation guarantee of prio3gpu_state_create, a failure being PRIO3GPU_E_CAPACITY.
+ * Checked before anything is launched or changed: num_keys >= 1, n <= the state's capacity, and
+ * every key_index[r] < num_keys (a device index through a host copy).  A violation is
+ * PRIO3GPU_E_ARG, prio3gpu_last_error naming the first bad row, and the state's previous setting
+ * stays in place.  num_keys == 0 clears the setting (verify_keys and key_index may be NULL, n is
+ * ignored); a state with no keys set behaves, and launches, exactly as before this call existed.
+ * The setting persists until it is replaced or cleared.  While it is set, prio3gpu_prepare_init,
+ * prio3gpu_prepare_init_xof and prio3gpu_helper_init take exactly the `n` of this call (anything
+ * else is PRIO3GPU_E_ARG with nothing launched), and prio3gpu_helper_init_request (one task id,
+ * one request) and prio3gpu_shard return PRIO3GPU_E_ARG.  The call waits for the context's
+ * stream. */
+int prio3gpu_state_set_verify_keys(prio3gpu_state* st, const uint8_t* verify_keys /* num_keys x 16 */,
+                                   uint32_t num_keys, const uint32_t* key_index /* n */, size_t n);
 
 /* Aggregate shares: `num_slots` batch identifiers (caller maps BatchIdentifier -> slot). */
 int prio3gpu_agg_create(prio3gpu_ctx* ctx, uint32_t num_slots, prio3gpu_agg** out);

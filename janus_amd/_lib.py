@@ -87,8 +87,8 @@ def build(force: bool = False, verbose: bool = False) -> Path:
     compile_flags = [f for f in FLAGS if f != "-shared"] + [f'-DPRIO3GPU_BUILD_HASH="{want}"']
 
     def run(cmd):
-        if verbose:
-            print(" ".join(cmd))
+        if verbose:  # flushed: a build that is cut short still shows the step it was in
+            print(" ".join(cmd), flush=True)
         subprocess.run(cmd, check=True)
 
     def compile_one(src, obj):
@@ -130,6 +130,7 @@ def _declare(lib):
         "prio3gpu_state_create": (c.c_int, [P, c.c_int, c.c_size_t, c.POINTER(P)]),
         "prio3gpu_state_destroy": (c.c_int, [P]),
         "prio3gpu_state_set_input_pitch": (c.c_int, [P, c.c_size_t]),
+        "prio3gpu_state_set_verify_keys": (c.c_int, [P, u8p, c.c_uint32, P, c.c_size_t]),
         "prio3gpu_agg_create": (c.c_int, [P, c.c_uint32, c.POINTER(P)]),
         "prio3gpu_agg_destroy": (c.c_int, [P]),
         "prio3gpu_agg_reset": (c.c_int, [P]),
@@ -255,7 +256,7 @@ EXPORTED = [
     "prio3gpu_ctx_wait_mark",
     "prio3gpu_prepare_init_xof", "prio3gpu_prepare_init_query", "prio3gpu_prepare_init_weights",
     "prio3gpu_ctx_stream", "prio3gpu_state_create", "prio3gpu_state_destroy",
-    "prio3gpu_state_set_input_pitch",
+    "prio3gpu_state_set_input_pitch", "prio3gpu_state_set_verify_keys",
     "prio3gpu_agg_create", "prio3gpu_agg_destroy", "prio3gpu_agg_reset", "prio3gpu_agg_read",
     "prio3gpu_agg_merge_bytes", "prio3gpu_agg_update_reports", "prio3gpu_agg_read_reports",
     "prio3gpu_prepare_init",

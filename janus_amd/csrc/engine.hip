@@ -70,7 +70,8 @@ const char* const kKernelNames[KID_COUNT] = {
     "copy_request", "k_p256_dh", "k_p256_dh_idx", "k_x25519_eph", "k_hpke_seal",
     "k_hpke_seal_shares", "k_hpke_open_team", "k_hpke_open_team_shares", "k_hpke_seal_team",
     "k_hpke_seal_team_shares", "k_p256_eph", "k_p256_eph_kem", "k_hpke_open_team_split",
-    "k_hpke_open_team_join", "k_hpke_team_wipe", "k_hpke_seal_team_split", "k_hpke_seal_team_join"};
+    "k_hpke_open_team_join", "k_hpke_team_wipe", "k_hpke_seal_team_split", "k_hpke_seal_team_join",
+    "k_query_rand_keyed"};
 
 }  // namespace
 
@@ -127,6 +128,14 @@ int check_state(prio3gpu_ctx* c, prio3gpu_state* st, size_t n) {
   if (n > st->cap) {
     set_err("batch of %zu reports exceeds state capacity %zu", n, st->cap);
     return PRIO3GPU_E_CAPACITY;
+  }
+  return 0;
+}
+
+int check_keyed_n(const prio3gpu_state* st, size_t n) {
+  if (st->vk_num != 0 && n != st->vk_n) {
+    set_err("batch of %zu reports on a state whose verify-key index covers %zu", n, st->vk_n);
+    return PRIO3GPU_E_ARG;
   }
   return 0;
 }
@@ -351,6 +360,14 @@ int launch_prep_xof(prio3gpu_ctx* c, prio3gpu_state* st, size_t n, const uint8_t
   CRows pub{d_pub, g.public_share_len};
   Rows t_rows{st->t.u8(), (size_t)16 * g.qr_len};
   st->query_done = false;
+  // several tasks in the batch (prio3gpu_state_set_verify_keys): t under each report's own key
+  const bool keyed = st->vk_num != 0;
+  auto query_rand_keyed = [&] {
+    PROF(KID_QUERY_KEYED);
+    hipLaunchKernelGGL(k_query_rand_keyed<FO>, grid1(n, TPB), dim3(TPB), 0, c->stream, g, N,
+                       st->vkeys.u8(), reinterpret_cast<const uint32_t*>(st->vkidx.p), nonces,
+                       t_rows, d_status);
+  };
   if (g.kind == KIND_COUNT) {
     // Count: one kernel derives t and runs the whole FLP query (k_flp_query_lane with the nonces):
     // the short Keccak and the latency-bound query share the launch, and the query phase is empty
@@ -367,19 +384,22 @@ int launch_prep_xof(prio3gpu_ctx* c, prio3gpu_state* st, size_t n, const uint8_t
       meas = CRows{mo.base, mo.stride};
       proof = CRows{po.base, po.stride};
     }
+    if (keyed) query_rand_keyed();  // the kernel below then reads t from st->t, as Sum's does
     {
       PROF(KID_FLP_QUERY_LANE);
       hipLaunchKernelGGL(k_flp_query_lane<FO>, grid1(n, 256), dim3(256), 0, c->stream, g, N, meas,
                          proof, CRows{st->t.u8(), 16}, CRows{st->jr.u8(), 16},
                          CRows{st->part.u8(), 16}, Rows{st->prep.u8(), g.prep_share_len}, d_status,
-                         d_nonces, vk_lo, vk_hi);
+                         keyed ? nullptr : d_nonces, vk_lo, vk_hi);
     }
     HIPCHK(hipGetLastError());
     xof_phase_done(st, n, meas, proof);
     st->query_done = true;
     return 0;
   }
-  {
+  if (keyed) {
+    query_rand_keyed();
+  } else {
     PROF(KID_QUERY);
     hipLaunchKernelGGL(k_query_rand<FO>, grid1(n, TPB), dim3(TPB), 0, c->stream, g, N, vk_lo, vk_hi,
                        nonces, t_rows, d_status);
@@ -1108,6 +1128,62 @@ int prio3gpu_state_set_input_pitch(prio3gpu_state* st, size_t pitch) {
   return 0;
 }
 
+int prio3gpu_state_set_verify_keys(prio3gpu_state* st, const uint8_t* verify_keys,
+                                   uint32_t num_keys, const uint32_t* key_index, size_t n) {
+  if (!st) {
+    set_err("null state");
+    return PRIO3GPU_E_ARG;
+  }
+  if (num_keys == 0) {  // back to the context's key; the buffers stay for the next keyed batch
+    st->vk_num = 0;
+    st->vk_n = 0;
+    return 0;
+  }
+  if (!verify_keys || (n && !key_index)) {
+    set_err("set_verify_keys: null argument");
+    return PRIO3GPU_E_ARG;
+  }
+  if (n > st->cap) {
+    set_err("set_verify_keys: key index of %zu reports exceeds state capacity %zu", n, st->cap);
+    return PRIO3GPU_E_ARG;
+  }
+  prio3gpu_ctx* c = st->ctx;
+  HIPCHK(hipSetDevice(c->device));
+  // every index is checked before anything is changed (a device index through a host copy)
+  std::vector<uint32_t> host;
+  const uint32_t* h_idx = key_index;
+  if (n && is_device_ptr(key_index)) {
+    host.resize(n);
+    HIPCHK(hipMemcpyAsync(host.data(), key_index, n * 4, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    h_idx = host.data();
+  }
+  for (size_t r = 0; r < n; ++r)
+    if (h_idx[r] >= num_keys) {
+      set_err("set_verify_keys: key_index[%zu] = %u is not below num_keys %u", r, h_idx[r],
+              num_keys);
+      return PRIO3GPU_E_ARG;
+    }
+  // A larger key table is allocated beside the old one, so a failure leaves the setting as it was.
+  auto capacity_rc = [](int rc) { return rc == PRIO3GPU_E_HIP ? PRIO3GPU_E_CAPACITY : rc; };
+  CHK(capacity_rc(st->vkidx.ensure(st->cap * 4)));
+  const size_t key_bytes = (size_t)num_keys * 16;
+  if (key_bytes > st->vkeys.cap) {
+    DevBuf grown;
+    CHK(capacity_rc(grown.ensure(key_bytes)));
+    HIPCHK(hipStreamSynchronize(c->stream));  // a queued batch may still read the old table
+    std::swap(grown.p, st->vkeys.p);
+    std::swap(grown.cap, st->vkeys.cap);
+  }
+  // queued after every earlier batch of the state on the context's stream, which reads the old rows
+  HIPCHK(hipMemcpyAsync(st->vkeys.p, verify_keys, key_bytes, hipMemcpyDefault, c->stream));
+  if (n) HIPCHK(hipMemcpyAsync(st->vkidx.p, key_index, n * 4, hipMemcpyDefault, c->stream));
+  HIPCHK(hipStreamSynchronize(c->stream));  // the caller's memory is free again
+  st->vk_num = num_keys;
+  st->vk_n = n;
+  return 0;
+}
+
 int prio3gpu_state_destroy(prio3gpu_state* st) {
   if (!st) return 0;
   if (st->ctx) (void)hipStreamSynchronize(st->ctx->stream);
@@ -1335,6 +1411,7 @@ int prio3gpu_prepare_init(prio3gpu_ctx* c, prio3gpu_state* st, size_t n, const u
                           const uint8_t* public_shares, const uint8_t* input_shares,
                           uint8_t* out_prep_shares, uint8_t* status) {
   CHK(check_state(c, st, n));
+  CHK(check_keyed_n(st, n));
   if (n == 0) return 0;
   PrepInputs d;
   CHK(stage_prepare_inputs(c, st, n, nonces, public_shares, input_shares, status, &d));
@@ -1350,6 +1427,7 @@ int prio3gpu_prepare_init_xof(prio3gpu_ctx* c, prio3gpu_state* st, size_t n, con
                               const uint8_t* public_shares, const uint8_t* input_shares,
                               uint8_t* status) {
   CHK(check_state(c, st, n));
+  CHK(check_keyed_n(st, n));
   if (n == 0) return 0;
   PrepInputs d;
   CHK(stage_prepare_inputs(c, st, n, nonces, public_shares, input_shares, status, &d));
@@ -1639,6 +1717,7 @@ int prio3gpu_helper_init(prio3gpu_ctx* c, prio3gpu_state* st, size_t n, const ui
                          const uint8_t* leader_prep_shares, const uint32_t* batch_slots,
                          uint8_t* out_prep_msgs, uint8_t* status, prio3gpu_agg* agg) {
   CHK(check_state(c, st, n));
+  CHK(check_keyed_n(st, n));
   if (st->agg_id != 1) {
     set_err("helper_init needs a helper (agg_id 1) state");
     return PRIO3GPU_E_ARG;
@@ -1765,6 +1844,10 @@ int prio3gpu_shard(prio3gpu_ctx* c, prio3gpu_state* st, size_t n, const uint8_t*
   CHK(check_state(c, st, n));
   if (st->agg_id != 1) {
     set_err("shard needs a helper-shaped (agg_id 1) state for scratch");
+    return PRIO3GPU_E_ARG;
+  }
+  if (st->vk_num != 0) {
+    set_err("shard on a state with verify keys set (prio3gpu_state_set_verify_keys)");
     return PRIO3GPU_E_ARG;
   }
   if (n == 0) return 0;

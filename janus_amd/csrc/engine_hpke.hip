@@ -1286,6 +1286,10 @@ int prio3gpu_helper_init_request(
     set_err("helper_init_request needs a helper (agg_id 1) state");
     return PRIO3GPU_E_ARG;
   }
+  if (st->vk_num != 0) {  // one task id, one request: the state's key table has no meaning here
+    set_err("helper_init_request on a state with verify keys set (prio3gpu_state_set_verify_keys)");
+    return PRIO3GPU_E_ARG;
+  }
   if (n == 0) return 0;
   if (!task_id || !msg || !views || !status || (n_task_keys && !task_keys) ||
       (n_global_keys && !global_keys) || n > 0x7FFFFFFFu) {

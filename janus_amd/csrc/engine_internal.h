@@ -40,7 +40,9 @@ namespace p3g::eng {
 // guarantee: such calls on a created state never allocate or grow one of its buffers.  Staging of
 // host-pointer inputs, and prio3gpu_shard, allocate on first use at a new size and report
 // PRIO3GPU_E_CAPACITY if the device cannot hold it.  The context's scratch (accumulation plan and
-// partial sums, staged outputs) grows to the largest batch the context has seen.  An allocation
+// partial sums, staged outputs) grows to the largest batch the context has seen.  A state's
+// verify-key table and key index (prio3gpu_state_set_verify_keys) are allocated by the first keyed
+// use, the index for the state's capacity; the table grows with the number of keys.  An allocation
 // the device cannot hold is PRIO3GPU_E_CAPACITY, with the HIP error cleared so the next launch
 // check of the same context does not report it.
 struct DevBuf {
@@ -90,7 +92,7 @@ enum KernelId {
   KID_HPKE_SEAL, KID_HPKE_SEAL_SHARES, KID_HPKE_OPEN_TEAM, KID_HPKE_OPEN_TEAM_SHARES,
   KID_HPKE_SEAL_TEAM, KID_HPKE_SEAL_TEAM_SHARES, KID_P256_EPH, KID_P256_EPH_KEM,
   KID_HPKE_OPEN_TEAM_SPLIT, KID_HPKE_OPEN_TEAM_JOIN, KID_HPKE_TEAM_WIPE, KID_HPKE_SEAL_TEAM_SPLIT,
-  KID_HPKE_SEAL_TEAM_JOIN, KID_COUNT
+  KID_HPKE_SEAL_TEAM_JOIN, KID_QUERY_KEYED, KID_COUNT
 };
 
 // Per-kernel HIP-event timing on the context's stream (opt-in; used by bench.py).
@@ -265,6 +267,11 @@ struct prio3gpu_state {
   size_t cap = 0;
   size_t n = 0;
   size_t in_pitch = 0;  // row pitch of the caller's input shares (0: packed, the share length)
+  // prio3gpu_state_set_verify_keys: the batch's key table (vk_num x 16 B) and report r's row in it
+  // (vk_n x u32), allocated on the first keyed use.  vk_num == 0: the context's key, as ever.
+  DevBuf vkeys, vkidx;
+  uint32_t vk_num = 0;
+  size_t vk_n = 0;
   DevBuf t, jr, part, seed, meas, proof, prep, msg, status, nonces, pub, input, w;
   DevBuf fpart, flags;  // FixedPointBoundedL2VecSum: wire partials per row group, query flags
   size_t fpart_rows = 0;  // reports fpart holds (the query runs in chunks of at most this many)
@@ -317,6 +324,9 @@ int check_state(prio3gpu_ctx* c, prio3gpu_state* st, size_t n);
 int finish_call(prio3gpu_ctx* c, std::initializer_list<const void*> bufs);
 
 inline dim3 grid1(size_t n, uint32_t tpb) { return dim3((unsigned)((n + tpb - 1) / tpb)); }
+
+// A keyed state (prio3gpu_state_set_verify_keys) prepares exactly the n reports its index covers.
+int check_keyed_n(const prio3gpu_state* st, size_t n);
 
 // Row pitch of a state's input shares: the caller's (prio3gpu_state_set_input_pitch) or packed.
 inline size_t input_pitch(const prio3gpu_state* st) {

@@ -312,6 +312,28 @@ __global__ void __launch_bounds__(256) k_query_rand(Cfg cfg, uint32_t n, uint64_
   squeeze_vec<FO>(s, cfg.qr_len, out_t.at(r), cfg.xof, cfg.exact_squeeze);
 }
 
+// The same for a batch of several tasks (prio3gpu_state_set_verify_keys): report r's verify key
+// is row key_index[r] of `keys` (16 bytes a row; the host checked every index against the table).
+template <class FO>
+__global__ void __launch_bounds__(256) k_query_rand_keyed(Cfg cfg, uint32_t n, const uint8_t* keys,
+                                                          const uint32_t* key_index, CRows nonces,
+                                                          Rows out_t, const uint8_t* status) {
+  const uint32_t r = blockIdx.x * blockDim.x + threadIdx.x;
+  if (r >= n) return;
+  if (status && status[r] != ST_OK) return;
+  const uint8_t* vk = keys + 16u * (size_t)key_index[r];
+  const uint8_t* nz = nonces.at(r);
+  MsgBlock m;
+  m.clear();
+  m.header(cfg.algo_id, DST_QUERY_RANDOMNESS, ld64(vk), ld64(vk + 8));
+  m.put64(25, ld64(nz));
+  m.put64(33, ld64(nz + 8));
+  m.pad(41, cfg.xof);
+  uint64_t s[25];
+  sponge_one_block(s, m, cfg.xof);
+  squeeze_vec<FO>(s, cfg.qr_len, out_t.at(r), cfg.xof, cfg.exact_squeeze);
+}
+
 // Helper share expansion: meas share XOF(k_meas, dst1, [agg_id]) and proof share
 // XOF(k_proof, dst2, [agg_id]) (prio prepare_init, Share::Helper arms).
 template <class FO>

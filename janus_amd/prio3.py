@@ -164,6 +164,37 @@ class PrepareState:
             check(lib().prio3gpu_state_set_input_pitch(self._h, pitch), "state_set_input_pitch")
             self._pitch = pitch
 
+    def set_verify_keys(self, keys, key_index):
+        """Reports of several tasks in one batch (prio3gpu_state_set_verify_keys): report r of the
+        next prepare_init / prepare_init_xof / helper_init calls, which must cover exactly
+        len(key_index) reports, is prepared under keys[key_index[r]].  `keys`: a sequence of
+        16-byte keys or a (T, 16) uint8 array; `key_index`: (n,) uint32, numpy or a device tensor.
+        Both are copied by the call."""
+        if isinstance(keys, np.ndarray):
+            kt = np.ascontiguousarray(keys, dtype=np.uint8)
+        else:
+            keys = [bytes(k) for k in keys]
+            if any(len(k) != 16 for k in keys):
+                raise ValueError("verify keys are 16 bytes each")
+            kt = np.frombuffer(b"".join(keys), np.uint8).reshape(len(keys), 16)
+        if kt.ndim != 2 or kt.shape[1] != 16 or kt.shape[0] == 0:
+            raise ValueError("verify keys: a non-empty (T, 16) uint8 table")
+        idx = key_index
+        if isinstance(idx, (list, tuple)):
+            idx = np.asarray(idx, dtype=np.uint32)
+        if isinstance(idx, np.ndarray):
+            idx = np.ascontiguousarray(idx, dtype=np.uint32)
+        elif idx.element_size() != 4:
+            raise ValueError("key_index: a 32-bit integer tensor")
+        n = _nbytes(idx) // 4
+        check(lib().prio3gpu_state_set_verify_keys(self._h, _ptr(kt), kt.shape[0], _ptr(idx), n),
+              "state_set_verify_keys")
+
+    def clear_verify_keys(self):
+        """Back to the context's verify key for every report."""
+        check(lib().prio3gpu_state_set_verify_keys(self._h, None, 0, None, 0),
+              "state_set_verify_keys")
+
     def close(self):
         if getattr(self, "_h", None):
             lib().prio3gpu_state_destroy(self._h)

@@ -159,6 +159,9 @@ extern "C" {
                                  out: *mut *mut prio3gpu_state) -> c_int;
     pub fn prio3gpu_state_destroy(st: *mut prio3gpu_state) -> c_int;
     pub fn prio3gpu_state_set_input_pitch(st: *mut prio3gpu_state, pitch: usize) -> c_int;
+    pub fn prio3gpu_state_set_verify_keys(st: *mut prio3gpu_state, verify_keys: *const u8,
+                                          num_keys: u32, key_index: *const u32, n: usize)
+                                          -> c_int;
     pub fn prio3gpu_agg_create(ctx: *mut prio3gpu_ctx, num_slots: u32,
                                out: *mut *mut prio3gpu_agg) -> c_int;
     pub fn prio3gpu_agg_destroy(agg: *mut prio3gpu_agg) -> c_int;
