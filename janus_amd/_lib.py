@@ -37,7 +37,8 @@ class EmptyAggregation(Prio3GpuError):
 
 E_INVALID_MESSAGE = -7
 
-SOURCES = ("engine.hip", "engine_hpke.hip", "engine_hpke_split.hip", "codec.cpp", "hpke.cpp")
+SOURCES = ("engine.hip", "engine_hpke.hip", "engine_hpke_dh.hip", "engine_hpke_seal.hip",
+           "engine_hpke_team.hip", "engine_hpke_split.hip", "codec.cpp", "hpke.cpp")
 FLAGS = ("--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-shared")
 LIBS = ("-lrccl", "-lcrypto")
 HASH_MARKER = b"PRIO3GPU_BUILD_HASH="

@@ -4,15 +4,16 @@
 // rows in place; prio3gpu_hpke_open_report_shares_gpu packs a request's key groups for the first.
 // The seals: prio3gpu_hpke_seal_batch / _long_batch share hpke_seal_batch_entry, prio3gpu_seal_
 // input_shares / _long share seal_input_shares_entry.  With the "hpke_team_split" option the two
-// share-row calls may give a report several waves: share_split decides, and the kernels and their
-// launches are engine_hpke_split.hip's (hpke_split_launch.h).  prio3gpu_helper_init_request is the
-// helper's aggregate-init from the request's bytes, in steps req_plan ... req_host_fallback.
-// Every call refuses in one order: null context, suite, keys, n == 0, null arguments, pitches.
-// The context's scratch is named in engine_internal.h; a call's per-report secrets in it belong
-// to one CallSecrets (below), which states what every path keeps about them.  The suite
-// predicates and the column geometry are plan_hpke.h's (no HIP, tested on the CPU).  No Prio3
-// kernel is in scope here: the request path hands over to the Prio3 side (engine.hip) through the
-// public prio3gpu_helper_init alone.
+// share-row calls may give a report several waves: share_split decides.  prio3gpu_helper_init_
+// request is the helper's aggregate-init from the request's bytes, in steps req_plan ...
+// req_host_fallback.  Every call refuses in one order: null context, suite, keys, n == 0, null
+// arguments, pitches.  This unit is the host side alone: the checks, the staging, the secrets and
+// the entry points.  No kernel is in scope here: every launch is a call into one of the kernel
+// units engine_hpke_*.hip through hpke_launch.h, and the request path hands over to the Prio3
+// side (engine.hip) through the public prio3gpu_helper_init alone.  The context's scratch is named
+// in engine_internal.h; a call's per-report secrets in it belong to one CallSecrets (below), which
+// states what every path keeps about them.  The suite predicates and the column geometry are
+// plan_hpke.h's (no HIP, tested on the CPU).
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -20,19 +21,13 @@
 #include <cstring>
 #include <string>
 #include <thread>
-#include <type_traits>
 #include <vector>
 
 #include "../../include/prio3gpu.h"
 #include "../../include/prio3gpu_test.h"
 #include "engine_internal.h"
 #include "plan_hpke.h"
-#include "hpke_gpu.h"
-#include "helper_request.h"
-#include "hpke_seal_gpu.h"
-#include "hpke_open_team.h"
-#include "hpke_seal_team.h"
-#include "hpke_split_launch.h"
+#include "hpke_launch.h"
 
 using namespace p3g;
 using namespace p3g::eng;
@@ -52,11 +47,6 @@ int hpke_fetch_u64(prio3gpu_ctx* c, const uint64_t* p, uint64_t* out) {
     *out = *p;
   }
   return 0;
-}
-
-void wipe(void* p, size_t n) {  // a memset the compiler may not drop
-  memset(p, 0, n);
-  __asm__ __volatile__("" : : "r"(p) : "memory");
 }
 
 // The per-report secrets of the current call that lie in the engine's own memory, and their end:
@@ -124,7 +114,7 @@ size_t dh_bytes(size_t n, bool p256) { return n * (p256 ? 33 : 32); }
 uint8_t* dh_ok_at(void* d_dh, size_t n) { return static_cast<uint8_t*>(d_dh) + n * 32; }
 
 // The seal ladders' output for n reports: X25519 n encapsulated keys, then n DH values, 32 bytes
-// each; P-256 hpke_seal_gpu.h's layout, whose validity bytes follow the 96 n bytes of both.
+// each; P-256 kP256EphBytes' layout, whose validity bytes follow the 96 n bytes of both.
 size_t eph_bytes(size_t n, bool p256) { return n * (p256 ? kP256EphBytes : 64); }
 uint8_t* p256_eph_ok_at(void* d_eph, size_t n) { return static_cast<uint8_t*>(d_eph) + n * 96; }
 
@@ -145,90 +135,6 @@ void host_parallel(size_t n, int threads, F&& f) {
     });
   for (size_t i = 0; i < std::min(n, per); ++i) f(i);
   for (auto& th : pool) th.join();
-}
-
-// launch(ks) with sk clamped (decodeScalar25519): the scalar travels as a kernel argument, so no
-// device buffer ever holds the private key, and its host copy is wiped after the launch.
-template <class F>
-int with_clamped_scalar(const uint8_t* sk, F&& launch) {
-  X25519Scalar ks;
-  memcpy(ks.w, sk, 32);  // little-endian host
-  ks.w[0] &= ~7u;
-  ks.w[7] = (ks.w[7] & 0x7FFFFFFFu) | 0x40000000u;
-  launch(ks);
-  wipe(&ks, sizeof ks);
-  HIPCHK(hipGetLastError());
-  return 0;
-}
-
-// d_out[r] = X25519(sk, d_points[r]) for r < n.
-int launch_x25519(prio3gpu_ctx* c, const uint8_t* sk, size_t n, const uint8_t* d_points,
-                  uint32_t* d_out) {
-  return with_clamped_scalar(sk, [&](const X25519Scalar& ks) {
-    PROF(KID_X25519);
-    hipLaunchKernelGGL(k_x25519, dim3((unsigned)((n + 63) / 64)), dim3(64), 0, c->stream,
-                       (uint32_t)n, ks, d_points, d_out);
-  });
-}
-
-// The same over a key group of the request in device memory: d_dh[idx[j]] for j < m.
-int launch_x25519_idx(prio3gpu_ctx* c, const uint8_t* sk, size_t m, const uint32_t* d_idx,
-                      const uint8_t* d_msg, const ReqView* d_views, uint32_t* d_dh) {
-  return with_clamped_scalar(sk, [&](const X25519Scalar& ks) {
-    PROF(KID_X25519_IDX);
-    hipLaunchKernelGGL(k_x25519_idx, dim3((unsigned)((m + 63) / 64)), dim3(64), 0, c->stream,
-                       (uint32_t)m, ks, d_idx, d_msg, d_views, d_dh);
-  });
-}
-
-// A P-256 batch's constants: the coordinates of pk (pkRm of an open, pkR of a seal) and the empty
-// salt's pad states of bc.
-P256DhConsts p256_dh_consts(const uint8_t* pk, const HpkeBatchConsts& bc) {
-  P256DhConsts dc;
-  p256_load_be_words8(pk + 1, dc.pk.x);
-  p256_load_be_words8(pk + 33, dc.pk.y);
-  memcpy(dc.salt0_i, bc.salt0_i, sizeof dc.salt0_i);
-  memcpy(dc.salt0_o, bc.salt0_o, sizeof dc.salt0_o);
-  return dc;
-}
-
-// launch(ks, dc) with sk as a P-256 scalar (little-endian words from the 32 big-endian bytes) and
-// the batch's constants.  The keypair has passed p256_keypair_valid.  The scalar's host copy is
-// wiped after the launch.
-template <class F>
-int with_p256_scalar(const uint8_t* sk, const uint8_t* pk, const HpkeBatchConsts& bc, F&& launch) {
-  P256Scalar ks;
-  for (int i = 0; i < 8; ++i)
-    ks.w[i] = (uint32_t)sk[31 - 4 * i] | ((uint32_t)sk[30 - 4 * i] << 8) |
-              ((uint32_t)sk[29 - 4 * i] << 16) | ((uint32_t)sk[28 - 4 * i] << 24);
-  const P256DhConsts dc = p256_dh_consts(pk, bc);
-  launch(ks, dc);
-  wipe(&ks, sizeof ks);
-  HIPCHK(hipGetLastError());
-  return 0;
-}
-
-// d_out[r] = the shared_secret (raw: x([sk] point)) and d_ok[r] for the n packed 65-byte points.
-int launch_p256_dh(prio3gpu_ctx* c, const uint8_t* sk, const uint8_t* pk,
-                   const HpkeBatchConsts& bc, bool raw, size_t n, const uint8_t* d_points,
-                   uint32_t* d_out, uint8_t* d_ok) {
-  return with_p256_scalar(sk, pk, bc, [&](const P256Scalar& ks, const P256DhConsts& dc) {
-    PROF(KID_P256_DH);
-    hipLaunchKernelGGL(k_p256_dh, dim3((unsigned)((n + 63) / 64)), dim3(64), 0, c->stream,
-                       (uint32_t)n, ks, dc, raw ? 1u : 0u, d_points, d_out, d_ok);
-  });
-}
-
-// The same over a key group of the request in device memory.
-int launch_p256_dh_idx(prio3gpu_ctx* c, const uint8_t* sk, const uint8_t* pk,
-                       const HpkeBatchConsts& bc, size_t m, const uint32_t* d_idx,
-                       const uint8_t* d_msg, const ReqView* d_views, uint32_t* d_ss,
-                       uint8_t* d_ok) {
-  return with_p256_scalar(sk, pk, bc, [&](const P256Scalar& ks, const P256DhConsts& dc) {
-    PROF(KID_P256_DH_IDX);
-    hipLaunchKernelGGL(k_p256_dh_idx, dim3((unsigned)((m + 63) / 64)), dim3(64), 0, c->stream,
-                       (uint32_t)m, ks, dc, d_idx, d_msg, d_views, d_ss, d_ok);
-  });
 }
 
 // The DH step of an open under one keypair: the n packed encapsulated keys at d_points to the
@@ -255,21 +161,6 @@ int check_views(const Cfg& g, const prio3gpu_prepare_init_view* views, size_t n,
   return rc;
 }
 
-// k_req_gather over n checked views: rows of 16 / public_share_len / prep_share_len bytes.
-int launch_req_gather(prio3gpu_ctx* c, size_t n, const uint8_t* d_msg, size_t msg_len,
-                      const ReqView* d_views, uint8_t* d_nonces, uint8_t* d_pub, uint8_t* d_lps,
-                      uint8_t* d_faults) {
-  const Cfg& g = c->cfg;
-  {
-    PROF(KID_REQ_GATHER);
-    hipLaunchKernelGGL(k_req_gather, dim3((unsigned)req_gather_blocks(g, n), 3), dim3(256), 0,
-                       c->stream, (uint32_t)n, d_msg, (uint64_t)msg_len, d_views,
-                       g.public_share_len, g.prep_share_len, d_nonces, d_pub, d_lps, d_faults);
-  }
-  HIPCHK(hipGetLastError());
-  return 0;
-}
-
 // The context's options as plan_hpke.h's mask, and the suite check of an entry point under them:
 // a wave per report (`team`) is hpke_team_suite's for opens and seals alike; a lane per report is
 // hpke_gpu_suite's for an open and hpke_seal_suite's for a seal.
@@ -286,20 +177,6 @@ int suite_check(const prio3gpu_ctx* c, const char* who, bool seal, bool team, ui
   set_err("%s: HPKE suite 0x%04x/%u/%u is not taken %s on this context", who, kem, kdf, aead,
           team ? "a wave per report" : "a lane per report");
   return PRIO3GPU_E_UNSUPPORTED;
-}
-
-// f(KDF, AEAD) with the suite of bc as compile-time constants (one kernel instantiation each of
-// the nine pairs; the entry points have checked the suite, so no other value arrives).
-template <class F>
-void hpke_suite_dispatch(const HpkeBatchConsts& bc, F&& f) {
-  auto with_aead = [&](auto kdf) {
-    if (bc.aead_id == 1) f(kdf, std::integral_constant<int, 1>{});
-    else if (bc.aead_id == 2) f(kdf, std::integral_constant<int, 2>{});
-    else f(kdf, std::integral_constant<int, 3>{});
-  };
-  if (bc.kdf_id == 1) with_aead(std::integral_constant<int, 1>{});
-  else if (bc.kdf_id == 2) with_aead(std::integral_constant<int, 2>{});
-  else with_aead(std::integral_constant<int, 3>{});
 }
 
 int hpke_open_batch_impl(prio3gpu_ctx* c, uint16_t kem_id, uint16_t kdf_id, uint16_t aead_id,
@@ -345,26 +222,11 @@ int hpke_open_batch_impl(prio3gpu_ctx* c, uint16_t kem_id, uint16_t kdf_id, uint
     uint32_t* d_dh;
     CHK(open_dh(c, sec, kem_id, sk, pk, bc, /*raw=*/false, n, d_enc, &d_dh));
     // a lane per report, or (prio3gpu_hpke_open_long_batch) a wave per report
-    auto launch = [&](auto kernel, size_t per_block) {
-      hipLaunchKernelGGL(kernel, dim3((unsigned)((n + per_block - 1) / per_block)), dim3(256), 0,
-                         c->stream, (uint32_t)n, bc, d_dh, d_enc, d_aad,
-                         reinterpret_cast<const uint64_t*>(d_aoff), aad_total, d_ct,
-                         reinterpret_cast<const uint64_t*>(d_coff), ct_total, d_pt,
-                         reinterpret_cast<const uint64_t*>(d_poff), pt_total, d_st);
-    };
-    if (team) {
-      PROF(KID_HPKE_OPEN_TEAM);
-      hpke_suite_dispatch(bc, [&](auto kdf, auto aead) {
-        launch(k_hpke_open_team<decltype(kdf)::value, decltype(aead)::value>, kTeamsPerBlock);
-      });
-    } else {
-      PROF(KID_HPKE_OPEN);
-      hpke_suite_dispatch(bc, [&](auto kdf, auto aead) {
-        launch(k_hpke_open<decltype(kdf)::value, decltype(aead)::value>, 256);
-      });
-    }
-    HIPCHK(hipGetLastError());
-    return 0;
+    const PackedOpenCall q{(uint32_t)n, bc, d_dh, d_enc, d_aad,
+                           reinterpret_cast<const uint64_t*>(d_aoff), aad_total, d_ct,
+                           reinterpret_cast<const uint64_t*>(d_coff), ct_total, d_pt,
+                           reinterpret_cast<const uint64_t*>(d_poff), pt_total, d_st};
+    return team ? launch_hpke_open_team(c, q) : launch_hpke_open(c, q);
   }();
   CHK(sec.finish(c, rc));
   if (pt_host && pt_total > pt_first)
@@ -481,23 +343,6 @@ int open_group_packed(prio3gpu_ctx* c, const HpkePlan& plan, size_t k, const uin
 }
 
 // ---- prio3gpu_helper_init_request, step by step -------------------------------------------------
-// k_hpke_open_req over one key group, instantiated for the suite of bc.
-int launch_hpke_open_req(prio3gpu_ctx* c, const HpkeBatchConsts& bc, const ReqTaskId& tid,
-                         size_t m, const uint32_t* d_idx, const uint32_t* d_dh,
-                         const uint8_t* d_msg, const ReqView* d_views, uint8_t* d_pts,
-                         const uint64_t* d_poff, uint8_t* d_status) {
-  {
-    PROF(KID_HPKE_OPEN_REQ);
-    hpke_suite_dispatch(bc, [&](auto kdf, auto aead) {
-      hipLaunchKernelGGL((k_hpke_open_req<decltype(kdf)::value, decltype(aead)::value>),
-                         dim3((unsigned)((m + 255) / 256)), dim3(256), 0, c->stream, (uint32_t)m,
-                         bc, tid, d_idx, d_dh, d_msg, d_views, d_pts, d_poff, d_status);
-    });
-  }
-  HIPCHK(hipGetLastError());
-  return 0;
-}
-
 // One call's arguments, plan and buffers.
 struct ReqCall {
   prio3gpu_ctx* c;
@@ -631,13 +476,8 @@ int req_open_groups(ReqCall& q) {
 // 5. Plaintexts to input-share rows; the status image comes back for the host's classification.
 int req_decode(ReqCall& q) {
   prio3gpu_ctx* c = q.c;
-  {
-    PROF(KID_DECODE_PT);
-    hipLaunchKernelGGL(k_decode_plaintext_input_shares, grid1(q.n, 256), dim3(256), 0, c->stream,
-                       (uint32_t)q.n, q.d_pts, q.d_poff, c->cfg.helper_share_len, q.d_in,
-                       (uint64_t)q.in_pitch, q.d_faults, q.d_status);
-  }
-  HIPCHK(hipGetLastError());
+  CHK(launch_decode_plaintext_input_shares(c, q.n, q.d_pts, q.d_poff, c->cfg.helper_share_len,
+                                           q.d_in, q.in_pitch, q.d_faults, q.d_status));
   HIPCHK(hipMemcpyAsync(q.dst.data(), q.d_status, q.n, hipMemcpyDeviceToHost, c->stream));
   HIPCHK(hipStreamSynchronize(c->stream));
   return 0;
@@ -693,13 +533,8 @@ int req_host_fallback(ReqCall& q) {
   CHK(c->req.fallback.ensure(l.bytes));
   uint8_t* d_fb = c->req.fallback.u8();
   HIPCHK(hipMemcpyAsync(d_fb, q.fb.data(), l.bytes, hipMemcpyHostToDevice, c->stream));
-  {
-    PROF(KID_REQ_SCATTER);
-    hipLaunchKernelGGL(k_req_scatter, grid1(l.kf, 256), dim3(256), 0, c->stream, (uint32_t)l.kf,
-                       reinterpret_cast<const uint32_t*>(d_fb), d_fb + l.o_rows, d_fb + l.o_st,
-                       want, q.d_in, (uint64_t)q.in_pitch, q.d_faults, q.d_status);
-  }
-  HIPCHK(hipGetLastError());
+  CHK(launch_req_scatter(c, l.kf, reinterpret_cast<const uint32_t*>(d_fb), d_fb + l.o_rows,
+                         d_fb + l.o_st, want, q.d_in, q.in_pitch, q.d_faults, q.d_status));
   HIPCHK(hipMemsetAsync(d_fb, 0, l.bytes, c->stream));  // input shares are secrets too
   return 0;
 }
@@ -723,34 +558,6 @@ int seal_pk_check(uint16_t kem_id, const uint8_t* pk, size_t pk_len) {
   return 0;
 }
 
-// The generator, as SerializePublicKey writes it
-const uint8_t kP256G[65] = {
-    0x04, 0x6b, 0x17, 0xd1, 0xf2, 0xe1, 0x2c, 0x42, 0x47, 0xf8, 0xbc, 0xe6, 0xe5, 0x63, 0xa4,
-    0x40, 0xf2, 0x77, 0x03, 0x7d, 0x81, 0x2d, 0xeb, 0x33, 0xa0, 0xf4, 0xa1, 0x39, 0x45, 0xd8,
-    0x98, 0xc2, 0x96, 0x4f, 0xe3, 0x42, 0xe2, 0xfe, 0x1a, 0x7f, 0x9b, 0x8e, 0xe7, 0xeb, 0x4a,
-    0x7c, 0x0f, 0x9e, 0x16, 0x2b, 0xce, 0x33, 0x57, 0x6b, 0x31, 0x5e, 0xce, 0xcb, 0xb6, 0x40,
-    0x68, 0x37, 0xbf, 0x51, 0xf5};
-
-// k_p256_eph over n staged ephemeral scalars to the recipient pk (a point: seal_pk_check): the
-// points, the raw DH values and the validity bytes, in hpke_seal_gpu.h's layout at d_eph.
-int launch_p256_eph(prio3gpu_ctx* c, const uint8_t* pk, size_t n, const uint8_t* d_sk,
-                    uint32_t* d_eph) {
-  P256EphPoints pts;
-  uint32_t x[8], y[8];
-  if (!p256_decode(kP256G, x, y, pts.X[0], pts.Y[0]) ||
-      !p256_decode(pk, x, y, pts.X[1], pts.Y[1])) {
-    set_err("HPKE seal: the public key is not a P-256 point");
-    return PRIO3GPU_E_HPKE;
-  }
-  {
-    PROF(KID_P256_EPH);
-    hipLaunchKernelGGL(k_p256_eph, dim3((unsigned)((n + 63) / 64), 2), dim3(64), 0, c->stream,
-                       (uint32_t)n, d_sk, pts, d_eph, p256_eph_ok_at(d_eph, n));
-  }
-  HIPCHK(hipGetLastError());
-  return 0;
-}
-
 // Stage the n ephemeral keys and run both ladders of every report into the context's eph scratch
 // (*d_eph), both the call's secrets from here on.  Under P-256 the KEM half follows
 // (k_p256_eph_kem) and bc.dh_ok is set to the validity bytes.
@@ -765,25 +572,10 @@ int seal_ladders(prio3gpu_ctx* c, CallSecrets& sec, HpkeBatchConsts& bc, const u
   if (p256) {
     uint8_t* d_ok = p256_eph_ok_at(eph, n);
     bc.dh_ok = d_ok;
-    CHK(launch_p256_eph(c, pk, n, d_sk, eph));
-    const P256DhConsts dc = p256_dh_consts(pk, bc);
-    {
-      PROF(KID_P256_EPH_KEM);
-      hipLaunchKernelGGL(k_p256_eph_kem, dim3((unsigned)((n + 255) / 256)), dim3(256), 0,
-                         c->stream, (uint32_t)n, dc, eph, d_ok);
-    }
-    HIPCHK(hipGetLastError());
-    return 0;
+    CHK(launch_p256_eph(c, pk, n, d_sk, eph, d_ok));
+    return launch_p256_eph_kem(c, pk, bc, n, eph, d_ok);
   }
-  X25519Point pkw;
-  memcpy(pkw.w, pk, 32);  // little-endian host
-  {
-    PROF(KID_X25519_EPH);
-    hipLaunchKernelGGL(k_x25519_eph, dim3((unsigned)((n + 63) / 64), 2), dim3(64), 0, c->stream,
-                       (uint32_t)n, d_sk, pkw, eph);
-  }
-  HIPCHK(hipGetLastError());
-  return 0;
+  return launch_x25519_eph(c, pk, n, d_sk, eph);
 }
 
 // Where a seal writes an output of `bytes` bytes: the caller's buffer when it is device memory,
@@ -855,26 +647,11 @@ int hpke_seal_batch_entry(prio3gpu_ctx* c, uint16_t kem_id, uint16_t kdf_id, uin
     CHK(stage_secret(c, sec, c->seal.pt_in, pts, pt_total, &d_pt));
     CHK(seal_ladders(c, sec, bc, pk, n, sk_es, &d_eph));
     // a lane per report, or (prio3gpu_hpke_seal_long_batch) a wave per report
-    auto launch = [&](auto kernel, size_t per_block) {
-      hipLaunchKernelGGL(kernel, dim3((unsigned)((n + per_block - 1) / per_block)), dim3(256), 0,
-                         c->stream, (uint32_t)n, bc, d_eph, d_aad,
-                         reinterpret_cast<const uint64_t*>(d_aoff), aad_total, d_pt,
-                         reinterpret_cast<const uint64_t*>(d_poff), pt_total, d_enc, d_ct,
-                         reinterpret_cast<const uint64_t*>(d_coff), ct_total, d_st);
-    };
-    if (team) {
-      PROF(KID_HPKE_SEAL_TEAM);
-      hpke_suite_dispatch(bc, [&](auto kdf, auto aead) {
-        launch(k_hpke_seal_team<decltype(kdf)::value, decltype(aead)::value>, kTeamsPerBlock);
-      });
-    } else {
-      PROF(KID_HPKE_SEAL);
-      hpke_suite_dispatch(bc, [&](auto kdf, auto aead) {
-        launch(k_hpke_seal<decltype(kdf)::value, decltype(aead)::value>, 256);
-      });
-    }
-    HIPCHK(hipGetLastError());
-    return 0;
+    const PackedSealCall q{(uint32_t)n, bc, d_eph, d_aad,
+                           reinterpret_cast<const uint64_t*>(d_aoff), aad_total, d_pt,
+                           reinterpret_cast<const uint64_t*>(d_poff), pt_total, d_enc, d_ct,
+                           reinterpret_cast<const uint64_t*>(d_coff), ct_total, d_st};
+    return team ? launch_hpke_seal_team(c, q) : launch_hpke_seal(c, q);
   }();
   CHK(sec.finish(c, rc));
   CHK(copy_out(c, encs, d_enc, n * bc.nenc));
@@ -913,7 +690,7 @@ TeamSplit share_split(const prio3gpu_ctx* c, size_t n, uint32_t input_share_len,
                          (uint64_t)c->cus * 4 * split_waves_per_simd(aead_id));
 }
 
-// What a split call's kernels share (hpke_split_launch.h), with the call's scratch: the
+// What a split call's kernels share (hpke_launch.h's SplitShareCall), with the call's scratch: the
 // segments' sums and the header flags, the call's secret from here on.
 int split_call(prio3gpu_ctx* c, CallSecrets& sec, const TeamSplit& sp, size_t n,
                const HpkeBatchConsts& bc, const ReqTaskId& tid, const uint8_t* d_rid,
@@ -994,36 +771,21 @@ int seal_input_shares_entry(prio3gpu_ctx* c, const uint8_t* task_id, uint16_t ke
                      rows_span(n, spitch, input_share_len), &d_sh));
     CHK(seal_ladders(c, sec, bc, pk, n, sk_es, &d_eph));
     // a lane per report, or (prio3gpu_seal_input_shares_long) a wave per report
-    auto launch = [&](auto kernel, size_t per_block) {
-      hipLaunchKernelGGL(kernel, dim3((unsigned)((n + per_block - 1) / per_block)), dim3(256), 0,
-                         c->stream, (uint32_t)n, bc, tid, d_eph, d_rid,
-                         reinterpret_cast<const uint64_t*>(d_time), d_pub, public_share_len,
-                         d_sh, input_share_len, (uint64_t)spitch, d_enc,
-                         (uint64_t)(enc_host ? nenc : epitch), d_pay,
-                         (uint64_t)(pay_host ? plen : ppitch), d_st);
-    };
     const TeamSplit sp = team ? share_split(c, n, input_share_len, aead_id)
                               : TeamSplit{1, 0};
     if (sp.S >= 2) {  // several waves per report: the segments, then the tags and encs
       SplitShareCall q;
       CHK(split_call(c, sec, sp, n, bc, tid, d_rid, d_time, d_pub, public_share_len,
                      input_share_len, d_st, &q));
-      CHK(launch_seal_team_split(c, q, d_eph, d_sh, spitch, d_enc, enc_host ? nenc : epitch,
-                                 d_pay, pay_host ? plen : ppitch));
-    } else if (team) {
-      PROF(KID_HPKE_SEAL_TEAM_SHARES);
-      hpke_suite_dispatch(bc, [&](auto kdf, auto aead) {
-        launch(k_hpke_seal_team_shares<decltype(kdf)::value, decltype(aead)::value>,
-               kTeamsPerBlock);
-      });
-    } else {
-      PROF(KID_HPKE_SEAL_SHARES);
-      hpke_suite_dispatch(bc, [&](auto kdf, auto aead) {
-        launch(k_hpke_seal_shares<decltype(kdf)::value, decltype(aead)::value>, 256);
-      });
+      return launch_seal_team_split(c, q, d_eph, d_sh, spitch, d_enc, enc_host ? nenc : epitch,
+                                    d_pay, pay_host ? plen : ppitch);
     }
-    HIPCHK(hipGetLastError());
-    return 0;
+    const ShareSealCall q{(uint32_t)n, bc, tid, d_eph, d_rid,
+                          reinterpret_cast<const uint64_t*>(d_time), d_pub, public_share_len,
+                          d_sh, input_share_len, (uint64_t)spitch, d_enc,
+                          (uint64_t)(enc_host ? nenc : epitch), d_pay,
+                          (uint64_t)(pay_host ? plen : ppitch), d_st};
+    return team ? launch_hpke_seal_team_shares(c, q) : launch_hpke_seal_shares(c, q);
   }();
   CHK(sec.finish(c, rc));
   if (enc_host) CHK(packed_rows_to_host(c, out_encs, epitch, d_enc, nenc, n));
@@ -1197,19 +959,11 @@ int prio3gpu_open_input_shares(prio3gpu_ctx* c, const uint8_t* task_id, uint16_t
       return launch_open_team_split(c, q, d_dh, d_enc, epitch, d_pay, ppitch, d_out,
                                     out_host ? input_share_len : spitch);
     }
-    {
-      PROF(KID_HPKE_OPEN_TEAM_SHARES);
-      hpke_suite_dispatch(bc, [&](auto kdf, auto aead) {
-        hipLaunchKernelGGL((k_hpke_open_team_shares<decltype(kdf)::value, decltype(aead)::value>),
-                           dim3((unsigned)((n + kTeamsPerBlock - 1) / kTeamsPerBlock)), dim3(256),
-                           0, c->stream, (uint32_t)n, bc, tid, d_dh, d_rid,
-                           reinterpret_cast<const uint64_t*>(d_time), d_pub, public_share_len,
-                           d_enc, (uint64_t)epitch, d_pay, (uint64_t)ppitch, input_share_len,
-                           d_out, (uint64_t)(out_host ? input_share_len : spitch), d_st);
-      });
-    }
-    HIPCHK(hipGetLastError());
-    return 0;
+    return launch_hpke_open_team_shares(
+        c, ShareOpenCall{(uint32_t)n, bc, tid, d_dh, d_rid,
+                         reinterpret_cast<const uint64_t*>(d_time), d_pub, public_share_len,
+                         d_enc, (uint64_t)epitch, d_pay, (uint64_t)ppitch, input_share_len,
+                         d_out, (uint64_t)(out_host ? input_share_len : spitch), d_st});
   }();
   rc = sec.finish(c, rc);
   if (out_host && out_bytes) {
@@ -1424,7 +1178,9 @@ int prio3gpu_test_p256_eph_gpu(prio3gpu_ctx* c, const uint8_t* pk, const uint8_t
   CallSecrets sec;  // the ladders' output is this hook's: cleared after its copy
   sec.add(d_eph, nb);
   int rc = stage_secret(c, sec, c->seal.eph_sk, sk_es, n * 32, &d_sk);
-  if (!rc) rc = launch_p256_eph(c, pk, n, d_sk, reinterpret_cast<uint32_t*>(d_eph));
+  if (!rc)
+    rc = launch_p256_eph(c, pk, n, d_sk, reinterpret_cast<uint32_t*>(d_eph),
+                         p256_eph_ok_at(d_eph, n));
   if (!rc) rc = copy_out(c, h.data(), d_eph, nb);
   rc = sec.finish(c, rc);
   HIPCHK(hipStreamSynchronize(c->stream));
@@ -1462,10 +1218,8 @@ int prio3gpu_test_poly1305_gpu(prio3gpu_ctx* c, const uint8_t* keys, const uint8
   CHK(stage_in(c, c->hpke.aad, msgs, total, &d_msgs, kHpkeMinStage));
   CHK(stage_in(c, c->hpke.aad_off, msg_offsets, (n + 1) * 8, &d_off, kHpkeMinStage));
   CHK(c->hpke.pt_out.ensure(n * 16));
-  hipLaunchKernelGGL(k_test_poly1305, dim3((unsigned)((n + 63) / 64)), dim3(64), 0, c->stream,
-                     (uint32_t)n, d_keys, d_msgs, reinterpret_cast<const uint64_t*>(d_off),
-                     c->hpke.pt_out.u8());
-  HIPCHK(hipGetLastError());
+  CHK(launch_test_poly1305(c, n, d_keys, d_msgs, reinterpret_cast<const uint64_t*>(d_off),
+                           c->hpke.pt_out.u8()));
   HIPCHK(hipMemcpyAsync(tags, c->hpke.pt_out.u8(), n * 16, hipMemcpyDeviceToHost, c->stream));
   HIPCHK(hipStreamSynchronize(c->stream));
   return 0;

@@ -1,34 +1,18 @@
 // The launches of hpke_team_split.h's kernels (several waves per report for the share-row HPKE
 // open and seal, the context's "hpke_team_split" option), a unit of its own so that its thirty-six
-// instantiations compile beside engine_hpke.hip's.  engine_hpke.hip checks the call, stages its
-// buffers, runs the DH and owns the secrets (CallSecrets); this unit only queues kernels on the
-// context's stream (hpke_split_launch.h).
+// instantiations compile beside the other kernel units'.  engine_hpke.hip checks the call, stages
+// its buffers, runs the DH and owns the secrets (CallSecrets); this unit only queues kernels on
+// the context's stream (hpke_launch.h).
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
-#include <type_traits>
 
-#include "engine_internal.h"
-#include "hpke_split_launch.h"
+#include "hpke_launch.h"
 #include "hpke_team_split.h"
 
 namespace p3g::eng {
 
 namespace {
-
-// f(KDF, AEAD) with the suite of bc as compile-time constants (the entry points have checked the
-// suite, so no other value arrives).
-template <class F>
-void split_suite_dispatch(const HpkeBatchConsts& bc, F&& f) {
-  auto with_aead = [&](auto kdf) {
-    if (bc.aead_id == 1) f(kdf, std::integral_constant<int, 1>{});
-    else if (bc.aead_id == 2) f(kdf, std::integral_constant<int, 2>{});
-    else f(kdf, std::integral_constant<int, 3>{});
-  };
-  if (bc.kdf_id == 1) with_aead(std::integral_constant<int, 1>{});
-  else if (bc.kdf_id == 2) with_aead(std::integral_constant<int, 2>{});
-  else with_aead(std::integral_constant<int, 3>{});
-}
 
 dim3 waves_grid(uint64_t waves) {
   return dim3((unsigned)((waves + kTeamsPerBlock - 1) / kTeamsPerBlock));
@@ -61,7 +45,7 @@ int launch_open_team_split(prio3gpu_ctx* c, const SplitShareCall& q, const uint3
   };
   {
     PROF(KID_HPKE_OPEN_TEAM_SPLIT);
-    split_suite_dispatch(q.bc, [&](auto kdf, auto aead) {
+    hpke_suite_dispatch(q.bc, [&](auto kdf, auto aead) {
       hipLaunchKernelGGL((k_hpke_open_team_split<decltype(kdf)::value, decltype(aead)::value>),
                          waves_grid((uint64_t)q.n * q.S), dim3(256), 0, c->stream, q.n, q.S, q.L,
                          q.bc, q.tid, dh, q.rids, q.times, q.pubs, q.pslen, encs, enc_pitch,
@@ -73,7 +57,7 @@ int launch_open_team_split(prio3gpu_ctx* c, const SplitShareCall& q, const uint3
   if (e != hipSuccess) return fail(e);
   {
     PROF(KID_HPKE_OPEN_TEAM_JOIN);
-    split_suite_dispatch(q.bc, [&](auto kdf, auto aead) {
+    hpke_suite_dispatch(q.bc, [&](auto kdf, auto aead) {
       hipLaunchKernelGGL((k_hpke_open_team_join<decltype(kdf)::value, decltype(aead)::value>),
                          waves_grid(q.n), dim3(256), 0, c->stream, q.n, q.S, q.L, q.bc, dh, encs,
                          enc_pitch, payloads, ppitch, q.pslen, q.slen, parts_of(q), flags_of(q),
@@ -99,7 +83,7 @@ int launch_seal_team_split(prio3gpu_ctx* c, const SplitShareCall& q, const uint3
                            uint64_t enc_pitch, uint8_t* payloads, uint64_t ppitch) {
   {
     PROF(KID_HPKE_SEAL_TEAM_SPLIT);
-    split_suite_dispatch(q.bc, [&](auto kdf, auto aead) {
+    hpke_suite_dispatch(q.bc, [&](auto kdf, auto aead) {
       hipLaunchKernelGGL((k_hpke_seal_team_split<decltype(kdf)::value, decltype(aead)::value>),
                          waves_grid((uint64_t)q.n * q.S), dim3(256), 0, c->stream, q.n, q.S, q.L,
                          q.bc, q.tid, eph, q.rids, q.times, q.pubs, q.pslen, shares, q.slen,
@@ -109,7 +93,7 @@ int launch_seal_team_split(prio3gpu_ctx* c, const SplitShareCall& q, const uint3
   HIPCHK(hipGetLastError());
   {
     PROF(KID_HPKE_SEAL_TEAM_JOIN);
-    split_suite_dispatch(q.bc, [&](auto kdf, auto aead) {
+    hpke_suite_dispatch(q.bc, [&](auto kdf, auto aead) {
       hipLaunchKernelGGL((k_hpke_seal_team_join<decltype(kdf)::value, decltype(aead)::value>),
                          waves_grid(q.n), dim3(256), 0, c->stream, q.n, q.S, q.L, q.bc, eph,
                          q.pslen, q.slen, parts_of(q), encs, enc_pitch, payloads, ppitch,

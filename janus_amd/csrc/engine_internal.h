@@ -1,4 +1,4 @@
-// What the engine's translation units (engine.hip, engine_hpke.hip) share on the host: the error
+// What the engine's translation units (engine.hip, engine_hpke*.hip) share on the host: the error
 // macros, the device buffer, the kernel ids and their HIP-event timing, the three objects behind
 // the ABI's handles, and the few helpers both units call.  No kernel header is included here, so a
 // unit gets only the kernels it includes itself.

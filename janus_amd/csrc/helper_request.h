@@ -4,21 +4,19 @@
 // kernel reads the request through the decoded views (prio3gpu_prepare_init_view), whose offsets
 // the host has checked against the message length.
 //   k_req_gather        nonces, public shares, leader prep shares -> rows; faults[i]
-//   k_x25519_idx        k_x25519 over a key group (a list of report indices), enc read in place
-//   k_p256_dh_idx       k_p256_dh over a key group, enc read in place
-//   k_hpke_open_req     hpke_open_lane (of the group's suite) over a key group: enc and ciphertext
-//                       in place, the InputShareAad assembled from its five pieces (hpke_lane.h's
-//                       ReqAad), never materialised
+//   k_hpke_open_req     hpke_open_lane (of the group's suite) over a key group (a list of report
+//                       indices): enc and ciphertext in place, the InputShareAad assembled from
+//                       its five pieces (hpke_lane.h's ReqAad), never materialised
 //   k_decode_plaintext_input_shares   PlaintextInputShare -> helper input share row, then faults
 //   k_req_scatter       host-fallback reports' rows and statuses into place
-// Included by engine_hpke.hip after include/prio3gpu.h.
+// A key group's DH values are hpke_dh_gpu.h's k_x25519_idx and k_p256_dh_idx, enc read in place.
+// Included by engine_hpke_team.hip alone, after include/prio3gpu.h.
 #pragma once
-#include "hpke_gpu.h"
+#include "hpke_kernel_args.h"
+#include "hpke_lane.h"
 #include "request_parse.h"
 
 namespace p3g {
-
-using ReqView = prio3gpu_prepare_init_view;
 
 // ---- gather ------------------------------------------------------------------------------------
 // One lane per 16-byte piece of a destination row; blockIdx.y picks the row kind (0 nonces,
@@ -76,45 +74,6 @@ __global__ void __launch_bounds__(256) k_req_gather(uint32_t n, const uint8_t* m
 }
 
 // ---- the open, in place ------------------------------------------------------------------------
-// dh[idx[j]] = X25519(k, enc of report idx[j]) for the m reports of a key group.  A report whose
-// encapsulated key is not 32 bytes is not read (k_hpke_open_req rejects it); its lane runs the
-// ladder over zeros like an idle lane.
-__global__ void __launch_bounds__(64) k_x25519_idx(uint32_t m, X25519Scalar k, const uint32_t* idx,
-                                                   const uint8_t* msg, const ReqView* views,
-                                                   uint32_t* dh) {
-  const uint32_t j = blockIdx.x * blockDim.x + threadIdx.x;
-  const bool live = j < m;
-  const uint32_t r = idx[live ? j : m - 1];
-  const ReqView& v = views[r];
-  uint32_t w[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-  if (v.enc_len == 32) load_le_words8(msg + v.enc_off, w);
-  x25519_lane(k, w);
-  if (live) {
-#pragma unroll
-    for (int i = 0; i < 8; ++i) dh[(size_t)r * 8 + i] = w[i];
-  }
-}
-
-// ss[idx[j]] = the P-256 shared_secret of (k, enc of report idx[j]) and ok[idx[j]] = 1 for the m
-// reports of a key group; zeros and 0 for an enc DeserializePublicKey refuses or whose length is
-// not 65 (not read: k_hpke_open_req rejects that one by its length).
-__global__ void __launch_bounds__(64) k_p256_dh_idx(uint32_t m, P256Scalar k, P256DhConsts dc,
-                                                    const uint32_t* idx, const uint8_t* msg,
-                                                    const ReqView* views, uint32_t* ss,
-                                                    uint8_t* ok) {
-  const uint32_t j = blockIdx.x * blockDim.x + threadIdx.x;
-  const bool live = j < m;
-  const uint32_t r = idx[live ? j : m - 1];
-  const ReqView& v = views[r];
-  uint32_t w[8];
-  const bool good = p256_lane_out(k, dc, 0u, msg + v.enc_off, v.enc_len == 65, w);
-  if (live) {
-#pragma unroll
-    for (int i = 0; i < 8; ++i) ss[(size_t)r * 8 + i] = w[i];
-    ok[r] = good ? 1 : 0;
-  }
-}
-
 // One lane per report of a key group: hpke_open_lane with enc, ciphertext and AAD read where the
 // request has them; report r's plaintext goes to pts[pt_off[r] .. pt_off[r + 1]).  An enc_len
 // other than the KEM's Nenc (32; 65 for P-256), a payload shorter than the tag or longer than its slot: status 4, nothing read.

@@ -140,7 +140,7 @@ DEVI void hpke_seal_lane(const uint8_t* sbox, const HpkeBatchConsts& bc, const u
   for (uint64_t j = plen + 16; j < ct_cap; ++j) ct[j] = 0;
 }
 
-// Where report r's enc and DH words lie in the seal ladders' output (hpke_seal_gpu.h):
+// Where report r's enc and DH words lie in the seal ladders' output (hpke_dh_gpu.h):
 // k_x25519_eph's n encs of 8 words, then n DH values; under P-256 (bc.dh_ok) n points of 16 words,
 // then n shared secrets.
 DEVI const uint32_t* eph_enc(const HpkeBatchConsts& bc, const uint32_t* eph, uint32_t r) {

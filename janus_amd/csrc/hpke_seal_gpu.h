@@ -3,112 +3,19 @@
 // (KDF 1-3 x AEAD 1-3), RFC 9180 base mode, single shot: what a DAP client does once per input
 // share (client/src/lib.rs:212-258, core/src/hpke.rs:158-182).  The mirror image of hpke_gpu.h's
 // open, one lane per report, every report of a launch to ONE recipient key, each under its own
-// ephemeral key:
-//   k_x25519_eph               enc = X25519(skE, 9), dh = X25519(skE, pkR)         RFC 9180 §4.1
-//   k_p256_eph                 enc = [skE] G, dh = x([skE] pkR), the scalar's validity   §7.1
-//   k_p256_eph_kem             dh -> shared_secret (ExtractAndExpand over enc || pkR)    §4.1
+// ephemeral key, whose ladders (hpke_dh_gpu.h's k_x25519_eph, or k_p256_eph and k_p256_eph_kem)
+// have run before:
 //   k_hpke_seal<KDF, AEAD>     key schedule + AEAD encryption over packed plaintexts and AADs
 //   k_hpke_seal_shares<KDF, AEAD>   the same over Prio3 input shares: the PlaintextInputShare and
 //                              the InputShareAad are byte sources over the caller's rows and are
 //                              never written to memory
-// The two ladders of a report run on two lanes of one launch (blockIdx.y picks the point), each
-// the unchanged x25519_lane with the lane's own scalar: one ladder's registers per lane, no
-// scratch, and twice the lanes for the latency-bound field arithmetic to hide behind.
 // Only the kernels are here: the lane (hpke_seal_lane) and the two byte sources (SharePlaintext,
-// ReqAad) are hpke_lane.h's, free of HIP and run by CPU tests too.  Included by engine_hpke.hip.
+// ReqAad) are hpke_lane.h's, free of HIP and run by CPU tests too.  Included by
+// engine_hpke_seal.hip alone.
 #pragma once
-#include "hpke_gpu.h"
 #include "hpke_lane.h"
-#include "x25519.h"
 
 namespace p3g {
-
-struct X25519Point {  // a u coordinate as little-endian words; a kernel argument
-  uint32_t w[8];
-};
-
-// out[which n 8 + r 8 ..] = X25519(sk_es[r], which ? pkR : 9) as 8 little-endian words:
-// blockIdx.y = 0 the encapsulated keys, 1 the DH values.  The scalar is clamped here
-// (decodeScalar25519); its bits are read with selects inside x25519_lane, so no branch and no
-// address depends on it or on a field value.
-__global__ void __launch_bounds__(64) k_x25519_eph(uint32_t n, const uint8_t* sk_es,
-                                                   X25519Point pk, uint32_t* out) {
-  const uint32_t r = blockIdx.x * blockDim.x + threadIdx.x;
-  const uint32_t which = blockIdx.y;
-  const bool live = r < n;
-  X25519Scalar k;
-  load_le_words8(sk_es + (size_t)(live ? r : n - 1) * 32, k.w);
-  k.w[0] &= ~7u;
-  k.w[7] = (k.w[7] & 0x7FFFFFFFu) | 0x40000000u;
-  uint32_t w[8];
-#pragma unroll
-  for (int i = 0; i < 8; ++i) w[i] = which ? pk.w[i] : (i ? 0u : 9u);
-  x25519_lane(k, w);
-  if (live) {
-    uint32_t* o = out + ((size_t)which * n + r) * 8;
-#pragma unroll
-    for (int i = 0; i < 8; ++i) o[i] = w[i];
-  }
-}
-
-// The ladders' output for n reports under P-256, as the seal kernels read it (bc.dh_ok set), in
-// bytes: [0, 64 n) the ephemeral points' x || y, 64 per report; [64 n, 96 n) the DH values' x, after
-// k_p256_eph_kem the shared secrets; [96 n, 97 n) one validity byte per report (bc.dh_ok).
-constexpr size_t kP256EphBytes = 97;
-
-struct P256EphPoints {  // G ([0]) and pkR ([1]) in Montgomery coordinates; a kernel argument
-  Fp256 X[2], Y[2];
-};
-
-// The P-256 counterpart of k_x25519_eph: blockIdx.y = 0 the encapsulated keys [sk_es[r]] G (both
-// coordinates, and the report's validity byte), 1 the DH values x([sk_es[r]] pkR).  ONE ladder:
-// the point comes from selects on blockIdx.y.  The scalar is the lane's own (p256_eph_lane): its
-// bits are select masks only, no branch and no address depends on it; a scalar outside [1, n)
-// runs the same instructions and leaves zeros and ok = 0.
-__global__ void __launch_bounds__(64) k_p256_eph(uint32_t n, const uint8_t* sk_es,
-                                                 P256EphPoints pts, uint32_t* out, uint8_t* ok) {
-  const uint32_t r = blockIdx.x * blockDim.x + threadIdx.x;
-  const uint32_t which = blockIdx.y;
-  const bool live = r < n;
-  Fp256 X, Y;
-#pragma unroll
-  for (int i = 0; i < 8; ++i) {
-    X.v[i] = which ? pts.X[1].v[i] : pts.X[0].v[i];
-    Y.v[i] = which ? pts.Y[1].v[i] : pts.Y[0].v[i];
-  }
-  uint32_t x[8], y[8];
-  const bool good = p256_eph_lane(sk_es + (size_t)(live ? r : n - 1) * 32, X, Y, x, y);
-  if (!live) return;
-  if (which == 0) {
-    uint32_t* o = out + (size_t)r * 16;
-#pragma unroll
-    for (int i = 0; i < 8; ++i) o[i] = bswap32(x[i]), o[8 + i] = bswap32(y[i]);
-    ok[r] = good ? 1 : 0;
-  } else {
-    uint32_t* o = out + (size_t)n * 16 + (size_t)r * 8;
-#pragma unroll
-    for (int i = 0; i < 8; ++i) o[i] = bswap32(x[i]);
-  }
-}
-
-// The KEM half after k_p256_eph, one lane per report: eph's DH value becomes the shared_secret in
-// place (zeros for a report whose ok byte is 0).
-__global__ void __launch_bounds__(256) k_p256_eph_kem(uint32_t n, P256DhConsts dc, uint32_t* eph,
-                                                      const uint8_t* ok) {
-  const uint32_t r = blockIdx.x * blockDim.x + threadIdx.x;
-  if (r >= n) return;
-  uint32_t ex[8], ey[8], dh[8], ss[8];
-  uint32_t* d = eph + (size_t)n * 16 + (size_t)r * 8;
-#pragma unroll
-  for (int i = 0; i < 8; ++i) {
-    ex[i] = bswap32(eph[(size_t)r * 16 + i]);
-    ey[i] = bswap32(eph[(size_t)r * 16 + 8 + i]);
-    dh[i] = bswap32(d[i]);
-  }
-  p256_eph_shared_secret(dc.salt0_i, dc.salt0_o, dh, ex, ey, dc.pk, ok[r] != 0, ss);
-#pragma unroll
-  for (int i = 0; i < 8; ++i) d[i] = bswap32(ss[i]);
-}
 
 // One lane per report: hpke_seal_lane over packed plaintexts and AADs; report r's ciphertext ||
 // tag goes to cts[ct_off[r] .. ct_off[r + 1]) and its enc to encs[bc.nenc r ..].  A slot shorter than

@@ -1,6 +1,6 @@
 // Batched HPKE seal of long plaintexts on the GPU, one WAVE per report: DHKEM(X25519, HKDF-SHA256)
 // (and DHKEM(P-256, HKDF-SHA256) behind the context's "hpke_gpu_p256" option; its ladders are
-// hpke_seal_gpu.h's k_p256_eph) with HKDF-SHA256 / -SHA384 / -SHA512 and AES-128-GCM / AES-256-GCM / ChaCha20-Poly1305, RFC 9180
+// hpke_dh_gpu.h's k_p256_eph) with HKDF-SHA256 / -SHA384 / -SHA512 and AES-128-GCM / AES-256-GCM / ChaCha20-Poly1305, RFC 9180
 // base mode, single shot.  What a DAP client does for the leader's input share of a hundred
 // kilobytes, where hpke_seal_gpu.h's lane per report would walk it alone; the mirror of
 // hpke_open_team.h:
@@ -8,7 +8,7 @@
 //   k_hpke_seal_team_shares<KDF, AEAD>   Prio3 input-share rows in, enc and payload columns out: the
 //                                        PlaintextInputShare and the InputShareAad are byte sources
 //                                        over the caller's rows and are never written to memory
-// The ladders are hpke_seal_gpu.h's k_x25519_eph, one lane per report and point, launched before.
+// The ladders are hpke_dh_gpu.h's k_x25519_eph, one lane per report and point, launched before.
 // Four reports per block; the only block barrier is the one after the S-box build (reports differ
 // in length).  Every lane of a wave derives the same key, nonce, round keys, H and AAD hash
 // (registers only); the lanes then share the plaintext by stripes (aes_gcm_team.h): a block is
@@ -16,14 +16,13 @@
 // and one lane stores it.  The wave's table of H^1 .. H^64 (LDS, key-derived) is zeroed before the
 // wave ends.  With ChaCha20-Poly1305 (AEAD 3) the lanes share the plaintext by 64-byte chunks
 // (chacha_poly_team.h): a block is encrypted, stored and absorbed by Poly1305, and the lanes' sums
-// are added by hpke_open_team.h's poly_team_sum; no S-box, no block barrier, no LDS.  Only the
+// are added by hpke_team_wave.h's poly_team_sum; no S-box, no block barrier, no LDS.  Only the
 // kernels and what crosses lanes are here; a lane's arithmetic is aes_gcm_team.h's and
 // chacha_poly_team.h's, free of HIP and run by CPU tests too.  The wave's place in its block
-// (team_wave_setup, team_lds_sync, kTeam, kTeamsPerBlock) is hpke_open_team.h's.  Included by
-// engine_hpke.hip.
+// (team_wave_setup, team_lds_sync) is hpke_team_wave.h's.  Included by
+// engine_hpke_team.hip alone.
 #pragma once
-#include "hpke_open_team.h"
-#include "hpke_seal_gpu.h"
+#include "hpke_team_wave.h"
 
 namespace p3g {
 

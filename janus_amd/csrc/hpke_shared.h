@@ -28,6 +28,10 @@ struct HpkeBatchConsts {
   const uint8_t* dh_ok;
 };
 
+// The wave-per-report kernels' geometry, which their launches' grids follow.
+constexpr uint32_t kTeam = 64;          // lanes per report: one wave
+constexpr uint32_t kTeamsPerBlock = 4;  // reports per 256-thread block
+
 // hpke.cpp.  false if the suite is not one above or its primitives are unavailable.  pk is pkR's
 // 32 bytes for X25519 and is not read for P-256.
 bool hpke_batch_consts(uint16_t kem_id, uint16_t kdf_id, uint16_t aead_id, const uint8_t* pk, const uint8_t* info,

@@ -26,11 +26,10 @@
 // gets its slice zeroed by each of its waves, and so does a seal whose DH value is refused.
 // Only the kernels are here; a lane's arithmetic is aes_gcm_team.h's and chacha_poly_team.h's,
 // free of HIP and run by a CPU test (tests/native/team_split_host.cpp); the wave's place in its
-// block (team_wave_setup, team_lds_sync, poly_team_sum, kTeam) is hpke_open_team.h's.  Included by
-// engine_hpke_split.hip alone, which includes no header with a kernel that is no template: those
-// belong to engine_hpke.hip.
+// block (team_wave_setup, team_lds_sync, poly_team_sum) is hpke_team_wave.h's.  Included by
+// engine_hpke_split.hip alone.
 #pragma once
-#include "hpke_open_team.h"
+#include "hpke_team_wave.h"
 
 namespace p3g {
 

@@ -1,11 +1,11 @@
 // NIST P-256 for the GPU HPKE open of DHKEM(P-256, HKDF-SHA256) (KEM 0x0010), free of HIP so the
-// device kernels (hpke_gpu.h: k_p256_dh, helper_request.h: k_p256_dh_idx) and a CPU test
+// device kernels (hpke_dh_gpu.h: k_p256_dh, k_p256_dh_idx) and a CPU test
 // (tests/native/p256_host.cpp) run the same code:
 //   Fp256, fp_*            GF(p), p = 2^256 - 2^224 + 2^192 + 2^96 - 1            FIPS 186-4 D.1.2.3
 //   p256_decode            DeserializePublicKey with the on-curve check           RFC 9180 §7.1.1, §7.1.4
 //   p256_dh_x, p256_mul_xy x([k] P) and (x, y)([k] P), one instruction sequence for every scalar,
 //                          wave-uniform (the recipient's key) or the lane's own (the sender's
-//                          ephemeral key, hpke_seal_gpu.h: k_p256_eph)
+//                          ephemeral key, hpke_dh_gpu.h: k_p256_eph)
 // The KEM half (ExtractAndExpand, RFC 9180 §4.1) and the kernels' lane are p256_kem.h's, which
 // hashes; this header has no dependency, so the host planning (plan_hpke.h) validates keypairs
 // with the kernels' own decoder.

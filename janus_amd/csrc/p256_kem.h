@@ -1,6 +1,6 @@
 // The KEM half of DHKEM(P-256, HKDF-SHA256) (RFC 9180 §4.1) over p256.h, one lane of the DH
-// kernels (hpke_gpu.h: k_p256_dh, helper_request.h: k_p256_dh_idx) and one lane of the sender's
-// (hpke_seal_gpu.h: k_p256_eph, k_p256_eph_kem).  Free of HIP like p256.h; it hashes with
+// kernels (hpke_dh_gpu.h: k_p256_dh, k_p256_dh_idx) and one lane of the sender's
+// (hpke_dh_gpu.h: k_p256_eph, k_p256_eph_kem).  Free of HIP like p256.h; it hashes with
 // sha256.h, device code in a HIP unit and host code in a plain C++ build
 // (tests/native/p256_host.cpp, tests/native/p256_eph_host.cpp).
 #pragma once
@@ -153,7 +153,7 @@ P3G_P256_DEV bool p256_dh_lane(const P256Scalar& k, const P256PublicKey& pk,
   return ok;
 }
 
-// One lane of the sender's ladders (hpke_seal_gpu.h: k_p256_eph): (x, y)([sk_e] P) as big-endian
+// One lane of the sender's ladders (hpke_dh_gpu.h: k_p256_eph): (x, y)([sk_e] P) as big-endian
 // words for the report's own ephemeral scalar sk_e (32 big-endian bytes, any alignment) and a valid
 // point P = (X, Y), the generator (the encapsulated key) or the recipient's key (the DH value).
 // Returns whether sk_e is in [1, n); a scalar outside runs the same instructions over 1 and both

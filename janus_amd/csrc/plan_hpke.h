@@ -1,8 +1,9 @@
 // Host planning of the helper's HPKE open and of the fused aggregate-init from the request's bytes,
 // no HIP: which key opens a report, which reports the GPU opens (one group per keypair) and which
 // the host, the second trial with a global key, the host fallback's packed upload, and the checks
-// of a request's views.  Included by engine_hpke.hip and hpke.cpp; built alone with g++ by
-// tests/test_hpke_plan.py.  A plan points at the caller's keypairs and never copies key bytes.
+// of a request's views.  Included by engine_hpke.hip, engine_hpke_team.hip (req_gather_blocks)
+// and hpke.cpp; built alone with g++ by tests/test_hpke_plan.py.  A plan points at the caller's
+// keypairs and never copies key bytes.
 #pragma once
 #include <stddef.h>
 #include <stdint.h>

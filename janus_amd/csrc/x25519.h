@@ -1,6 +1,6 @@
 // X25519 (RFC 7748 §5) for one lane: GF(2^255 - 19) in ten unsigned limbs and the Montgomery ladder
-// the DH kernels run per report (hpke_gpu.h: k_x25519, helper_request.h: k_x25519_idx,
-// hpke_seal_gpu.h: k_x25519_eph).  Free of HIP: the kernels and a CPU test
+// the DH kernels run per report (hpke_dh_gpu.h: k_x25519, k_x25519_idx and
+// k_x25519_eph).  Free of HIP: the kernels and a CPU test
 // (tests/native/hpke_lane_host.cpp) run the same text; DEVI is sha256.h's.
 #pragma once
 #include "sha256.h"

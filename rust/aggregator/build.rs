@@ -45,9 +45,18 @@ fn main() {
         .arg("-o")
         .arg(out.join("libprio3gpu.so"))
         .args(
-            ["engine.hip", "engine_hpke.hip", "engine_hpke_split.hip", "codec.cpp", "hpke.cpp"]
-                .iter()
-                .map(|f| csrc.join(f)),
+            [
+                "engine.hip",
+                "engine_hpke.hip",
+                "engine_hpke_dh.hip",
+                "engine_hpke_seal.hip",
+                "engine_hpke_team.hip",
+                "engine_hpke_split.hip",
+                "codec.cpp",
+                "hpke.cpp",
+            ]
+            .iter()
+            .map(|f| csrc.join(f)),
         )
         .args(["-lrccl", "-lcrypto"])
         .status()

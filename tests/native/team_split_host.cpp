@@ -106,7 +106,7 @@ static void powers(const uint32_t h[4], uint32_t* tbl) {  // the shell's order: 
     for (uint32_t lane = 0; lane < kLanes; ++lane) gf128_powers_step(tbl, lane, half);
 }
 
-// hpke_open_team.h's poly_team_sum: the butterfly's steps 1, 2, 4, a carry pass, 8, 16, 32, a
+// hpke_team_wave.h's poly_team_sum: the butterfly's steps 1, 2, 4, a carry pass, 8, 16, 32, a
 // carry pass, in 32 bits.  false if the lanes do not end alike.
 static bool team_sum(std::vector<PolyTeam>& t, uint32_t sum[5]) {
   uint32_t h[kLanes][5], g[kLanes][5];

@@ -77,8 +77,10 @@ def kernels(co):
 
 def disasm(co, name):
     txt = sh(LLVM / "llvm-objdump", "-d", "--no-show-raw-insn", f"--disassemble-symbols={name}", co)
-    return [re.sub(r"^\s*", "", re.sub(r"\s*//.*$", "", l)) for l in txt.splitlines()
-            if l.startswith("\t") or l.startswith("  ")]
+    lines = [re.sub(r"^\s*", "", re.sub(r"\s*//.*$", "", l)) for l in txt.splitlines()
+             if l.startswith("\t") or l.startswith("  ")]
+    # objdump prints "..." for the zero padding after an object's last kernel: no instruction
+    return [l for l in lines if l != "..."]
 
 
 def main():

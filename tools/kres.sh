@@ -1,7 +1,8 @@
 #!/bin/bash
 # Print VGPR / occupancy of the main kernels (compile-only, no GPU):  tools/kres.sh [pattern]
 C=$(cd "$(dirname "$0")/.." && pwd)/janus_amd/csrc
-for unit in engine.hip engine_hpke.hip engine_hpke_split.hip; do
+for unit in engine.hip engine_hpke.hip engine_hpke_dh.hip engine_hpke_seal.hip \
+    engine_hpke_team.hip engine_hpke_split.hip; do
   hipcc --offload-arch=gfx950 -O3 -std=c++17 -fPIC -c --cuda-device-only -Rpass-analysis=kernel-resource-usage \
     -o /tmp/kres.o "$C/$unit" 2>&1
 done | python3 -c '
